@@ -19,9 +19,14 @@ What is timed is ALWAYS the steady state of SURVEY.md 8d (mirrors mega_core/engi
 --warmup says: an internal pre-roll runs the cold start (frame 0: 13 local + 10 global frames) and then key frames
 until (i) the local window, the global pool and the 25-entry memory deques of all three stages are full and (ii) the
 steady frame-stage / aggregation hipGraphs have been captured AND replayed; --warmup only lengthens it.  The timed
-region is then R blocks of EXACTLY --steps key frames, each block bracketed by barrier + synchronize on both sides
-(R chosen so that the blocks cover >= ~1 s); `value` / `ms_per_step` are the MEDIAN block (all block times are in
-`config.timed_blocks_ms`).  The engine's graph statistics must not change inside the timed region (asserted).
+region is then ONE block of EXACTLY --steps steps, bracketed by barrier + synchronize on both sides: --steps is the
+number of timed steps.  (--min-seconds S repeats such blocks until they cover S seconds, for A/B runs; `value` /
+`ms_per_step` are then the MEDIAN block, and all block times are in `config.timed_blocks_ms`.)  The engine's graph
+statistics must not change inside the timed region (asserted).
+--dump-outputs DIR writes the detections of the last timed step (what ClipEngine.run hands its caller: the boxes
+and every field of each key frame's BoxList) as DIR/<name>.npy in float32 / float64.  Weights, clip and global-frame
+schedule are seeded, so the same arguments give the same inputs on every run and two builds can be compared output
+for output (with the default single block the last timed step is always the same key frame of the clip).
 N>1: a step is N key frames of the video (one per rank: "weak" scaling, per-GPU work fixed); the frame stage of each
 step-batch (20 N key frames = 40 N frames, 40 per rank) is sharded over the ranks and the fixed-size frame records are
 exchanged with one RCCL all-gather per row-count group; the key frames' aggregation is dealt to the ranks, the memory
@@ -103,7 +108,11 @@ def parse():
     ap.add_argument("--ramp", action="store_true",
                     help="short first / last step-batch inside a timed block (ClipEngine ramp; measured slower: 555 vs 585 FPS)")
     ap.add_argument("--cpu-frames", type=int, default=3, help="steady key frames timed by the CPU baseline (memory full)")
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="the timed blocks cover at least this long")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until the blocks cover at least this long (value = median "
+                         "block); default 0: one block, i.e. exactly --steps timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the detections of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / reporting only (no model, no kernels; gloo when there is no HIP device): "
                          "proves the --gpus N self-launch and the n_gpus bookkeeping on a CPU box (tests/test_bench_cli.py)")
@@ -242,6 +251,30 @@ def make_clip(T, H, W, device, unique=16):
     base = synth.make_clip(min(unique, T), H, W, seed=0).to(device)
     idx = torch.arange(T, device=device) % base.shape[0]
     return base.index_select(0, idx).contiguous()
+
+
+def dump_outputs(path, step):
+    """--dump-outputs: `step` = [(key frame, BoxList)] of the last timed step -> path/<name>.npy, the rows of its key
+    frames concatenated: boxes.npy [N, 4], one file per BoxList field (scores, labels, ...) and key_frame.npy (the key
+    frame of each row).  Integer fields are written as float64 (exact), floating ones as float32.  At most a few hundred
+    detections per key frame: far below 64 MB.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cols = {"key_frame": [], "boxes": []}
+    for i, det in step:
+        cols["key_frame"].append(np.full((len(det),), i, dtype=np.float64))
+        cols["boxes"].append(det.bbox.detach().float().cpu().numpy())
+        for f in det.fields():
+            v = det.get_field(f)
+            if torch.is_tensor(v):
+                v = v.detach().cpu()
+                cols.setdefault(f, []).append((v.float() if v.is_floating_point() and v.dtype != torch.float64 else v.double()).numpy())
+    shapes = {}
+    for name, parts in cols.items():
+        a = np.concatenate(parts) if parts else np.zeros((0,), dtype=np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def cpu_baseline(arch, sd, H, W, n_timed):
@@ -629,11 +662,17 @@ def main():
         runner.host_times[k] = 0
     fc_before = runner.frames_computed
 
-    # ---- timed region: blocks of EXACTLY K key frames, each bracketed by barrier + synchronize
+    # ---- timed region: one block of EXACTLY K steps (--min-seconds: more such blocks), bracketed by barrier + synchronize
+    block_dets = {}          # --dump-outputs: key frame -> detections of the newest timed block on this rank
+
+    def keep_det(i, det):
+        block_dets[i] = det
+
     def timed_block(first):
+        block_dets.clear()
         barrier()
         t0 = time.perf_counter()
-        d = runner.run(clip, T, gfor, first=first, last=first + KF)
+        d = runner.run(clip, T, gfor, first=first, last=first + KF, on_step=keep_det if args.dump_outputs else None)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -669,6 +708,11 @@ def main():
     if not args.no_graphs:
         assert captures_in_region == 0, "a frame-stage batch ran eagerly / was captured inside the timed region: %s -> %s" % (st0, st1)
     assert st1["pools_full"], "pools not full in the timed region: %s" % (st1,)
+    dumped = None
+    if args.dump_outputs and rank == 0:      # the last step = the last `world` key frames of the last block
+        dumped = dump_outputs(args.dump_outputs, [(i, block_dets[i]) for i in range(pos - world, pos) if i in block_dets])
+        log("outputs of the last timed step (key frames %d..%d) written to %s: %s" % (pos - world, pos - 1, args.dump_outputs,
+                                                                                      dumped))
     ht = dict(runner.host_times)
     log("host ms/step: frame-stage enqueue %.3f, aggregation enqueue %.3f (of which waiting for the frame stage %.3f), "
         "waiting for results %.3f" % tuple(1e3 * ht[k] / max(ht["steps"], 1)
@@ -929,7 +973,10 @@ def main():
                        "graph_captures_in_timed_region": captures_in_region,
                        "engine_state_before": st0, "engine_state_after": st1,
                        "timed_blocks": len(blocks), "timed_blocks_ms": [round(1e3 * b, 2) for b in blocks],
-                       "value_is": "median block (each block = exactly --steps steps between barrier+synchronize)",
+                       "timed_steps": K * len(blocks),
+                       "value_is": "median block (each block = exactly --steps steps between barrier+synchronize; one block "
+                                   "unless --min-seconds asks for more)",
+                       "dumped_outputs": dumped,
                        "clip": "16 unique synthetic frames repeated (only the RPN NMS's early stop depends on frame content)",
                        "frames_through_frame_stage_per_key_frame": round(
                            (runner_frames_after - fc_before) / (KF * len(blocks)), 2),

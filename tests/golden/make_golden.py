@@ -16,6 +16,8 @@
 5. ref_base_r50.npz / ref_rdn_r50.npz / ref_feed.npz -- see golden_base / golden_rdn / golden_feed.
 4. ref_fgfa_r50.npz -- GeneralizedRCNNFGFA (configs/FGFA/vid_R_50_C4_FGFA_1x.yaml) on a 128x192 clip: flow field,
    aggregated feature map, predictor logits and final detections per key frame.
+6. ref_live.npz -- value types and small host functions (BoxList, cat_boxlist, to_image_list, Pooler, cell anchors,
+   VIDTestDistributedSampler) on seeded inputs: see golden_live.
 """
 import importlib.util
 import os
@@ -430,6 +432,103 @@ def golden_checkpoint():
         json.dump(out, f, indent=0, sort_keys=True)
 
 
+def golden_live():
+    """ref_live.npz: seeded inputs and what the reference's value types and small host functions return for them --
+    BoxList (bounding_box.py: clip_to_image, indexing, fields, copy_with_fields), cat_boxlist, to_image_list,
+    Pooler.convert_to_roi_format, the R-50 MEGA model's cell anchors and state_dict layout, the attributes a pickled
+    BoxList carries, and the frame ranges VIDTestDistributedSampler hands each rank (tests/test_against_reference_live.py,
+    tests/test_inference_loop.py)."""
+    ref_shim.install()
+    import mega_core.structures.bounding_box as bb
+    import mega_core.structures.boxlist_ops as bops
+    import mega_core.structures.image_list as il
+    import mega_core.modeling.poolers as poolers
+    from mega_core.data.samplers.distributed import VIDTestDistributedSampler
+
+    def boxes(n, seed):
+        g = torch.Generator().manual_seed(seed)
+        c = torch.rand((n, 2), generator=g) * torch.tensor([300., 200.]) - 20
+        wh = torch.rand((n, 2), generator=g) * 120 - 10          # some degenerate / out-of-image boxes on purpose
+        return torch.cat([c, c + wh], dim=1)
+    out = {}
+    # ---- BoxList semantics: clip_to_image (in place, remove_empty), indexing, fields, copy_with_fields
+    for seed in range(5):
+        b = boxes(40, seed)
+        s = torch.rand(40, generator=torch.Generator().manual_seed(100 + seed))
+        out["bl%d_boxes" % seed], out["bl%d_scores" % seed] = b.numpy(), s.numpy()
+        for remove_empty in (False, True):
+            t2 = bb.BoxList(b.clone(), (256, 160), "xyxy")
+            t2.add_field("scores", s.clone())
+            to_ = t2.clip_to_image(remove_empty)
+            k = "bl%d_clip%d_" % (seed, remove_empty)
+            out[k + "bbox"], out[k + "scores"], out[k + "inplace_bbox"] = \
+                to_.bbox.numpy(), to_.get_field("scores").numpy(), t2.bbox.numpy()
+        theirs = bb.BoxList(b.clone(), (256, 160), "xyxy")
+        theirs.add_field("scores", s.clone())
+        theirs.add_field("labels", torch.arange(40))
+        sub = theirs[torch.tensor([3, 1, 7])]
+        out["bl%d_idx_bbox" % seed], out["bl%d_idx_labels" % seed] = sub.bbox.numpy(), sub.get_field("labels").numpy()
+        out["bl%d_keep_bbox" % seed] = theirs[s > 0.5].bbox.numpy()
+        c2 = theirs.copy_with_fields(["scores"])
+        out["bl%d_copy_bbox" % seed], out["bl_copy_fields"] = c2.bbox.numpy(), np.array(c2.fields())
+        out["bl_fields"], out["bl_size"], out["bl_mode"] = np.array(theirs.fields()), np.array(theirs.size), np.array(theirs.mode)
+    # ---- cat_boxlist, to_image_list
+    a, b = boxes(5, 1), boxes(7, 2)
+    g = torch.Generator().manual_seed(7)
+    fa, fb, img = torch.rand(5, generator=g), torch.rand(7, generator=g), torch.rand((3, 37, 53), generator=g)
+    out.update(cat_a=a.numpy(), cat_b=b.numpy(), cat_fa=fa.numpy(), cat_fb=fb.numpy(), img=img.numpy())
+
+    def mk(x, f):
+        bl = bb.BoxList(x.clone(), (100, 80), "xyxy")
+        bl.add_field("scores", f.clone())
+        return bl
+    t = bops.cat_boxlist([mk(a, fa), mk(b, fb)])
+    out.update(cat_bbox=t.bbox.numpy(), cat_scores=t.get_field("scores").numpy(), cat_size=np.array(t.size))
+    for k, inp in enumerate((img, [img], (img,))):
+        ti = il.to_image_list(inp)
+        out["il%d_tensors" % k], out["il%d_sizes" % k] = ti.tensors.numpy(), np.array([tuple(x) for x in ti.image_sizes])
+    # ---- poolers.py:78-89 and the anchor generator's cell anchors as they sit in the R-50 MEGA model's state_dict
+    rb = [boxes(4, 3), boxes(2, 4)]
+    out["roi_boxes0"], out["roi_boxes1"] = rb[0].numpy(), rb[1].numpy()
+    out["roi_format"] = poolers.Pooler((7, 7), (1.0 / 16,), 0).convert_to_roi_format(
+        [bb.BoxList(x.clone(), (64, 64), "xyxy") for x in rb]).numpy()
+    rsd = ref_shim.build_model(ref_shim.make_cfg("configs/MEGA/vid_R_50_C4_MEGA_1x.yaml")).state_dict()
+    out["cell_anchors0"] = rsd["rpn.anchor_generator.cell_anchors.0"].numpy()
+    out["sd_keys"] = np.array(list(rsd.keys()))
+    out["sd_shapes"] = np.array([",".join(str(d) for d in v.shape) for v in rsd.values()])
+    # ---- the on-disk BoxList: attribute -> type of what the reference's constructor and add_field leave on it
+    bl = mk(a, fa)
+    out["boxlist_attrs"] = np.array(["%s:%s" % (k, type(v).__name__) for k, v in sorted(vars(bl).items())])
+    # ---- VIDTestDistributedSampler on random video-length lists: (start is None, first index, count) per world / rank
+    rng = np.random.RandomState(0)
+    worlds = (2, 3, 4, 8)
+    lens_all = np.zeros((40, 14), np.int64)
+    want_all = np.full((40, len(worlds), max(worlds), 3), -1, np.int64)
+
+    class _DS(object):
+        def __init__(self, lens):
+            self.start_index, n = [], 0
+            for l in lens:
+                self.start_index.append(n)
+                n += l
+            self.n = n
+
+        def __len__(self):
+            return self.n
+    for trial in range(40):
+        lens = rng.randint(1, 60, size=rng.randint(1, 14)).tolist()
+        lens_all[trial, :len(lens)] = lens
+        ds = _DS(lens)
+        for wi, world in enumerate(worlds):
+            for rank in range(world):
+                smp = VIDTestDistributedSampler(ds, num_replicas=world, rank=rank)
+                want = list(iter(smp))
+                assert want == list(range(want[0], want[0] + len(want))) if want else True
+                want_all[trial, wi, rank] = (smp.start is None, want[0] if want else -1, len(want))
+    out.update(sampler_lens=lens_all, sampler_worlds=np.array(worlds), sampler_want=want_all)
+    np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **out)
+
+
 def golden_configs():
     """ref_configs.json: for every reference config file this package mirrors, the values the REFERENCE's yacs tree
     holds (defaults.py merged with the yaml) for exactly the keys mega.pytorch_amd.config.get_cfg defines."""
@@ -559,3 +658,4 @@ if __name__ == "__main__":
     golden_dff()
     golden_checkpoint()
     golden_configs()
+    golden_live()

@@ -4,7 +4,9 @@
     (gloo here, nccl = RCCL when every rank has a device) and prints ONE line whose n_gpus comes from the live process group;
   * launched BY torch.distributed.run (the round driver's form) it must agree with WORLD_SIZE, else exit code 2;
   * `--gpus 2` on a box with fewer than 2 devices is refused (exit code 2) instead of silently reporting N = 1;
-  * the host-side prefetch of a sharded run asks for exactly the frames records_async computes on that rank.
+  * the host-side prefetch of a sharded run asks for exactly the frames records_async computes on that rank;
+  * on the GPU: `--steps K` times exactly K steps, and `--dump-outputs DIR` writes the last one's detections, the same
+    arrays on every run with the same arguments.
 Reference: one process per GPU, tools/test_net.py:41,:69-75.
 """
 import json
@@ -55,6 +57,37 @@ def test_driver_form_and_world_size_mismatch():
     assert line["n_gpus"] == 2 and line["config"]["key_frames_per_block"] == 20
     rc, out, err = _run(base + ["--gpus", "4", "--steps", "10", "--dry-run"])       # WORLD_SIZE 2, --gpus 4
     assert rc != 0 and "must agree" in err and not out.strip()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K steps (one block); --dump-outputs writes the detections of the last of them as float
+    .npy files, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    args = [sys.executable, BENCH, "--gpus", "1", "--arch", "R-50", "--steps", "3", "--warmup", "0", "--no-f32-leg",
+            "--no-h2d-leg", "--no-whole-clip", "--no-cpu-baseline", "--no-roofline"]
+    got = []
+    for run in range(2):
+        d = str(tmp_path / ("run%d" % run))
+        rc, out, err = _run(args + ["--dump-outputs", d])
+        assert rc == 0, err[-3000:]
+        lines = [l for l in out.splitlines() if l.strip()]
+        assert len(lines) == 1, out
+        line = json.loads(lines[0])
+        c = line["config"]
+        assert line["steps"] == 3 and c["timed_blocks"] == 1 and c["timed_steps"] == 3
+        files = sorted(os.listdir(d))
+        assert files == ["boxes.npy", "key_frame.npy", "labels.npy", "scores.npy"], files
+        a = {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        n = a["boxes"].shape[0]
+        assert n > 0 and a["boxes"].shape == (n, 4) and all(v.shape == (n,) for k, v in a.items() if k != "boxes")
+        assert c["dumped_outputs"] == {k: list(v.shape) for k, v in a.items()}
+        assert set(a["key_frame"].tolist()) == {c["pre_roll_key_frames"] + 2}     # the last of the 3 timed key frames
+        got.append(a)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
 
 
 def test_more_gpus_than_devices_is_refused():

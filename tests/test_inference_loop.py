@@ -1,8 +1,10 @@
 """Test-time loop + result gathering: index parsing, video-per-rank partition, predictions.pth in
 the reference's on-disk format, and the world-size-2 gather over gloo."""
 import os
+import pickle
 import sys
 import tempfile
+import types
 
 import numpy as np
 import pytest
@@ -12,7 +14,6 @@ import torch.multiprocessing as mp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 from mega.pytorch_amd import config, engine, inference, modeling, synth  # noqa: E402
 from oracle import pil_resize  # noqa: E402
@@ -102,16 +103,28 @@ def test_inference_writes_reference_format_predictions(monkeypatch, tmp_path):
     # round trip through the file
     back = inference.load_predictions(os.path.join(out, "predictions.pth"))
     assert len(back) == 12 and all(torch.equal(a.bbox, b.bbox) for a, b in zip(back, preds))
-    # ... and the reference itself unpickles it as ITS BoxList (the reference cannot travel to the GPU box)
-    import ref_shim
-    if ref_shim.available():
-        ref_shim.install()
-        from mega_core.structures.bounding_box import BoxList as RefBoxList
-        loaded = torch.load(os.path.join(out, "predictions.pth"), weights_only=False)
-        assert all(type(b) is RefBoxList for b in loaded)
-        assert loaded[3].mode == "xyxy" and loaded[3].size == (MAX_S, MIN_S)
-        assert torch.equal(loaded[3].get_field("scores"), preds[3].get_field("scores"))
-        assert len(loaded[3]) == len(preds[3]) and loaded[3].resize((W0, H0)).size == (W0, H0)
+    # ... and it unpickles as the reference's BoxList, carrying exactly the attributes (and their types) the
+    # reference's constructor and add_field leave on one (tests/golden/ref_live.npz)
+    seen = []
+
+    class _Stand(object):
+        pass
+
+    class _Unpickler(pickle.Unpickler):
+        def find_class(self, mod, name):
+            if (mod, name) == ("mega_core.structures.bounding_box", "BoxList"):
+                seen.append(name)
+                return _Stand
+            return super().find_class(mod, name)
+    loaded = torch.load(os.path.join(out, "predictions.pth"), weights_only=False,
+                        pickle_module=types.SimpleNamespace(Unpickler=_Unpickler, load=pickle.load, __name__="pickle"))
+    gold = np.load(os.path.join(HERE, "golden", "ref_live.npz"))
+    assert seen and len(loaded) == 12 and all(type(b) is _Stand for b in loaded)
+    assert all(sorted("%s:%s" % (k, type(v).__name__) for k, v in vars(b).items()) == gold["boxlist_attrs"].tolist()
+               for b in loaded)
+    assert loaded[3].mode == "xyxy" and loaded[3].size == (MAX_S, MIN_S)
+    assert torch.equal(loaded[3].extra_fields["scores"], preds[3].get_field("scores"))
+    assert torch.equal(loaded[3].bbox, preds[3].bbox) and list(loaded[3].extra_fields) == preds[3].fields()
 
 
 def _worker(rank, world, port, root, outdir):
@@ -149,40 +162,26 @@ def test_video_sharded_inference_world2(monkeypatch, tmp_path):
 
 
 def test_video_partition_equals_reference_sampler():
-    """videos_for_rank == the frame ranges mega_core.data.samplers.VIDTestDistributedSampler hands out (executed from
-    the reference tree when it is present: the build container), on random video-length lists and world sizes."""
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("needs /root/reference")
-    ref_shim.install()
-    from mega_core.data.samplers.distributed import VIDTestDistributedSampler
-
-    class _DS(object):
-        def __init__(self, lens):
-            self.start_index, n = [], 0
-            for l in lens:
-                self.start_index.append(n)
-                n += l
-            self.n = n
-
-        def __len__(self):
-            return self.n
+    """videos_for_rank == the frame ranges mega_core.data.samplers.VIDTestDistributedSampler hands out (recorded from
+    the reference in tests/golden/ref_live.npz), on random video-length lists and world sizes."""
+    gold = np.load(os.path.join(HERE, "golden", "ref_live.npz"))
     rng = np.random.RandomState(0)
     for trial in range(40):
         lens = rng.randint(1, 60, size=rng.randint(1, 14)).tolist()
-        ds = _DS(lens)
-        videos = [{"start": s, "seg_len": l, "pattern": str(i)} for i, (s, l) in enumerate(zip(ds.start_index, lens))]
-        for world in (2, 3, 4, 8):
+        assert lens == [l for l in gold["sampler_lens"][trial].tolist() if l]
+        starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).tolist()
+        videos = [{"start": s, "seg_len": l, "pattern": str(i)} for i, (s, l) in enumerate(zip(starts, lens))]
+        for wi, world in enumerate(gold["sampler_worlds"].tolist()):
             covered = []
             for rank in range(world):
-                smp = VIDTestDistributedSampler(ds, num_replicas=world, rank=rank)
-                if smp.start is None:
+                start_is_none, first, count = gold["sampler_want"][trial, wi, rank].tolist()
+                if start_is_none:
                     # the reference's find_zero fell off its list (offset inside the LAST video) and returned None;
                     # its slice [None:end] would then hand this rank the whole dataset again.  Here: nothing.
                     # (an end of None slices to the end of the dataset, which is what is meant: compared below)
                     assert inference.videos_for_rank(videos, rank, world) == []
                     continue
-                want = list(iter(smp))
+                want = list(range(first, first + count))
                 mine = inference.videos_for_rank(videos, rank, world)
                 got = [i for v in mine for i in range(v["start"], v["start"] + v["seg_len"])]
                 assert got == want, (lens, world, rank)
