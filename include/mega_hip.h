@@ -456,6 +456,30 @@ int mega_fgfa_warp_aggregate_ring_pos_batched(const void* feats, const float* fl
                                               int H, int W, int Cf, int Ce, const int* order, int key_pos, int G, int dtype,
                                               void* stream);
 
+/* ImageNet VID evaluation (AP50 and motion-specific AP).  Replaces the Python loops of
+ * mega_core/data/datasets/evaluation/vid/vid_eval.py:156-285 (calc_detection_vid_prec_rec) and :288-343
+ * (calc_detection_vid_ap, use_07_metric=False), for F frames, R motion ranges and C classes (labels 0 .. C-1).
+ * Matching: one wave per (frame, range).  Inputs, flat over frames:
+ *   det_box [N][4] f32 in the prediction's frame size, det_label [N] i32, det_off [F+1] i64 (frame f's detections are
+ *   det_off[f] .. det_off[f+1]), order [N] i32: detection indices, each frame's run ordered by label, then score
+ *   descending, then position descending; ratio [F][2] f32 = (annotation width / prediction width, height / height) as in
+ *   BoxList.resize (bounding_box.py:91-125); gt_box [G][4] f32, gt_label [G] i32, gt_off [F+1] i64; gt_motion [G] f64 or
+ *   NULL (NaN: the frame has no motion list, nothing is ignored); ranges [R][3] f64 = (lo, hi, empty_weight); max_gt = the
+ *   largest GT count of a frame (<= 4096).
+ * Outputs: match [R][N] u8, pred_ignore [R][N] f64 (indexed by detection), n_pos [R][C] i32 (non-ignored GT per class). */
+int mega_vid_eval_match(const float* det_box, const int* det_label, const long long* det_off, const int* order,
+                        const float* ratio, const float* gt_box, const int* gt_label, const double* gt_motion,
+                        const long long* gt_off, const double* ranges, int F, int R, int C, long long N, int max_gt,
+                        unsigned char* match, double* pred_ignore, int* n_pos, void* stream);
+/* Precision / recall / AP: one workgroup per (class, range) sweeps the class's detections in global order
+ * gorder[seg_off[l] .. seg_off[l+1]) (score descending, equal scores by descending position in the frame-by-frame
+ * concatenation): inclusive tp (integer) / fp (f64) scans, prec = tp / (fp + tp + 2^-52), rec = tp / n_pos, the
+ * precision envelope (suffix max) and AP = sum of (rec_j - rec_j-1) * envelope_j where recall changes.  ap [R][C] f64,
+ * NaN where n_pos is 0.  Workspace: mega_vid_eval_workspace_bytes(N, C, R) bytes. */
+size_t mega_vid_eval_workspace_bytes(long long N, int C, int R);
+int mega_vid_eval_ap(const unsigned char* match, const double* pred_ignore, const int* gorder, const long long* seg_off,
+                     const int* n_pos, int C, int R, long long N, double* ap, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

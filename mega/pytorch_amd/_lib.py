@@ -95,6 +95,9 @@ SIGNATURES = {
     "mega_flow_conv1_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong, c_int, c_int, c_void_p]),
     "mega_fgfa_warp_aggregate_ring_pos": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_int, c_void_p]),
     "mega_fgfa_warp_aggregate_ring_pos_batched": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mega_vid_eval_match": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_longlong, c_int] + [c_void_p] * 4),
+    "mega_vid_eval_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
+    "mega_vid_eval_ap": (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong] + [c_void_p] * 2 + [c_size_t, c_void_p]),
     "mega_last_error_string": (ctypes.c_char_p, []),
 }
 

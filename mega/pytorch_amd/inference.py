@@ -266,9 +266,12 @@ def load_predictions(path):
     return out
 
 
-def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, **kw):
-    """inference.py:72-134 up to (and including) predictions.pth; evaluation itself (datasets/evaluation) is the
-    reference's and consumes the returned list / the file unchanged."""
+def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, anno_path=None,
+              motion_iou=None, **kw):
+    """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
+    evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
+    result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
+    vid_eval.load_motion_iou() lists (motion-specific AP).  The return value is the list[BoxList] either way."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     device = torch.device(cfg.MODEL.DEVICE if device is None else device)
     dist = torch.distributed
@@ -291,4 +294,10 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
         save_predictions(predictions, os.path.join(output_folder, "predictions.pth"))
+    if anno_path is not None:
+        from . import vid_eval
+        if isinstance(motion_iou, str):
+            motion_iou = vid_eval.load_motion_iou(motion_iou)
+        vid_eval.evaluate_detections(predictions, vid_eval.VIDGroundTruth(img_index, anno_path), motion_iou=motion_iou,
+                                     output_folder=output_folder, device=device, logger=logger)
     return predictions

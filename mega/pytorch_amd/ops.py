@@ -1262,3 +1262,49 @@ def avgpool2x2_ceil(x):
     rc = lib.mega_avgpool2x2_ceil_nhwc(_ptr(x), _ptr(out), N, H, W, C, _dt(x), _stream())
     _lib.check(rc, "mega_avgpool2x2_ceil_nhwc")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ VID evaluation
+def vid_eval_match(det_box, det_label, det_off, order, ratio, gt_box, gt_label, gt_motion, gt_off, ranges, C, max_gt):
+    """vid_eval.py:156-253 matching for F frames and R motion ranges (include/mega_hip.h mega_vid_eval_match).
+    det_box [N,4] f32, det_label [N] i32, det_off [F+1] i64, order [N] i32, ratio [F,2] f32, gt_box [G,4] f32,
+    gt_label [G] i32, gt_motion [G] f64 or None, gt_off [F+1] i64, ranges [R,3] f64 (lo, hi, empty_weight).
+    -> match [R,N] u8, pred_ignore [R,N] f64, n_pos [R,C] i32 (all on the device)."""
+    _gpu(det_box, det_label, det_off, order, ratio, gt_box, gt_label, gt_motion, gt_off, ranges)
+    lib = _lib.load()
+    N, F, R = det_box.shape[0], det_off.shape[0] - 1, ranges.shape[0]
+    for t, dt in ((det_box, torch.float32), (det_label, torch.int32), (det_off, torch.int64), (order, torch.int32),
+                  (ratio, torch.float32), (gt_box, torch.float32), (gt_label, torch.int32), (gt_motion, torch.float64),
+                  (gt_off, torch.int64), (ranges, torch.float64)):
+        assert t is None or (t.dtype == dt and t.is_contiguous())
+    dev = det_box.device
+    match = torch.empty((R, N), dtype=torch.uint8, device=dev)
+    pign = torch.empty((R, N), dtype=torch.float64, device=dev)
+    n_pos = torch.empty((R, C), dtype=torch.int32, device=dev)
+    _tok = _pb("vid_eval_match")
+    rc = lib.mega_vid_eval_match(_ptr(det_box), _ptr(det_label), _ptr(det_off), _ptr(order), _ptr(ratio), _ptr(gt_box),
+                                 _ptr(gt_label), _ptr(gt_motion), _ptr(gt_off), _ptr(ranges), F, R, int(C), N, int(max_gt),
+                                 _ptr(match), _ptr(pign), _ptr(n_pos), _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_vid_eval_match")
+    return match, pign, n_pos
+
+
+def vid_eval_ap(match, pred_ignore, gorder, seg_off, n_pos):
+    """vid_eval.py:255-343: per (range, class) precision / recall scans and AP over the classes' detections in global
+    order gorder[seg_off[l] : seg_off[l+1]].  -> ap [R,C] f64 on the device (NaN where n_pos == 0)."""
+    _gpu(match, pred_ignore, gorder, seg_off, n_pos)
+    lib = _lib.load()
+    R, C = n_pos.shape
+    N = match.shape[1]
+    assert match.dtype == torch.uint8 and pred_ignore.dtype == torch.float64 and gorder.dtype == torch.int32
+    assert seg_off.dtype == torch.int64 and n_pos.dtype == torch.int32 and seg_off.shape[0] == C + 1
+    ap = torch.empty((R, C), dtype=torch.float64, device=match.device)
+    nb = lib.mega_vid_eval_workspace_bytes(N, C, R)
+    ws = _ws(nb, match.device)
+    _tok = _pb("vid_eval_ap")
+    rc = lib.mega_vid_eval_ap(_ptr(match), _ptr(pred_ignore), _ptr(gorder), _ptr(seg_off), _ptr(n_pos), C, R, N, _ptr(ap),
+                              _ptr(ws), nb, _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_vid_eval_ap")
+    return ap

@@ -1,0 +1,337 @@
+"""ImageNet VID evaluation: AP50 and motion-specific AP ("fast" / "medium" / "slow") of a list[BoxList], the step the
+reference's inference() ends with (mega_core/engine/inference.py:129-132, inference_no_model :135-160).
+
+Mirror of  mega_core/data/datasets/vid.py:22-40, :139-192        class lists, _preprocess_annotation, annotation cache
+           mega_core/data/datasets/evaluation/vid/vid_eval.py      do_vid_evaluation / eval_detection_vid /
+                                                                   calc_detection_vid_prec_rec / calc_detection_vid_ap
+
+What changes: the per-frame / per-class / per-detection Python loops run as two HIP kernels (csrc/vid_eval.hip): one wave
+per (frame, motion range) matches detections to GT boxes, one workgroup per (class, motion range) scans precision /
+recall and reduces AP.  The predictions are packed into flat arrays on the host and copied to the device once.
+
+What is defined here where the reference leaves it to the platform:
+  - ORDER ON TIES.  The reference sorts with numpy's argsort()[::-1], whose order of equal scores depends on numpy's sort
+    implementation.  Here equal scores are ordered by DESCENDING position: within a frame, the position in the
+    prediction list; per class over the dataset, the position in the frame-by-frame concatenation (of the frames' already
+    ordered detections).  This is a stable ascending argsort reversed -- what numpy gives for runs of 16 or fewer.
+  - Motion IoUs are read into per-frame lists (load_motion_iou); the reference's np.array over those ragged lists
+    (vid_eval.py:133-137) fails on numpy >= 1.24.
+  - empty_weight (the pred_ignore of a detection whose class has no GT box in its frame) is, as in the reference, the
+    fraction of ALL entries of the motion file inside the range, even when fewer frames are evaluated.
+Not provided (a clear error): box_only proposal recall (eval_proposals_vid) and the VOC07 11-point metric.
+There is no CPU path: the matching and the AP reduction run on a HIP device.
+"""
+import logging
+import os
+import warnings
+import xml.etree.ElementTree as ET
+
+import numpy as np
+import torch
+
+from .structures import BoxList
+
+CLASSES = ['__background__',  # always index 0
+           'airplane', 'antelope', 'bear', 'bicycle',
+           'bird', 'bus', 'car', 'cattle',
+           'dog', 'domestic_cat', 'elephant', 'fox',
+           'giant_panda', 'hamster', 'horse', 'lion',
+           'lizard', 'monkey', 'motorcycle', 'rabbit',
+           'red_panda', 'sheep', 'snake', 'squirrel',
+           'tiger', 'train', 'turtle', 'watercraft',
+           'whale', 'zebra']
+CLASSES_MAP = ['__background__',  # always index 0
+               'n02691156', 'n02419796', 'n02131653', 'n02834778',
+               'n01503061', 'n02924116', 'n02958343', 'n02402425',
+               'n02084071', 'n02121808', 'n02503517', 'n02118333',
+               'n02510455', 'n02342885', 'n02374451', 'n02129165',
+               'n01674464', 'n02484322', 'n03790512', 'n02324045',
+               'n02509815', 'n02411705', 'n01726692', 'n02355227',
+               'n02129604', 'n04468005', 'n01662784', 'n04530566',
+               'n02062744', 'n02391049']
+CLASSES_TO_IND = dict(zip(CLASSES_MAP, range(len(CLASSES_MAP))))
+
+# vid_eval.py:39-44
+MOTION_RANGES = [[0.0, 1.0], [0.0, 0.7], [0.7, 0.9], [0.9, 1.0]]
+MOTION_NAMES = ["all", "fast", "medium", "slow"]
+MAX_GT_PER_FRAME = 4096     # the matching kernel keeps 64 selected flags per lane
+
+
+def parse_annotation(root, classes_to_ind=CLASSES_TO_IND):
+    """vid.py:139-166 (_preprocess_annotation) on a parsed XML root -> {"boxes": [n,4] f32, "labels": [n] i64,
+    "im_info": (height, width)}.  An object is kept when its raw name is a known wnid; its box is clipped to the frame."""
+    size = root.find("size")
+    im_info = tuple(map(int, (size.find("height").text, size.find("width").text)))
+    boxes, labels = [], []
+    for obj in root.findall("object"):
+        if obj.find("name").text not in classes_to_ind:
+            continue
+        bb = obj.find("bndbox")
+        boxes.append([max(float(bb.find("xmin").text), 0.0), max(float(bb.find("ymin").text), 0.0),
+                      min(float(bb.find("xmax").text), im_info[1] - 1), min(float(bb.find("ymax").text), im_info[0] - 1)])
+        labels.append(classes_to_ind[obj.find("name").text.lower().strip()])
+    return {"boxes": np.asarray(boxes, dtype=np.float32).reshape(-1, 4), "labels": np.asarray(labels, dtype=np.int64),
+            "im_info": im_info}
+
+
+class VIDGroundTruth(object):
+    """The GT boxes of every frame of a VID index file (inference.VIDTestIndex), flat: boxes [G,4] f32, labels [G] i64,
+    off [F+1] (frame i's boxes are off[i] .. off[i+1]), height / width [F] (the annotation's frame size).
+
+    cache: an optional .npz path.  When it exists and lists the same frames it is read instead of the XML files; else it
+    is written after parsing (what the reference's <image_set>_anno.pkl is for, vid.py:168-192)."""
+
+    classes = CLASSES
+
+    def __init__(self, img_index, anno_path, cache=None):
+        from .inference import VIDTestIndex
+        self.image_set_index = list(VIDTestIndex(img_index).image_set_index)
+        if cache and os.path.exists(cache):
+            z = np.load(cache, allow_pickle=False)
+            if list(z["image_set_index"]) == self.image_set_index:
+                self._set(z["boxes"], z["labels"], z["off"], z["height"], z["width"])
+                return
+            logging.getLogger("mega.pytorch_amd.vid_eval").warning("%s lists other frames: re-reading the XML files", cache)
+        annos = [parse_annotation(ET.parse(os.path.join(anno_path, name + ".xml")).getroot())
+                 for name in self.image_set_index]
+        self._set_annos(annos)
+        if cache:
+            d = os.path.dirname(os.path.abspath(cache))
+            os.makedirs(d, exist_ok=True)
+            np.savez(cache, image_set_index=np.asarray(self.image_set_index), boxes=self.boxes, labels=self.labels,
+                     off=self.off, height=self.height, width=self.width)
+
+    @classmethod
+    def from_annotations(cls, annos):
+        """From a list of parse_annotation() dicts (one per frame)."""
+        self = cls.__new__(cls)
+        self.image_set_index = None
+        self._set_annos(annos)
+        return self
+
+    def _set_annos(self, annos):
+        n = [len(a["labels"]) for a in annos]
+        off = np.zeros(len(annos) + 1, dtype=np.int64)
+        off[1:] = np.cumsum(n)
+        boxes = np.concatenate([np.asarray(a["boxes"], np.float32).reshape(-1, 4) for a in annos]) if annos else \
+            np.zeros((0, 4), np.float32)
+        labels = np.concatenate([np.asarray(a["labels"], np.int64).reshape(-1) for a in annos]) if annos else \
+            np.zeros((0,), np.int64)
+        self._set(boxes, labels, off, [a["im_info"][0] for a in annos], [a["im_info"][1] for a in annos])
+
+    def _set(self, boxes, labels, off, height, width):
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+        self.labels = np.ascontiguousarray(labels, dtype=np.int64)
+        self.off = np.ascontiguousarray(off, dtype=np.int64)
+        self.height = np.asarray(height, dtype=np.int64)
+        self.width = np.asarray(width, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.off) - 1
+
+    def get_img_info(self, idx):
+        return {"height": int(self.height[idx]), "width": int(self.width[idx])}
+
+    def get_groundtruth(self, idx):
+        """vid.py:220-227: BoxList of frame idx in the annotation's size, field "labels"."""
+        s, e = self.off[idx], self.off[idx + 1]
+        b = BoxList(torch.from_numpy(self.boxes[s:e].copy()), (int(self.width[idx]), int(self.height[idx])))
+        b.add_field("labels", torch.from_numpy(self.labels[s:e].copy()))
+        return b
+
+    def map_class_id_to_class_name(self, class_id):
+        return self.classes[class_id]
+
+
+def load_motion_iou(path):
+    """vid_groundtruth_motion_iou.mat -> list (one entry per frame) of f64 arrays, entry j of frame i =
+    m['motion_iou'][i][0][j][0], or 0 where that cell is empty (the values vid_eval.py:133-137 means to build).  In the
+    reference's file frame i is an [n_gt x 1] array, and a frame without GT boxes a [1 x 0] one: one entry, 0."""
+    import scipy.io as sio
+    m = sio.loadmat(path)["motion_iou"]
+    out = []
+    for i in range(len(m)):
+        cells = m[i][0]
+        out.append(np.asarray([float(cells[j][0]) if len(cells[j]) != 0 else 0.0 for j in range(len(cells))],
+                              dtype=np.float64))
+    return out
+
+
+def empty_weights(motion_iou, motion_ranges):
+    """vid_eval.py:163-168: per range, the fraction of ALL motion entries (every frame of the file) inside [lo, hi];
+    0 when that fraction is 1 or without motion IoUs."""
+    if motion_iou is None:
+        return [0.0] * len(motion_ranges)
+    allm = np.concatenate([np.asarray(m, np.float64).reshape(-1) for m in motion_iou]) if len(motion_iou) else np.zeros(0)
+    if allm.size == 0:
+        raise ValueError("the motion IoU list holds no entries")
+    out = []
+    for lo, hi in motion_ranges:
+        w = int(np.count_nonzero((allm >= lo) & (allm <= hi))) / float(allm.size)
+        out.append(0.0 if w == 1 else w)
+    return out
+
+
+def format_result(result, classes=CLASSES, motion_names=None):
+    """do_vid_evaluation's result text (vid_eval.py:53-64), byte for byte."""
+    names = motion_names or (MOTION_NAMES if len(result) == len(MOTION_NAMES) else MOTION_NAMES[:len(result)])
+    s = ""
+    for mi in range(len(names)):
+        s += 'AP50 | motion={:>6s} = {:0.4f}\n'.format(names[mi], result[mi]["map"])
+    s += "Category AP:\n"
+    for i, ap in enumerate(result[0]["ap"]):
+        if i == 0:  # skip background
+            continue
+        s += "{:<16}: {:.4f}\n".format(classes[i], ap)
+    return s
+
+
+def _pack(predictions, groundtruth, motion_iou, motion_ranges):
+    """Flat host arrays of the whole evaluation, in one byte buffer (one host-to-device copy)."""
+    F = len(predictions)
+    if F == 0:
+        raise ValueError("evaluate_detections: no predictions")
+    if len(groundtruth) != F:
+        raise ValueError("Length of gt and pred lists need to be same (%d predictions, %d GT frames)" % (F, len(groundtruth)))
+    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
+    det_off = np.zeros(F + 1, np.int64)
+    det_off[1:] = np.cumsum(counts)
+    N = int(det_off[-1])
+    if N:
+        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
+        scores = torch.cat([p.get_field("scores").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
+        labels = torch.cat([p.get_field("labels").reshape(-1).to("cpu", torch.int64) for p in predictions]).numpy()
+    else:
+        boxes, scores, labels = np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64)
+    if not np.isfinite(boxes).all():
+        raise ValueError("evaluate_detections: a prediction box is not finite")
+    if np.isnan(scores).any():
+        raise ValueError("evaluate_detections: a prediction score is NaN")
+    gl = groundtruth.labels
+    if (N and labels.min() < 0) or (gl.size and gl.min() < 0):
+        raise ValueError("evaluate_detections: negative class label")
+    if not np.isfinite(groundtruth.boxes).all():
+        raise ValueError("evaluate_detections: a GT box is not finite")
+    C = int(max(labels.max() if N else -1, gl.max() if gl.size else -1)) + 1     # n_fg_class = max(seen) + 1
+    if C <= 0:
+        raise ValueError("evaluate_detections: no class occurs in the predictions or the GT")
+    gcount = np.diff(groundtruth.off)
+    max_gt = int(gcount.max()) if F else 0
+    if max_gt > MAX_GT_PER_FRAME:
+        raise ValueError("evaluate_detections: a frame holds %d GT boxes (at most %d)" % (max_gt, MAX_GT_PER_FRAME))
+    # BoxList.resize (bounding_box.py:95): ratios as Python floats, applied in f32
+    pw = np.asarray([float(p.size[0]) for p in predictions])
+    ph = np.asarray([float(p.size[1]) for p in predictions])
+    ratio = np.stack([groundtruth.width / pw, groundtruth.height / ph], axis=1).astype(np.float32)
+    G = int(groundtruth.off[-1])
+    motion = None
+    if motion_iou is not None:
+        if len(motion_iou) < F:
+            raise ValueError("the motion IoU list covers %d frames, %d are evaluated" % (len(motion_iou), F))
+        motion = np.full(G, np.nan, np.float64)       # NaN: the frame has no motion list, nothing is ignored
+        for i in np.nonzero(gcount)[0]:
+            m = motion_iou[i]
+            if len(m) == 0:
+                continue
+            if len(m) < gcount[i]:
+                raise ValueError("frame %d: %d GT boxes, %d motion IoUs" % (i, gcount[i], len(m)))
+            motion[groundtruth.off[i]:groundtruth.off[i + 1]] = np.asarray(m, np.float64)[:gcount[i]]
+    ranges = np.asarray([[lo, hi, w] for (lo, hi), w in zip(motion_ranges, empty_weights(motion_iou, motion_ranges))],
+                        np.float64)
+    parts = [("det_box", boxes.astype(np.float32)), ("score", (scores + np.float32(0)).astype(np.float32)),   # -0 -> +0
+             ("det_label", labels.astype(np.int32)), ("det_off", det_off), ("ratio", ratio),
+             ("gt_box", groundtruth.boxes), ("gt_label", gl.astype(np.int32)), ("gt_off", groundtruth.off),
+             ("ranges", ranges)]
+    if motion is not None:
+        parts.append(("gt_motion", motion))
+    layout, off = [], 0
+    for name, a in parts:
+        a = np.ascontiguousarray(a)
+        layout.append((name, a, off))
+        off += (a.nbytes + 15) // 16 * 16
+    buf = np.empty(max(off, 16), np.uint8)
+    for name, a, o in layout:
+        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    meta = {"F": F, "N": N, "C": C, "max_gt": max_gt, "counts": counts}
+    return buf, [(name, a.dtype, a.shape, o) for name, a, o in layout], meta
+
+
+def _torch_dtype(dt):
+    return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
+            np.dtype(np.int64): torch.int64}[np.dtype(dt)]
+
+
+def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_only=False):
+    """The kernels' outputs (numpy): match [R,N] u8 and pred_ignore [R,N] f64 per detection (flat, frame by frame, in
+    each BoxList's order), n_pos [R,C] i32, ap [R,C] f64, with R = 4 motion ranges (1 without motion IoUs).
+    ap_only: copy back only ap (the per-detection arrays stay on the device and are freed)."""
+    from . import ops
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    motion_ranges = MOTION_RANGES if motion_iou is not None else MOTION_RANGES[:1]
+    buf, layout, meta = _pack(predictions, groundtruth, motion_iou, motion_ranges)
+    F, N, C = meta["F"], meta["N"], meta["C"]
+    dbuf = torch.from_numpy(buf).to(dev)
+    t = {}
+    for name, dt, shape, o in layout:
+        n = int(np.prod(shape))
+        t[name] = dbuf[o:o + n * np.dtype(dt).itemsize].view(_torch_dtype(dt)).reshape(shape)
+    labels = t["det_label"]
+    scores = t["score"]
+    if N:
+        # within-frame order: frame, label, score descending, position descending
+        rev = torch.arange(N - 1, -1, -1, device=dev)
+        perm = rev[torch.sort(scores[rev], descending=True, stable=True).indices]
+        fid = torch.repeat_interleave(torch.arange(F, device=dev), torch.from_numpy(meta["counts"]).to(dev),
+                                      output_size=N)
+        key = fid * C + labels.long()
+        order = perm[torch.sort(key[perm], stable=True).indices]
+        # per class over the dataset: score descending, then descending position in that frame-by-frame concatenation
+        rev2 = order.flip(0)
+        perm2 = rev2[torch.sort(scores[rev2], descending=True, stable=True).indices]
+        gorder = perm2[torch.sort(labels[perm2], stable=True).indices]
+        order, gorder = order.int(), gorder.int()
+        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+        seg_off[1:] = torch.cumsum(torch.bincount(labels.long(), minlength=C), 0)
+    else:
+        order = gorder = torch.zeros(0, dtype=torch.int32, device=dev)
+        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        match, pign, n_pos = ops.vid_eval_match(t["det_box"], labels, t["det_off"], order, t["ratio"], t["gt_box"],
+                                                t["gt_label"], t.get("gt_motion"), t["gt_off"], t["ranges"], C,
+                                                meta["max_gt"])
+        ap = ops.vid_eval_ap(match, pign, gorder, seg_off, n_pos)
+    if ap_only:
+        return {"ap": ap.cpu().numpy()}
+    return {"match": match.cpu().numpy(), "pred_ignore": pign.cpu().numpy(), "n_pos": n_pos.cpu().numpy(),
+            "ap": ap.cpu().numpy()}
+
+
+def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder=None, device="cuda", box_only=False,
+                        use_07_metric=False, logger=None):
+    """eval_detection_vid (+ do_vid_evaluation's result.txt) for `predictions` (list[BoxList] with "scores" / "labels",
+    boxes in the size each BoxList carries: what inference() returns or inference.load_predictions() reads, written by this
+    package or by the reference) against `groundtruth` (VIDGroundTruth, same frames, same order).
+    motion_iou: None (one range, "all") or load_motion_iou()'s per-frame lists (the 4 ranges all / fast / medium / slow).
+    -> {motion_index: {"ap": ndarray [n_fg_class] f64 (NaN: class not seen or without non-ignored GT), "map": nanmean}}."""
+    if box_only:
+        raise NotImplementedError("box_only proposal recall (eval_proposals_vid) is not provided")
+    if use_07_metric:
+        raise NotImplementedError("the VOC07 11-point metric is not provided (the reference hard-codes use_07_metric=False)")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    ap = match_and_ap(predictions, groundtruth, motion_iou, device, ap_only=True)["ap"]
+    motion_ranges = MOTION_RANGES if motion_iou is not None else MOTION_RANGES[:1]
+    result = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)     # nanmean of an all-NaN row is NaN, as in the reference
+        for ri in range(len(motion_ranges)):
+            result[ri] = {"ap": ap[ri].copy(), "map": np.nanmean(ap[ri])}
+    text = format_result(result)
+    (logger or logging.getLogger("mega.pytorch_amd.vid_eval")).info("\n" + text)
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+        with open(os.path.join(output_folder, "result.txt"), "w") as fid_:
+            fid_.write(text)
+    return result
