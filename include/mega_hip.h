@@ -4,9 +4,11 @@
  * Boundary rules
  *   - extern "C", plain device pointers + sizes, no torch / ATen types.
  *   - every entry point returns int: 0 = MEGA_OK, 1 = bad argument, 2 = launch failure,
- *     3 = workspace too small.  Nothing is allocated inside: the caller owns outputs and workspaces.
+ *     3 = workspace too small, 4 = a kernel's loop bound was exceeded (mega_seq_nms).  Nothing is allocated inside:
+ *     the caller owns outputs and workspaces.
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All work is
- *     enqueued on that stream; no call synchronises the device or copies to the host.
+ *     enqueued on that stream; no call synchronises the device or copies to the host, except mega_seq_nms, which
+ *     reads its status word back.
  *   - dtype codes: MEGA_F32 = 0 (exact-f32 MFMA path, parity mode), MEGA_BF16 = 1, MEGA_F16 = 2 (IEEE half: the same
  *     kernels instantiated for _Float16 operands -- the bf16 MFMA rate and bytes with 11 significant bits instead of 8,
  *     values bounded by 65 504; accumulation is f32 in every mode).  Wherever an entry point takes a dtype code, MEGA_F16
@@ -33,6 +35,7 @@ extern "C" {
 #define MEGA_ERR_ARG 1
 #define MEGA_ERR_LAUNCH 2
 #define MEGA_ERR_WS 3
+#define MEGA_ERR_LIMIT 4   /* a kernel's loop bound was exceeded (reported by mega_seq_nms) */
 
 /* Conv2d (+ FrozenBatchNorm2d scale/bias) (+ residual add) (+ ReLU), implicit GEMM on MFMA.
  * Replaces torch Conv2d->cuDNN + the unfused FrozenBatchNorm2d / relu_ / += of
@@ -479,6 +482,23 @@ int mega_vid_eval_match(const float* det_box, const int* det_label, const long l
 size_t mega_vid_eval_workspace_bytes(long long N, int C, int R);
 int mega_vid_eval_ap(const unsigned char* match, const double* pred_ignore, const int* gorder, const long long* seg_off,
                      const int* n_pos, int C, int R, long long N, double* ap, void* ws, size_t ws_bytes, void* stream);
+
+/* Seq-NMS video-level rescoring (mega/pytorch_amd/seq_nms.py defines it; the reference has no counterpart).  One
+ * workgroup per (video, class) task; per task, until no box is alive: forward DP in f64 over the frames (S = score + the
+ * best S of an alive box of the previous frame with IoU > link_iou, arg-max P: smallest position on equal S), the best
+ * end box (largest S, then earliest frame, then smallest position), backtrack, rescore the path (rescore_max = 0: f32(S /
+ * path length), 1: the largest score on the path), remove the path boxes and every alive box with IoU > nms_iou to them.
+ * IoU: the +1 convention in f32.  The DP is recomputed incrementally after each removal (bit-identical to a full pass).
+ * Inputs, sorted class-major then frame, positions kept within each (class, frame) run:
+ *   box [N][4] f32, score [N] f32 (>= 0), seg_off [C * F + 1] i64 (class c, frame f: seg_off[c F + f] .. seg_off[c F + f
+ *   + 1]), tasks [T][3] i32 = (class, first frame, frame count) of each task, longest first.
+ * Outputs (same order): keep [N] u8 (1: on a path), new_score [N] f32 (set where keep is 1), stats [T][2] i64 or NULL =
+ * (iterations, DP frame steps) per task.  Thresholds in [0, 1].  Workspace: mega_seq_nms_workspace_bytes(N, C * F).
+ * Synchronises the stream: returns MEGA_ERR_LIMIT if a task ran past its loop bound (its box count). */
+size_t mega_seq_nms_workspace_bytes(long long N, long long segs);
+int mega_seq_nms(const float* box, const float* score, const long long* seg_off, const int* tasks, int T, int F, int C,
+                 long long N, float link_iou, float nms_iou, int rescore_max, unsigned char* keep, float* new_score,
+                 long long* stats, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

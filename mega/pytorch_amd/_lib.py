@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(HERE, "libmega_hip.so")
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_longlong = ctypes.c_longlong
 
-_ERR = {1: "bad argument", 2: "kernel launch failure", 3: "workspace too small"}
+_ERR = {1: "bad argument", 2: "kernel launch failure", 3: "workspace too small", 4: "kernel loop bound exceeded"}
 
 # name -> (restype, argtypes).  Must list every symbol declared in include/mega_hip.h.
 SIGNATURES = {
@@ -98,6 +98,9 @@ SIGNATURES = {
     "mega_vid_eval_match": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_longlong, c_int] + [c_void_p] * 4),
     "mega_vid_eval_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
     "mega_vid_eval_ap": (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong] + [c_void_p] * 2 + [c_size_t, c_void_p]),
+    "mega_seq_nms_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
+    "mega_seq_nms": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int] + [c_void_p] * 4 +
+                     [c_size_t, c_void_p]),
     "mega_last_error_string": (ctypes.c_char_p, []),
 }
 

@@ -12,6 +12,7 @@
 #define MEGA_ERR_ARG 1
 #define MEGA_ERR_LAUNCH 2
 #define MEGA_ERR_WS 3
+#define MEGA_ERR_LIMIT 4
 
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;

@@ -267,11 +267,15 @@ def load_predictions(path):
 
 
 def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, anno_path=None,
-              motion_iou=None, **kw):
+              motion_iou=None, seq_nms=None, **kw):
     """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
     evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
     result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
-    vid_eval.load_motion_iou() lists (motion-specific AP).  The return value is the list[BoxList] either way."""
+    vid_eval.load_motion_iou() lists (motion-specific AP).  The return value is the list[BoxList] either way.
+    seq_nms: None (off), True or a dict of seq_nms.seq_nms's link_iou / nms_iou / rescore: Seq-NMS over all videos on
+    the main process after the gather.  predictions.pth stays the raw list; the rescored one goes to
+    predictions_seq_nms.pth and its evaluation to result_seq_nms.txt (result.txt stays the raw evaluation); the return
+    value is then the rescored list."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     device = torch.device(cfg.MODEL.DEVICE if device is None else device)
     dist = torch.distributed
@@ -294,10 +298,21 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
         save_predictions(predictions, os.path.join(output_folder, "predictions.pth"))
+    rescored = None
+    if seq_nms is not None and seq_nms is not False:
+        from . import seq_nms as sn
+        params = {} if seq_nms is True else dict(seq_nms)
+        rescored = sn.seq_nms(predictions, [(v["start"], v["seg_len"]) for v in index.videos], device=device, **params)
+        if output_folder:
+            save_predictions(rescored, os.path.join(output_folder, "predictions_seq_nms.pth"))
     if anno_path is not None:
         from . import vid_eval
         if isinstance(motion_iou, str):
             motion_iou = vid_eval.load_motion_iou(motion_iou)
-        vid_eval.evaluate_detections(predictions, vid_eval.VIDGroundTruth(img_index, anno_path), motion_iou=motion_iou,
-                                     output_folder=output_folder, device=device, logger=logger)
-    return predictions
+        gt = vid_eval.VIDGroundTruth(img_index, anno_path)
+        vid_eval.evaluate_detections(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
+                                     logger=logger)
+        if rescored is not None:
+            vid_eval.evaluate_detections(rescored, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
+                                         logger=logger, result_name="result_seq_nms.txt")
+    return predictions if rescored is None else rescored

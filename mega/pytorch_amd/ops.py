@@ -1308,3 +1308,30 @@ def vid_eval_ap(match, pred_ignore, gorder, seg_off, n_pos):
     _pe(_tok)
     _lib.check(rc, "mega_vid_eval_ap")
     return ap
+
+
+# ------------------------------------------------------------------------------------------------ Seq-NMS
+def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
+    """Seq-NMS over T (video, class) tasks (include/mega_hip.h mega_seq_nms).  box [N,4] f32, score [N] f32 sorted class-
+    major then frame, seg_off [C*F+1] i64, tasks [T,3] i32 (class, first frame, frame count), longest first.
+    -> keep [N] u8, new_score [N] f32 (valid where keep), stats [T,2] i64 (iterations, DP frame steps), on the device.
+    Synchronises the stream (the kernel's status word)."""
+    _gpu(box, score, seg_off, tasks)
+    lib = _lib.load()
+    N, T = box.shape[0], tasks.shape[0]
+    for t, dt in ((box, torch.float32), (score, torch.float32), (seg_off, torch.int64), (tasks, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert box.shape == (N, 4) and score.shape == (N,) and seg_off.shape == (C * F + 1,) and tasks.shape == (T, 3)
+    dev = box.device
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    new_score = torch.zeros(N, dtype=torch.float32, device=dev)
+    stats = torch.zeros((T, 2), dtype=torch.int64, device=dev)
+    nb = lib.mega_seq_nms_workspace_bytes(N, C * F)
+    ws = _ws(nb, dev)
+    _tok = _pb("seq_nms")
+    rc = lib.mega_seq_nms(_ptr(box), _ptr(score), _ptr(seg_off), _ptr(tasks), T, int(F), int(C), N, float(link_iou),
+                          float(nms_iou), int(bool(rescore_max)), _ptr(keep), _ptr(new_score), _ptr(stats), _ptr(ws), nb,
+                          _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_seq_nms")
+    return keep, new_score, stats

@@ -186,6 +186,44 @@ def format_result(result, classes=CLASSES, motion_names=None):
     return s
 
 
+def concat_predictions(predictions):
+    """A list[BoxList] as flat host arrays: counts [F] i64, off [F+1] i64 (frame f's boxes are off[f] .. off[f+1]),
+    boxes [N,4] f32, scores [N] f32, labels [N] i64 (the fields "scores" / "labels")."""
+    F = len(predictions)
+    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
+    off = np.zeros(F + 1, np.int64)
+    off[1:] = np.cumsum(counts)
+    if off[-1]:
+        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
+        scores = torch.cat([p.get_field("scores").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
+        labels = torch.cat([p.get_field("labels").reshape(-1).to("cpu", torch.int64) for p in predictions]).numpy()
+    else:
+        boxes, scores, labels = np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64)
+    return counts, off, boxes, scores, labels
+
+
+def one_buffer(parts):
+    """[(name, ndarray)] -> (one u8 host buffer, 16-byte aligned, [(name, dtype, shape, byte offset)]) for a single
+    host-to-device copy; device_views() cuts the copied buffer back into tensors."""
+    layout, off = [], 0
+    for name, a in parts:
+        a = np.ascontiguousarray(a)
+        layout.append((name, a, off))
+        off += (a.nbytes + 15) // 16 * 16
+    buf = np.empty(max(off, 16), np.uint8)
+    for name, a, o in layout:
+        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    return buf, [(name, a.dtype, a.shape, o) for name, a, o in layout]
+
+
+def device_views(dbuf, layout):
+    t = {}
+    for name, dt, shape, o in layout:
+        n = int(np.prod(shape))
+        t[name] = dbuf[o:o + n * np.dtype(dt).itemsize].view(_torch_dtype(dt)).reshape(shape)
+    return t
+
+
 def _pack(predictions, groundtruth, motion_iou, motion_ranges):
     """Flat host arrays of the whole evaluation, in one byte buffer (one host-to-device copy)."""
     F = len(predictions)
@@ -193,16 +231,8 @@ def _pack(predictions, groundtruth, motion_iou, motion_ranges):
         raise ValueError("evaluate_detections: no predictions")
     if len(groundtruth) != F:
         raise ValueError("Length of gt and pred lists need to be same (%d predictions, %d GT frames)" % (F, len(groundtruth)))
-    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
-    det_off = np.zeros(F + 1, np.int64)
-    det_off[1:] = np.cumsum(counts)
+    counts, det_off, boxes, scores, labels = concat_predictions(predictions)
     N = int(det_off[-1])
-    if N:
-        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
-        scores = torch.cat([p.get_field("scores").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
-        labels = torch.cat([p.get_field("labels").reshape(-1).to("cpu", torch.int64) for p in predictions]).numpy()
-    else:
-        boxes, scores, labels = np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64)
     if not np.isfinite(boxes).all():
         raise ValueError("evaluate_detections: a prediction box is not finite")
     if np.isnan(scores).any():
@@ -244,21 +274,14 @@ def _pack(predictions, groundtruth, motion_iou, motion_ranges):
              ("ranges", ranges)]
     if motion is not None:
         parts.append(("gt_motion", motion))
-    layout, off = [], 0
-    for name, a in parts:
-        a = np.ascontiguousarray(a)
-        layout.append((name, a, off))
-        off += (a.nbytes + 15) // 16 * 16
-    buf = np.empty(max(off, 16), np.uint8)
-    for name, a, o in layout:
-        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    buf, layout = one_buffer(parts)
     meta = {"F": F, "N": N, "C": C, "max_gt": max_gt, "counts": counts}
-    return buf, [(name, a.dtype, a.shape, o) for name, a, o in layout], meta
+    return buf, layout, meta
 
 
 def _torch_dtype(dt):
     return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
-            np.dtype(np.int64): torch.int64}[np.dtype(dt)]
+            np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8}[np.dtype(dt)]
 
 
 def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_only=False):
@@ -272,11 +295,7 @@ def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_on
     motion_ranges = MOTION_RANGES if motion_iou is not None else MOTION_RANGES[:1]
     buf, layout, meta = _pack(predictions, groundtruth, motion_iou, motion_ranges)
     F, N, C = meta["F"], meta["N"], meta["C"]
-    dbuf = torch.from_numpy(buf).to(dev)
-    t = {}
-    for name, dt, shape, o in layout:
-        n = int(np.prod(shape))
-        t[name] = dbuf[o:o + n * np.dtype(dt).itemsize].view(_torch_dtype(dt)).reshape(shape)
+    t = device_views(torch.from_numpy(buf).to(dev), layout)
     labels = t["det_label"]
     scores = t["score"]
     if N:
@@ -309,11 +328,12 @@ def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_on
 
 
 def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder=None, device="cuda", box_only=False,
-                        use_07_metric=False, logger=None):
+                        use_07_metric=False, logger=None, result_name="result.txt"):
     """eval_detection_vid (+ do_vid_evaluation's result.txt) for `predictions` (list[BoxList] with "scores" / "labels",
     boxes in the size each BoxList carries: what inference() returns or inference.load_predictions() reads, written by this
     package or by the reference) against `groundtruth` (VIDGroundTruth, same frames, same order).
     motion_iou: None (one range, "all") or load_motion_iou()'s per-frame lists (the 4 ranges all / fast / medium / slow).
+    result_name: the file the text goes to in output_folder (result_seq_nms.txt for Seq-NMS-rescored predictions).
     -> {motion_index: {"ap": ndarray [n_fg_class] f64 (NaN: class not seen or without non-ignored GT), "map": nanmean}}."""
     if box_only:
         raise NotImplementedError("box_only proposal recall (eval_proposals_vid) is not provided")
@@ -332,6 +352,6 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
     (logger or logging.getLogger("mega.pytorch_amd.vid_eval")).info("\n" + text)
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "result.txt"), "w") as fid_:
+        with open(os.path.join(output_folder, result_name), "w") as fid_:
             fid_.write(text)
     return result

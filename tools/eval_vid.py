@@ -6,6 +6,10 @@ the reference's inference_no_model (mega_core/engine/inference.py:135-160), matc
 
 predictions.pth may be written by this package or by the reference.  result.txt goes to --output-folder (default: the
 folder of predictions.pth); the text is also printed.
+
+--seq-nms (with --seq-nms-link-iou / --seq-nms-iou / --seq-nms-rescore) also applies Seq-NMS (mega.pytorch_amd.seq_nms)
+over the videos of --img-index, writes predictions_seq_nms.pth and result_seq_nms.txt to the output folder and prints
+that evaluation too.
 """
 import argparse
 import os
@@ -23,6 +27,11 @@ def main(argv=None):
     ap.add_argument("--output-folder", default=None, help="where result.txt goes (default: next to predictions.pth)")
     ap.add_argument("--cache", default=None, help="optional .npz cache of the parsed annotations")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--seq-nms", action="store_true", help="also evaluate the Seq-NMS-rescored predictions")
+    ap.add_argument("--seq-nms-link-iou", type=float, default=0.5, help="Seq-NMS: IoU above which boxes of adjacent "
+                    "frames link")
+    ap.add_argument("--seq-nms-iou", type=float, default=0.3, help="Seq-NMS: IoU above which a path box suppresses")
+    ap.add_argument("--seq-nms-rescore", choices=("avg", "max"), default="avg")
     a = ap.parse_args(argv)
     from mega.pytorch_amd import inference, vid_eval
     preds = inference.load_predictions(a.predictions)
@@ -31,6 +40,16 @@ def main(argv=None):
     out = a.output_folder or os.path.dirname(os.path.abspath(a.predictions))
     res = vid_eval.evaluate_detections(preds, gt, motion_iou=motion, output_folder=out, device=a.device)
     sys.stdout.write(vid_eval.format_result(res))
+    if a.seq_nms:
+        from mega.pytorch_amd import seq_nms
+        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
+        rescored = seq_nms.seq_nms(preds, videos, link_iou=a.seq_nms_link_iou, nms_iou=a.seq_nms_iou,
+                                   rescore=a.seq_nms_rescore, device=a.device)
+        os.makedirs(out, exist_ok=True)
+        inference.save_predictions(rescored, os.path.join(out, "predictions_seq_nms.pth"))
+        res = vid_eval.evaluate_detections(rescored, gt, motion_iou=motion, output_folder=out, device=a.device,
+                                           result_name="result_seq_nms.txt")
+        sys.stdout.write("Seq-NMS:\n" + vid_eval.format_result(res))
     return 0
 
 
