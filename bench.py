@@ -2,7 +2,7 @@
 """MEGA R-101 per-key-frame inference benchmark on MI355X (BASELINE.json metric: frames/sec, synthetic
 1000x600 VID clip, MEGA R-101 25 local / 10 global / 25-frame memory, bf16).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: one rank per GPU.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N`: WORLD_SIZE is set and must equal --gpus) or, when WORLD_SIZE is not set, bench.py launches them
@@ -32,11 +32,20 @@ step-batch (20 N key frames = 40 N frames, 40 per rank) is sharded over the rank
 exchanged with one RCCL all-gather per row-count group; the key frames' aggregation is dealt to the ranks, the memory
 entries all-gathered once per stage (engine.KeyFrameShard).  `value` = all key frames of a block / its time.
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract fields it carries
-  roofline     -- the dominant kernel family (implicit-GEMM conv/linear on MFMA): algorithmic FLOPs of its launches
-                  / their HIP-event durations measured in a separate, untimed, instrumented pass
-  cpu_baseline -- oracle/ (a CPU restatement of the reference path, kind "port") timed on the host cores over a
-                  bounded sample of the SAME workload (N=1, rank 0 only).
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set up, pre-roll, the timed
+block(s), --dump-outputs, the line.  --full adds the extra measurements, each after the timed region and each dropped
+from a --full run by its own --no-* switch:
+  config.with_h2d         -- the timed blocks again with the frames fed from host memory (--no-h2d-leg)
+  roofline, roofline_mfma, roofline_hbm, kernel_families
+                          -- the dominant kernel family (implicit-GEMM conv/linear on MFMA): algorithmic FLOPs of its
+                             launches / their HIP-event durations measured in a separate, untimed, instrumented pass,
+                             and the per-family / HBM-bound rows of that pass (--no-roofline)
+  config.whole_clip_incl_cold_start -- a fresh video: cold start + --steps key frames (--no-whole-clip)
+  config.fp16_mode, f32_parity_mode, bf16x3_parity_mode -- the same workload in the other precisions (--no-f32-leg)
+  cpu_baseline            -- oracle/ (a CPU restatement of the reference path, kind "port") timed on the host cores
+                             over a bounded sample of the SAME workload (N=1, rank 0 only; --no-cpu-baseline).
+Without --full these fields are null / empty.  The clip and the global-frame schedule are sized for the --full legs in
+either case, so the timed steps see the same inputs with and without --full.
 """
 import argparse
 import json
@@ -68,7 +77,7 @@ HALF_MODES = ("bfloat16", "wide", "float16", "f16x2")      # --dtype values whos
 ALGO_GFLOP_PER_FRAME = 729.0   # minimal algorithmic work per steady-state key frame, R-101 MEGA
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)     # three step-batches of 20 key frames
@@ -88,14 +97,17 @@ def parse():
     ap.add_argument("--head-stream", default=None, choices=["float32", "bfloat16"],
                     help="cfg.HEAD_STREAM of the bf16 mode (default: the product's default, float32 = the parity-preserving head; "
                          "bfloat16 = the round-3 head with 8 bf16 hand-offs, ~2 %% faster)")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the parity-mode legs (config.f32_parity_mode, "
-                    "config.bf16x3_parity_mode)")
-    ap.add_argument("--no-h2d-leg", action="store_true", help="skip the leg that feeds the frames from pinned host memory "
-                    "(config.with_h2d)")
-    ap.add_argument("--no-whole-clip", action="store_true", help="skip the whole-clip (cold start + K key frames) measurement "
-                    "after the timed region (kernel traces: the tail of the stream is then a steady timed block)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements after the timed region (the legs below, the roofline pass, the "
+                         "CPU baseline); a plain run only times the headline")
+    ap.add_argument("--no-f32-leg", action="store_true", help="--full: skip the other-precision legs (config.fp16_mode, "
+                    "config.f32_parity_mode, config.bf16x3_parity_mode)")
+    ap.add_argument("--no-h2d-leg", action="store_true", help="--full: skip the leg that feeds the frames from pinned host "
+                    "memory (config.with_h2d)")
+    ap.add_argument("--no-whole-clip", action="store_true", help="--full: skip the whole-clip (cold start + K key frames) "
+                    "measurement after the timed region (kernel traces: the tail of the stream is then a steady timed block)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the instrumented roofline pass")
     ap.add_argument("--no-overlap", action="store_true", help="run frame stage and aggregation on one stream")
     ap.add_argument("--no-graphs", action="store_true", help="launch the frame stage kernel by kernel (no hipGraph)")
     ap.add_argument("--reuse-records", action="store_true",
@@ -117,7 +129,12 @@ def parse():
                     help="launch / rendezvous / reporting only (no model, no kernels; gloo when there is no HIP device): "
                          "proves the --gpus N self-launch and the n_gpus bookkeeping on a CPU box (tests/test_bench_cli.py)")
     ap.add_argument("--max-blocks", type=int, default=300)
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def extra(args, name):
+    """Whether the extra measurement `name` (that of --no-<name>) runs: only under --full, and there unless switched off."""
+    return args.full and not getattr(args, "no_" + name.replace("-", "_"))
 
 
 def key_frames_per_block(steps, world):
@@ -611,6 +628,8 @@ def main():
     prof_steps = 0 if args.no_roofline else spb       # the instrumented pass runs the steady batch shape
     # (+ the with-H2D leg's blocks: one GPU only -- the clip is resident on every rank, 1.8 MB per frame)
     h2d_T = (62 * KF + 40 * max(spb, 1) + 8) if (world == 1 and not args.no_h2d_leg and args.dtype in HALF_MODES) else 0
+    # T (and with it the global-frame schedule) leaves room for the --full legs whether or not they run: the timed steps
+    # get the same inputs with and without --full
     T = pre + KF + extra_cap + KF * max_blocks + 2 * prof_steps + 1 + KF + 13 + h2d_T
     clip = make_clip(T, args.height, args.width, device)
     gfor = eng.global_schedule(T, cfg.MODEL.VID.MEGA.GLOBAL.SIZE, seed=0)
@@ -725,7 +744,7 @@ def main():
     #      test-time feed) copies each step-batch's frames into pinned staging buffers and issues ONE async H2D copy per
     #      batch; the engine, its graphs and the video state are the ones of the timed region.
     h2d_leg = None
-    if world == 1 and not args.no_h2d_leg and args.dtype in HALF_MODES:
+    if world == 1 and extra(args, "h2d-leg") and args.dtype in HALF_MODES:
         try:
             from mega.pytorch_amd import feed
             host = clip[:16].cpu().numpy()
@@ -777,7 +796,7 @@ def main():
     roofline_hbm = []
     roofline_mfma = []
     fam = {}
-    if prof_steps:
+    if extra(args, "roofline"):
         # Instrumented pass: kernel by kernel (no hipGraph replays, one stream), every launch between a HIP event pair on
         # the launch stream.  One UNTIMED eager batch of the same shape goes first: the first eager launches after the
         # graphs are switched off pay one-time costs (allocator growth, kernel attribute calls) that belong to no kernel.
@@ -902,27 +921,26 @@ def main():
     # whole-clip rate (SURVEY 8d ii): a fresh video -- cold start (13 local + 10 global frames, eager aggregation
     # while the pools fill) plus the same K steady key frames -- on the warmed-up engine.  Reported beside `value`.
     whole_clip = None
-    try:
-        if args.no_whole_clip:
-            raise RuntimeError("--no-whole-clip")
-        runner.use_graphs, runner.overlap = not args.no_graphs, not args.no_overlap   # (the instrumented pass turned them off)
-        runner.use_static = True
-        barrier()
-        t0 = time.perf_counter()
-        runner.run(clip, T, gfor, first=0, last=1 + KF)
-        barrier()
-        wc = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([wc], dtype=torch.float64, device=device)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            wc = float(t.item())
-        whole_clip = {"key_frames": 1 + KF, "seconds": round(wc, 4), "frames_per_s": round((1 + KF) / wc, 2)}
-        log("whole clip incl. cold start: %d key frames in %.3fs (%.1f frames/s)" % (1 + KF, wc, (1 + KF) / wc))
-    except Exception as e:  # noqa: BLE001  (an optional extra must never cost the headline line)
-        log("whole-clip measurement skipped: %r" % (e,))
+    if extra(args, "whole-clip"):
+        try:
+            runner.use_graphs, runner.overlap = not args.no_graphs, not args.no_overlap   # (the instrumented pass turned them off)
+            runner.use_static = True
+            barrier()
+            t0 = time.perf_counter()
+            runner.run(clip, T, gfor, first=0, last=1 + KF)
+            barrier()
+            wc = time.perf_counter() - t0
+            if world > 1:
+                t = torch.tensor([wc], dtype=torch.float64, device=device)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                wc = float(t.item())
+            whole_clip = {"key_frames": 1 + KF, "seconds": round(wc, 4), "frames_per_s": round((1 + KF) / wc, 2)}
+            log("whole clip incl. cold start: %d key frames in %.3fs (%.1f frames/s)" % (1 + KF, wc, (1 + KF) / wc))
+        except Exception as e:  # noqa: BLE001  (an optional extra must never cost the headline line)
+            log("whole-clip measurement skipped: %r" % (e,))
 
     f32_leg = x3_leg = f16_leg = None
-    if world == 1 and args.dtype == "bfloat16" and not args.no_f32_leg:
+    if world == 1 and args.dtype == "bfloat16" and extra(args, "f32-leg"):
         try:
             f16_leg = f32_parity_leg(args, device, clip, gfor, T, spb, mode="float16")
             log("fp16-mode leg: %.1f frames/s (%.3f ms per key frame)" % (f16_leg["fps"], f16_leg["ms_per_key_frame"]))
@@ -947,7 +965,7 @@ def main():
             log("bf16x3 parity-mode leg skipped: %r" % (e,))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and extra(args, "cpu-baseline"):
         cpu = cpu_baseline(args.arch, sd, args.height, args.width, args.cpu_frames)
 
     live_world = dist.get_world_size() if group is not None else 1

@@ -6,7 +6,8 @@
   * `--gpus 2` on a box with fewer than 2 devices is refused (exit code 2) instead of silently reporting N = 1;
   * the host-side prefetch of a sharded run asks for exactly the frames records_async computes on that rank;
   * on the GPU: `--steps K` times exactly K steps, and `--dump-outputs DIR` writes the last one's detections, the same
-    arrays on every run with the same arguments.
+    arrays on every run with the same arguments;
+  * the extra measurements run only under `--full`, and the timed steps get the same inputs with or without it.
 Reference: one process per GPU, tools/test_net.py:41,:69-75.
 """
 import json
@@ -86,6 +87,65 @@ def test_steps_and_dump_outputs(tmp_path):
         assert c["dumped_outputs"] == {k: list(v.shape) for k, v in a.items()}
         assert set(a["key_frame"].tolist()) == {c["pre_roll_key_frames"] + 2}     # the last of the 3 timed key frames
         got.append(a)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+EXTRAS = ("h2d-leg", "roofline", "whole-clip", "f32-leg", "cpu-baseline")
+
+
+def test_extras_run_only_under_full():
+    """A plain run measures the headline only; --full turns every extra on, and each --no-* switch still drops its own."""
+    bench = _bench_module()
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and not any(bench.extra(plain, x) for x in EXTRAS)
+    full = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert all(bench.extra(full, x) for x in EXTRAS)
+    for x in EXTRAS:
+        a = bench.parse(["--full", "--no-" + x])
+        assert [bench.extra(a, y) for y in EXTRAS] == [y != x for y in EXTRAS], x
+        assert not bench.extra(bench.parse(["--no-" + x]), x)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_and_full_runs(tmp_path):
+    """A plain run leaves every extra of the line empty; --full fills them (the CPU baseline, a minute of host time with
+    the GPU idle, switched off by its --no-* switch), and the timed steps of both runs see the same inputs: the last
+    timed step's detections are the same arrays."""
+    import numpy as np
+    args = [sys.executable, BENCH, "--gpus", "1", "--arch", "R-50", "--height", "160", "--width", "256", "--steps", "3",
+            "--warmup", "0"]
+    got, lines = [], []
+    for name, more in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        d = str(tmp_path / name)
+        rc, out, err = _run(args + more + ["--dump-outputs", d])
+        assert rc == 0, err[-3000:]
+        assert "skipped" not in err, err[-3000:]
+        ls = [l for l in out.splitlines() if l.strip()]
+        assert len(ls) == 1, out
+        lines.append(json.loads(ls[0]))
+        got.append({f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    plain, full = lines
+
+    def extras(l):
+        c = l["config"]
+        return [c["with_h2d"], c["whole_clip_incl_cold_start"], c["fp16_mode"], c["f32_parity_mode"], c["bf16x3_parity_mode"],
+                l["roofline"], l["roofline_mfma"], l["roofline_hbm"], l["kernel_families"]]
+    assert not any(extras(plain)) and plain["cpu_baseline"] is None, plain
+    assert all(extras(full)) and full["cpu_baseline"] is None, full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["config"]["pre_roll_key_frames"] == full["config"]["pre_roll_key_frames"]
+    assert sorted(got[0]) == sorted(got[1])
     for k in got[0]:
         assert np.array_equal(got[0][k], got[1][k]), k
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One pass of everything profiles/ needs, on the GPU box (run through gpurun; every step under its own timeout):
 #   tools/profile_round.sh <tag> [quick]      e.g. r02  ->  gpurun_out/<tag>/...
-# 1. pytest -m gpu   2. __graft_entry__.smoke()   3. bench.py (defaults, incl. CPU baseline unless "quick")
+# 1. pytest -m gpu   2. __graft_entry__.smoke()   3. bench.py --full (incl. CPU baseline unless "quick")
 # 4. rocprofv3 kernel stats of the bench   5. rocprofv3 PMC passes, ONE counter per pass, kernel trace only
 #    (MI355X_MICROARCH.md HBM section): FETCH_SIZE, WRITE_SIZE, SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE
 #    -> reduce with tools/pmc_summary.py (per kernel family: HBM bytes per launch, MFMA-busy fraction)
@@ -14,12 +14,12 @@ root=$(pwd)
 if [ -z "$quick" ]; then
   timeout 1500 python -m pytest tests -m gpu -q -s > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest_gpu.log; tail -2 $out/pytest_gpu.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-  timeout 900 python bench.py > $out/bench_n1.json 2> $out/bench_n1.err; tail -3 $out/bench_n1.err; cut -c1-260 $out/bench_n1.json
+  timeout 900 python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err; tail -3 $out/bench_n1.err; cut -c1-260 $out/bench_n1.json
 else
-  timeout 300 python bench.py --no-cpu-baseline > $out/bench_n1.json 2> $out/bench_n1.err; tail -3 $out/bench_n1.err; cut -c1-260 $out/bench_n1.json
+  timeout 300 python bench.py --full --no-cpu-baseline > $out/bench_n1.json 2> $out/bench_n1.err; tail -3 $out/bench_n1.err; cut -c1-260 $out/bench_n1.json
 fi
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_n1_driver_cli.json 2> $out/bench_n1_driver_cli.err
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -o bench -- python $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg --min-seconds 1 > $root/$out/bench_under_rocprof.json 2> $root/$out/prof.err); ls $out/prof | head -3
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_n1_driver_cli.json 2> $out/bench_n1_driver_cli.err
+(cd "$TMPDIR" && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -o bench -- python $root/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg --min-seconds 1 > $root/$out/bench_under_rocprof.json 2> $root/$out/prof.err); ls $out/prof | head -3
 pmcargs="--steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg --no-whole-clip --no-graphs --no-overlap --min-seconds 0.01 --max-blocks 1"
 for c in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE ${EXTRA_PMC:-}; do
   (cd /tmp && timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $root/$out/pmc_$c -o pmc -- python $root/bench.py $pmcargs > $root/$out/pmc_$c.json 2> $root/$out/pmc_$c.err); ls -la $out/pmc_$c | tail -1
@@ -27,7 +27,7 @@ done
 # round 6: the other modes as the PROFILED configuration (kernel stats + the same four PMC passes): the split-precision parity
 # mode, the fp16 mode, the fp16 two-pass mode  ->  <mode>_prof/, <mode>_pmc_<counter>/ (reduced with tools/pmc_summary.py)
 for mode in bf16x3 float16 f16x2; do
-  (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/${mode}_prof -o bench -- python $root/bench.py --dtype $mode --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg --min-seconds 1 > $root/$out/${mode}_bench_under_rocprof.json 2> $root/$out/${mode}_prof.err); ls $out/${mode}_prof | head -2
+  (cd "$TMPDIR" && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/${mode}_prof -o bench -- python $root/bench.py --full --dtype $mode --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg --min-seconds 1 > $root/$out/${mode}_bench_under_rocprof.json 2> $root/$out/${mode}_prof.err); ls $out/${mode}_prof | head -2
   for c in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE; do
     (cd /tmp && timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $root/$out/${mode}_pmc_$c -o pmc -- python $root/bench.py --dtype $mode $pmcargs > $root/$out/${mode}_pmc_$c.json 2> $root/$out/${mode}_pmc_$c.err); ls -la $out/${mode}_pmc_$c | tail -1
   done
@@ -35,15 +35,15 @@ done
 # keep only what the reducers need (the kernel-trace CSVs are large)
 rm -f $out/pmc_*/pmc_kernel_trace.csv $out/prof/bench_kernel_trace.csv $out/*_pmc_*/pmc_kernel_trace.csv $out/*_prof/bench_kernel_trace.csv
 # the RCCL collectives of the sharded aggregation on ONE GPU (world 1, every key frame owned by rank 0)
-leg="--steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg"
+leg="--full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg"
 MEGA_FORCE_SHARDED=1 timeout 300 python bench.py $leg > $out/bench_n1_forced_sharded.json 2> $out/bench_n1_forced_sharded.err
-timeout 300 python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg > $out/bench_n1_100step_blocks.json 2> $out/bench_n1_100step_blocks.err
+timeout 300 python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --no-f32-leg --no-h2d-leg > $out/bench_n1_100step_blocks.json 2> $out/bench_n1_100step_blocks.err
 # round 5's modes as the main configuration (kernel families of each in the line)
-timeout 300 python bench.py --steps 20 --warmup 5 --dtype bf16x3 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_bf16x3.json 2> $out/bench_n1_bf16x3.err
-timeout 300 python bench.py --steps 20 --warmup 5 --dtype wide --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_wide_trunk.json 2> $out/bench_n1_wide_trunk.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype bf16x3 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_bf16x3.json 2> $out/bench_n1_bf16x3.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype wide --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_wide_trunk.json 2> $out/bench_n1_wide_trunk.err
 # round 6's modes as the main configuration
-timeout 300 python bench.py --steps 20 --warmup 5 --dtype float16 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_float16.json 2> $out/bench_n1_float16.err
-timeout 300 python bench.py --steps 20 --warmup 5 --dtype f16x2 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_f16x2.json 2> $out/bench_n1_f16x2.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype float16 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_float16.json 2> $out/bench_n1_float16.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype f16x2 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_f16x2.json 2> $out/bench_n1_f16x2.err
 # round 6's opt-in GEMM kernels end to end (same box): igemm2 on the K <= 128 streaming layers, on the whole streaming class
 MEGA_IGEMM2=1 timeout 300 python bench.py $leg > $out/bench_n1_igemm2_k128.json 2> $out/bench_n1_igemm2_k128.err
 MEGA_IGEMM2=2 timeout 300 python bench.py $leg > $out/bench_n1_igemm2_streaming.json 2> $out/bench_n1_igemm2_streaming.err
