@@ -180,6 +180,31 @@ int mega_postprocess_batched(const float* logits, const float* deltas, const flo
                              float* out_scores, long long* out_labels, int* out_cnt, float* probs_out, void* ws,
                              size_t ws_bytes, void* stream);
 
+/* The first phase of the post-processor alone: the candidates that the reference's PostProcessor returns when
+ * TEST.BBOX_AUG is enabled (box_head/inference.py:79-86: prepare_boxlist + clip_to_image(remove_empty=False)),
+ * without the background class and with the score threshold applied.  No workspace.
+ *   cboxes [B][NC-1][R][4] (class j + 1, proposal row r), cscores [B][NC-1][R]: the softmax score, -1 when it is not
+ *   > score_thresh or r >= nprop[b]. */
+int mega_postprocess_candidates(const float* logits, const float* deltas, const float* props, const int* nprop, int R,
+                                int NC, float wx, float wy, float ww, float wh, float im_w, float im_h,
+                                float score_thresh, float* cboxes, float* cscores, void* stream);
+int mega_postprocess_candidates_batched(const float* logits, const float* deltas, const float* props, const int* nprop,
+                                        int B, int R, int NC, float wx, float wy, float ww, float wh, float im_w,
+                                        float im_h, float score_thresh, float* cboxes, float* cscores, void* stream);
+
+/* Test-time box augmentation merge (engine/bbox_aug.py:53-66) for F frames x K views (K <= 16, K * R <= 8192, else
+ * MEGA_ERR_LIMIT before any launch).  cboxes [K][F][NC-1][R][4] / cscores [K][F][NC-1][R] as the candidate entries
+ * write them, view k's boxes in its own image of view_w[k] x view_h[k] (host int arrays [K]), view_flip[k] (host) = 1
+ * if the view's frames were mirrored.  Each box is un-flipped (BoxList.transpose), scaled into view 0's image
+ * (BoxList.resize), then filter_results runs on the (view, row)-ordered concatenation: the outputs are those of
+ * mega_postprocess, per frame, with capacity (NC-1)*K*R rows: out_boxes [F][cap][4], out_scores [F][cap],
+ * out_labels [F][cap] i64, out_cnt device int[F]. */
+size_t mega_bbox_aug_merge_workspace_bytes(int F, int K, int R, int NC);
+int mega_bbox_aug_merge(const float* cboxes, const float* cscores, int F, int K, int R, int NC, const int* view_w,
+                        const int* view_h, const int* view_flip, float score_thresh, float nms_thresh, int strict_gt,
+                        int max_det, float* out_boxes, float* out_scores, long long* out_labels, int* out_cnt, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* Position-embedding logits of the relation module: log(relu(Wg . pe(q,k) + bg) + 1e-6).
  * Replaces extract_position_matrix + extract_position_embedding + the Wgs 1x1 conv + relu + log
  * (roi_box_feature_extractors.py:147-176,:126-144,:593-597,:630) without materialising the
@@ -229,6 +254,12 @@ int mega_preprocess_frames(const unsigned char* in, float* out, int N, int H, in
 int mega_resize_bilinear_u8(const unsigned char* in, unsigned char* out, unsigned char* tmp, int N, int Hi, int Wi,
                             int Ho, int Wo, const int* bounds_h, const int* coef_h, int ksize_h, const int* bounds_v,
                             const int* coef_v, int ksize_v, void* stream);
+/* The same resize followed by Image.transpose(FLIP_LEFT_RIGHT) (TT.RandomHorizontalFlip(1.0) after T.Resize,
+ * engine/bbox_aug.py:92-96), the mirror written by the last pass; hflip = 0 is mega_resize_bilinear_u8.  With no
+ * resize at all and hflip = 1 the frames are mirrored.  out must not alias in. */
+int mega_resize_bilinear_u8_flip(const unsigned char* in, unsigned char* out, unsigned char* tmp, int N, int Hi, int Wi,
+                                 int Ho, int Wo, const int* bounds_h, const int* coef_h, int ksize_h,
+                                 const int* bounds_v, const int* coef_v, int ksize_v, int hflip, void* stream);
 
 /* FGFA flow-guided aggregation (BASELINE configs[4]): bilinear warp of T frames' [features | embeddings] by their
  * flow fields (F.grid_sample bilinear / border / align_corners=False), cosine-similarity weights of the embeddings

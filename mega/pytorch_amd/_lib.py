@@ -42,6 +42,11 @@ SIGNATURES = {
     "mega_postprocess_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mega_postprocess_batched": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int] + [c_float] * 8 + [c_int, c_int] +
                                  [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "mega_postprocess_candidates": (c_int, [c_void_p] * 4 + [c_int, c_int] + [c_float] * 7 + [c_void_p] * 3),
+    "mega_postprocess_candidates_batched": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float] * 7 + [c_void_p] * 3),
+    "mega_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 4),
+    "mega_bbox_aug_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_float, c_float, c_int, c_int] +
+                            [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mega_position_logits": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "mega_position_logits_tiled": (c_int, [c_void_p] * 6 + [c_int] * 2 + [c_void_p]),
     "mega_relation_attention_tiled_pos": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
@@ -67,6 +72,8 @@ SIGNATURES = {
     "mega_fgfa_pair_taps": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "mega_resize_bilinear_u8": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                                                       c_int, c_void_p]),
+    "mega_resize_bilinear_u8_flip": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p,
+                                                                           c_void_p, c_int, c_int, c_void_p]),
     "mega_fgfa_warp_aggregate": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "mega_fgfa_warp_aggregate_ring": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "mega_copy_segments": (c_int, [c_void_p, c_int, c_void_p]),

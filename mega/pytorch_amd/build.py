@@ -31,6 +31,7 @@ SOURCES = {
     "bneck64.hip": [],
     "vid_eval.hip": ["-ffp-contract=off"],    # rescale + IoU must round like the reference's separate f32 torch ops
     "seq_nms.hip": ["-ffp-contract=off"],     # the f32 IoU in the order seq_nms.py defines
+    "bbox_aug.hip": ["-ffp-contract=off"],    # flip / resize of the merged boxes round like BoxList's separate f32 ops
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -97,6 +97,9 @@ def _mega_cfg(r50):
         # bfloat16 mode only: "bfloat16" = the residual trunk is a bf16 tensor (rounded at each of the 36 `out += identity`,
         # resnet.py:324-344); "planes" = the trunk is carried as [hi | lo] planes and added in f32 (modeling.conv_mode "wide")
         "RESIDUAL_STREAM": "bfloat16",
+        # test-time box augmentation (defaults.py:511-526; bbox_aug.py): views = identity, its flip if H_FLIP, then every
+        # SCALES entry at MAX_SIZE and its flip if SCALE_H_FLIP
+        "TEST": {"BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False}},
         "INPUT": {"MIN_SIZE_TEST": 600, "MAX_SIZE_TEST": 1000,
                   "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True},
         "MODEL": {

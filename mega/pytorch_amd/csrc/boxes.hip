@@ -565,7 +565,8 @@ __global__ void post_prepare_kernel(const float* __restrict__ logits, const floa
   props += (size_t)b * R;
   cboxes += (size_t)b * (NC - 1) * R;
   cscores += (size_t)b * (NC - 1) * R;
-  flags += (size_t)b * (NC - 1) * R;     // the kept flags of this call start from zero (written here, not by a memset node)
+  if (flags) flags += (size_t)b * (NC - 1) * R;     // the kept flags of this call start from zero (written here, not by a
+                                                    // memset node); null: candidates only (mega_postprocess_candidates)
   if (probs_out) probs_out += (size_t)b * R * NC;
   const int nprop = nprop_ptr ? min(nprop_ptr[b], R) : R;
   const bool live = r < nprop;
@@ -595,7 +596,7 @@ __global__ void post_prepare_kernel(const float* __restrict__ logits, const floa
     const size_t o = (size_t)(j - 1) * R + r;
     cboxes[o] = make_float4(x1, y1, x2, y2);
     cscores[o] = (live && pr > score_thresh) ? pr : -1.f;
-    flags[o] = 0;
+    if (flags) flags[o] = 0;
   }
 }
 
@@ -950,6 +951,48 @@ extern "C" int mega_postprocess_batched(const float* logits, const float* deltas
   if (rc != MEGA_OK) return rc;
   hipLaunchKernelGGL(post_finalize_kernel, dim3(B), dim3(1024), 0, st, flags, cboxes, cscores, C1, R, max_det,
                      (float4*)out_boxes, out_scores, out_labels, out_cnt, tmp_idx);
+  return mega_check_launch();
+}
+
+// P1 alone: the candidates of B images, what the reference's PostProcessor returns with bbox_aug_enabled
+// (box_head/inference.py:79-86) minus the background class, thresholded: cboxes [B][NC-1][R][4], cscores [B][NC-1][R].
+extern "C" int mega_postprocess_candidates_batched(const float* logits, const float* deltas, const float* props,
+                                                   const int* nprop, int B, int R, int NC, float wx, float wy, float ww,
+                                                   float wh, float im_w, float im_h, float score_thresh, float* cboxes,
+                                                   float* cscores, void* stream) {
+  mega_clear_error();
+  if (!logits || !deltas || !props || !cboxes || !cscores || R <= 0 || NC < 2 || B <= 0 || B > 65535)
+    return MEGA_ERR_ARG;
+  hipLaunchKernelGGL(post_prepare_kernel, dim3(cdiv(R, 64), B), dim3(64), 0, (hipStream_t)stream, logits, deltas,
+                     (const float4*)props, nprop, R, NC, wx, wy, ww, wh, logf(1000.f / 16.f), im_w, im_h, score_thresh,
+                     (float4*)cboxes, cscores, (float*)nullptr, (unsigned char*)nullptr);
+  return mega_check_launch();
+}
+
+extern "C" int mega_postprocess_candidates(const float* logits, const float* deltas, const float* props, const int* nprop,
+                                           int R, int NC, float wx, float wy, float ww, float wh, float im_w, float im_h,
+                                           float score_thresh, float* cboxes, float* cscores, void* stream) {
+  return mega_postprocess_candidates_batched(logits, deltas, props, nprop, 1, R, NC, wx, wy, ww, wh, im_w, im_h,
+                                             score_thresh, cboxes, cscores, stream);
+}
+
+// Library-internal (common.h): the lazy NMS and P4 of the post-processor, for the box-augmentation merge (bbox_aug.hip).
+int mega_boxes_nms_lazy(const float* boxes, const int* counts, const int* order, int P, int nmax, float thr, int strict_gt,
+                        int max_keep, int* keep_pos, int* keep_cnt, unsigned char* flags, hipStream_t st) {
+  if (nmax > SCAN_MAXCB * 64) return MEGA_ERR_ARG;
+  const size_t lds = (((size_t)nmax * 17 + 15) & ~(size_t)15) + (size_t)nmax * 2 + 16;
+  if (hipFuncSetAttribute((const void*)nms_lazy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return MEGA_ERR_LAUNCH;
+  hipLaunchKernelGGL(nms_lazy_kernel, dim3(P), dim3(1024), lds, st, (const float4*)boxes, counts,
+                     (const unsigned char*)nullptr, order, nmax, thr, strict_gt, max_keep, keep_pos, keep_cnt, flags);
+  return mega_check_launch();
+}
+
+int mega_boxes_post_finalize(const unsigned char* flags, const float* cboxes, const float* cscores, int B, int NCm1, int R,
+                             int max_det, float* out_boxes, float* out_scores, long long* out_labels, int* out_cnt,
+                             int* tmp_idx, hipStream_t st) {
+  hipLaunchKernelGGL(post_finalize_kernel, dim3(B), dim3(1024), 0, st, flags, (const float4*)cboxes, cscores, NCm1, R,
+                     max_det, (float4*)out_boxes, out_scores, out_labels, out_cnt, tmp_idx);
   return mega_check_launch();
 }
 

@@ -37,7 +37,9 @@ __device__ __forceinline__ unsigned char clip8(int v) {
   return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// in [N][Hi][Wi][3] -> out [N][Hi][Wo][3]; one thread per output pixel (3 channels).
+// in [N][Hi][Wi][3] -> out [N][Hi][Wo][3]; one thread per output pixel (3 channels).  Flip: the pixel is stored at the
+// mirrored column Wo - 1 - xo (TT.RandomHorizontalFlip after T.Resize, engine/bbox_aug.py:92-96).
+template <bool Flip>
 __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __restrict__ in,
                                                        unsigned char* __restrict__ out,
                                                        const int* __restrict__ bounds, const int* __restrict__ kk,
@@ -54,12 +56,14 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __re
       const int w = k[x];
       s0 += (int)p[3 * x] * w; s1 += (int)p[3 * x + 1] * w; s2 += (int)p[3 * x + 2] * w;
     }
-    unsigned char* o = out + i * 3;
+    unsigned char* o = out + (Flip ? (row * Wo + (Wo - 1 - xo)) : i) * 3;
     o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
   }
 }
 
 // in [N][Hi][W3] -> out [N][Ho][W3] (W3 = W*3 bytes per row); one thread per output byte, coalesced along the row.
+// Flip: the byte goes to the same channel of the mirrored pixel.
+template <bool Flip>
 __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __restrict__ in,
                                                        unsigned char* __restrict__ out,
                                                        const int* __restrict__ bounds, const int* __restrict__ kk,
@@ -75,7 +79,25 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __re
     const unsigned char* p = in + (n * Hi + ymin) * (size_t)W3 + xb;
     int s = 1 << (kPrecisionBits - 1);
     for (int y = 0; y < ymax; ++y) s += (int)p[(size_t)y * W3] * k[y];
-    out[i] = clip8(s);
+    if (Flip) {
+      const int x = xb / 3;
+      out[i - xb + (W3 - 3 - 3 * x) + (xb - 3 * x)] = clip8(s);
+    } else {
+      out[i] = clip8(s);
+    }
+  }
+}
+
+// Image.transpose(FLIP_LEFT_RIGHT) of [N][H][W][3]: one thread per output pixel.
+__global__ __launch_bounds__(256) void mirror_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
+                                                     int N, int H, int W) {
+  const size_t total = (size_t)N * H * W;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    const size_t row = i / W;
+    const unsigned char* p = in + (row * W + (W - 1 - x)) * 3;
+    unsigned char* o = out + i * 3;
+    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
   }
 }
 }  // namespace
@@ -117,12 +139,48 @@ extern "C" int mega_resize_bilinear_u8(const unsigned char* in, unsigned char* o
   const unsigned char* src = in;
   if (need_h) {   // horizontal first, exactly as ImagingResampleInner orders the passes
     unsigned char* dst = need_v ? tmp : out;
-    hipLaunchKernelGGL(resize_h_kernel, grid((size_t)N * Hi * Wo), dim3(256), 0, st, src, dst, bounds_h, coef_h,
+    hipLaunchKernelGGL(resize_h_kernel<false>, grid((size_t)N * Hi * Wo), dim3(256), 0, st, src, dst, bounds_h, coef_h,
                        ksize_h, N, Hi, Wi, Wo);
     src = dst;
   }
   if (need_v)
-    hipLaunchKernelGGL(resize_v_kernel, grid((size_t)N * Ho * Wo * 3), dim3(256), 0, st, src, out, bounds_v, coef_v,
+    hipLaunchKernelGGL(resize_v_kernel<false>, grid((size_t)N * Ho * Wo * 3), dim3(256), 0, st, src, out, bounds_v, coef_v,
                        ksize_v, N, Hi, Ho, Wo * 3);
+  return mega_check_launch();
+}
+
+// mega_resize_bilinear_u8 followed by a horizontal mirror of the result, the mirror folded into the last pass (hflip = 0:
+// exactly mega_resize_bilinear_u8).  Same size in and out with hflip = 1: the mirror alone.  out must not alias in.
+extern "C" int mega_resize_bilinear_u8_flip(const unsigned char* in, unsigned char* out, unsigned char* tmp, int N, int Hi,
+                                            int Wi, int Ho, int Wo, const int* bounds_h, const int* coef_h, int ksize_h,
+                                            const int* bounds_v, const int* coef_v, int ksize_v, int hflip, void* stream) {
+  if (!hflip)
+    return mega_resize_bilinear_u8(in, out, tmp, N, Hi, Wi, Ho, Wo, bounds_h, coef_h, ksize_h, bounds_v, coef_v, ksize_v,
+                                   stream);
+  mega_clear_error();
+  if (!in || !out || in == out || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return MEGA_ERR_ARG;
+  const bool need_h = Wo != Wi, need_v = Ho != Hi;
+  if ((need_h && (!bounds_h || !coef_h || ksize_h <= 0)) || (need_v && (!bounds_v || !coef_v || ksize_v <= 0)) ||
+      (need_h && need_v && !tmp))
+    return MEGA_ERR_ARG;
+  auto grid = [](size_t total) { return dim3((unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256)); };
+  hipStream_t st = (hipStream_t)stream;
+  if (!need_h && !need_v) {
+    hipLaunchKernelGGL(mirror_kernel, grid((size_t)N * Hi * Wi), dim3(256), 0, st, in, out, N, Hi, Wi);
+    return mega_check_launch();
+  }
+  if (!need_v) {        // the horizontal pass is the last one
+    hipLaunchKernelGGL(resize_h_kernel<true>, grid((size_t)N * Hi * Wo), dim3(256), 0, st, in, out, bounds_h, coef_h,
+                       ksize_h, N, Hi, Wi, Wo);
+    return mega_check_launch();
+  }
+  const unsigned char* src = in;
+  if (need_h) {
+    hipLaunchKernelGGL(resize_h_kernel<false>, grid((size_t)N * Hi * Wo), dim3(256), 0, st, in, tmp, bounds_h, coef_h,
+                       ksize_h, N, Hi, Wi, Wo);
+    src = tmp;
+  }
+  hipLaunchKernelGGL(resize_v_kernel<true>, grid((size_t)N * Ho * Wo * 3), dim3(256), 0, st, src, out, bounds_v, coef_v,
+                     ksize_v, N, Hi, Ho, Wo * 3);
   return mega_check_launch();
 }

@@ -111,7 +111,9 @@ class FrameSource(object):
     the device; prefetch(ids) starts the host decodes early."""
 
     def __init__(self, img_dir, pattern, seg_len, device, min_size=600, max_size=1000, workers=8, cache_frames=64,
-                 opener=None):
+                 opener=None, hflip=False):
+        # hflip: every fetched frame is mirrored left-right after the resize (a TEST.BBOX_AUG flip view, bbox_aug.py)
+        self.hflip = bool(hflip)
         self.img_dir, self.pattern, self.seg_len = img_dir, pattern, int(seg_len)
         self.device = torch.device(device)
         self.opener = opener or self._open
@@ -211,9 +213,11 @@ class FrameSource(object):
 
     def _resized(self, dev):
         if self.out_hw == self.in_hw:
-            return dev
+            return ops.resize_bilinear_u8_flip(dev, self.out_hw, None) if self.hflip else dev
         if self.tables is None:
             self.tables = ResizeTables(self.in_hw, self.out_hw, self.device)
+        if self.hflip:
+            return ops.resize_bilinear_u8_flip(dev, self.out_hw, self.tables)
         return ops.resize_bilinear_u8(dev, self.out_hw, self.tables)
 
     def _to_device(self, ids):

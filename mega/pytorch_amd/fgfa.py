@@ -665,8 +665,7 @@ class FgfaClipEngine(object):
         pp = box.post_processor
         if self.keep_intermediates:
             self._dbg_b = (props, logits, deltas, x, cnt)
-        return ops.postprocess(logits.float().contiguous(), deltas.float().contiguous(), props[0].contiguous(), cnt,
-                               pp.weights, W, H, pp.score_thresh, pp.nms, pp.detections_per_img, pp.strict_gt)
+        return pp.padded(logits.float().contiguous(), deltas.float().contiguous(), props[0].contiguous(), cnt, (W, H))
 
     def _body_bb(self, aggs, size):
         """_body_b for ALL maps of a group at once ([G,h,w,1024]): the RPN head, selection (one block per frame), res5, ROIAlign,
@@ -693,8 +692,8 @@ class FgfaClipEngine(object):
         x = fe.pooled_fc(y, [props[b] for b in range(G)])
         logits, deltas = box.predictor(x)
         pp = box.post_processor
-        return ops.postprocess_batched(logits.float().contiguous(), deltas.float().contiguous(), props.reshape(-1, 4).contiguous(), G,
-                                       pp.weights, W, H, pp.score_thresh, pp.nms, pp.detections_per_img, pp.strict_gt, nprop=cnt)
+        return pp.padded_batched(logits.float().contiguous(), deltas.float().contiguous(), props.reshape(-1, 4).contiguous(), G,
+                                 (W, H), nprop=cnt)
 
     def _eager(self, size, n):
         aggs = self._body_a()

@@ -120,20 +120,15 @@ def frame_feed(cfg, frames, idx):
     raise ValueError("frame_feed: MODEL.VID.METHOD = %r (mega runs through ClipEngine)" % method)
 
 
-def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_batch=10, seed=0, timer=None,
-                       source_kwargs=None, engine_kwargs=None):
-    """inference.py:17-47: -> {dataset index: BoxList on the host}, for every MODEL.VID.METHOD of the reference:
-      mega / rdn   ClipEngine on the video's FrameSource (RDN is the MEGA detector without memory / global pools: rdn.py).  The
-                   engine runs with reuse_records=True unless engine_kwargs says otherwise: every frame of a video goes
-                   through the frame stage once and serves both its local-window and its global-pool role (bit-identical
-                   detections on the GPU, ~half the backbone work); engine_kwargs={"per_frame": True}: RDN frame by frame;
-      fgfa / dff / base   fgfa.FgfaClipEngine / DffClipEngine / BaseClipEngine on the resident video (engine_kwargs: lookahead,
-                   graphs, pipeline, group / interval, lanes); engine_kwargs={"per_frame": True} runs the reference's call
-                   convention instead;
-      (per_frame)  the detector frame by frame on the reference's own test feed (frame_feed)."""
-    model.eval()
-    results = {}
-    videos = index.videos if videos is None else videos
+def _bbox_aug_cfg(cfg):
+    aug = getattr(getattr(cfg, "TEST", None), "BBOX_AUG", None)
+    return cfg if aug is not None and aug.ENABLED else None
+
+
+def _video_runner(model, steps_per_batch, seed, engine_kwargs):
+    """The engine of compute_on_dataset, built once -> run(src, v): the detections (list of BoxList on the device) of
+    video v whose frames come from the feed.FrameSource src.  Every call is a fresh video for the engine, so the views
+    of TEST.BBOX_AUG go through the same engine as consecutive videos do."""
     method = model.cfg.MODEL.VID.METHOD
     if method == "rdn" and not (engine_kwargs or {}).get("per_frame"):
         method = "mega"
@@ -149,42 +144,76 @@ def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_bat
                 eng = _fgfa.DffClipEngine(model, **{k: v for k, v in ek.items() if k in ("lookahead", "graphs", "pipeline", "interval", "lanes")})
             else:
                 eng = _fgfa.BaseClipEngine(model, **{k: v for k, v in ek.items() if k in ("group", "graphs", "pipeline", "lanes")})
-        for v in videos:
-            src = feed.FrameSource(os.path.join(img_dir, "%s.JPEG"), v["pattern"], v["seg_len"], device,
-                                   min_size=model.cfg.INPUT.MIN_SIZE_TEST, max_size=model.cfg.INPUT.MAX_SIZE_TEST,
-                                   **(source_kwargs or {}))
-            t0 = time.perf_counter()
-            with torch.no_grad():
-                frames = resident_video(src, model.cfg)
-                if eng is not None:
-                    dets = eng.run(frames, first=0, last=v["seg_len"])
-                else:
-                    dets = []
-                    for i in range(v["seg_len"]):
-                        out = model(frame_feed(model.cfg, frames, i))
-                        dets.append(out[0] if isinstance(out, (list, tuple)) else out)
-            if device.type == "cuda":
-                torch.cuda.synchronize(device)
-            if timer is not None:
-                timer["inference_s"] = timer.get("inference_s", 0.0) + time.perf_counter() - t0
-            for i, det in enumerate(dets):
-                results[v["start"] + i] = det.to("cpu")
-            src.close()
-        return results
+
+        def run(src, v):
+            frames = resident_video(src, model.cfg)
+            if eng is not None:
+                return eng.run(frames, first=0, last=v["seg_len"])
+            dets = []
+            for i in range(v["seg_len"]):
+                out = model(frame_feed(model.cfg, frames, i))
+                dets.append(out[0] if isinstance(out, (list, tuple)) else out)
+            return dets
+        return run
     ek = dict(reuse_records=model.cfg.MODEL.VID.METHOD == "mega")      # (RDN: a frame has one role, the local window)
     ek.update(engine_kwargs or {})
     ek.pop("per_frame", None)
     eng = _engine.ClipEngine(model, steps_per_batch=steps_per_batch, **ek)
     gsize = model.cfg.MODEL.VID.MEGA.GLOBAL.SIZE
-    for vi, v in enumerate(videos):
-        src = feed.FrameSource(os.path.join(img_dir, "%s.JPEG"), v["pattern"], v["seg_len"], device,
-                               min_size=model.cfg.INPUT.MIN_SIZE_TEST, max_size=model.cfg.INPUT.MAX_SIZE_TEST,
-                               **(source_kwargs or {}))
-        t0 = time.perf_counter()
-        # vid_mega.py:21-24 shuffles with numpy's global RNG; seeded per video here so runs are reproducible
+
+    def run(src, v):
+        # vid_mega.py:21-24 shuffles with numpy's global RNG; seeded per video here so runs are reproducible (and every
+        # TEST.BBOX_AUG view of a video has the same schedule)
         gfor = _engine.global_schedule(v["seg_len"], gsize, seed=seed + v["start"],
                                        shuffle=bool(model.cfg.MODEL.VID.MEGA.GLOBAL.SHUFFLE))
-        dets = eng.run(src, v["seg_len"], gfor)
+        return eng.run(src, v["seg_len"], gfor)
+    return run
+
+
+def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_batch=10, seed=0, timer=None,
+                       source_kwargs=None, engine_kwargs=None, bbox_aug_cfg=None):
+    """inference.py:17-47: -> {dataset index: BoxList on the host}, for every MODEL.VID.METHOD of the reference:
+      mega / rdn   ClipEngine on the video's FrameSource (RDN is the MEGA detector without memory / global pools: rdn.py).  The
+                   engine runs with reuse_records=True unless engine_kwargs says otherwise: every frame of a video goes
+                   through the frame stage once and serves both its local-window and its global-pool role (bit-identical
+                   detections on the GPU, ~half the backbone work); engine_kwargs={"per_frame": True}: RDN frame by frame;
+      fgfa / dff / base   fgfa.FgfaClipEngine / DffClipEngine / BaseClipEngine on the resident video (engine_kwargs: lookahead,
+                   graphs, pipeline, group / interval, lanes); engine_kwargs={"per_frame": True} runs the reference's call
+                   convention instead;
+      (per_frame)  the detector frame by frame on the reference's own test feed (frame_feed).
+    bbox_aug_cfg: a config whose TEST.BBOX_AUG.ENABLED is set (default: the model's own config, if set there): test-time
+    box augmentation of every video (bbox_aug.py) with that config's views, each view a pass through the same engine."""
+    model.eval()
+    results = {}
+    videos = index.videos if videos is None else videos
+    aug_cfg = bbox_aug_cfg if bbox_aug_cfg is not None else _bbox_aug_cfg(model.cfg)
+    run = _video_runner(model, steps_per_batch, seed, engine_kwargs)
+    pattern = os.path.join(img_dir, "%s.JPEG")
+    for v in videos:
+        def source(min_size, max_size, hflip=False):
+            return feed.FrameSource(pattern, v["pattern"], v["seg_len"], device, min_size=min_size, max_size=max_size,
+                                    hflip=hflip, **(source_kwargs or {}))
+        if aug_cfg is None:
+            src = source(model.cfg.INPUT.MIN_SIZE_TEST, model.cfg.INPUT.MAX_SIZE_TEST)
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                dets = run(src, v)
+        else:
+            from . import bbox_aug
+            src = source(aug_cfg.INPUT.MIN_SIZE_TEST, aug_cfg.INPUT.MAX_SIZE_TEST)      # the identity view's feed
+            views = bbox_aug.views_from_cfg(aug_cfg, (src.in_hw[1], src.in_hw[0]))
+
+            def run_view(view):
+                if view == views[0]:
+                    return run(src, v)
+                s = source(view.min_size, view.max_size, view.hflip)
+                try:
+                    return run(s, v)
+                finally:
+                    s.close()
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                dets = bbox_aug.detect_video(model, views, run_view)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         if timer is not None:
@@ -285,7 +314,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     mine = videos_for_rank(index.videos, rank, world)
     timer = {}
     t0 = time.perf_counter()
-    preds = compute_on_dataset(model, index, img_dir, device, videos=mine, timer=timer, **kw)
+    # TEST.BBOX_AUG.ENABLED is read from cfg, as tools/test_net.py does (engine/inference.py:26)
+    preds = compute_on_dataset(model, index, img_dir, device, videos=mine, timer=timer, bbox_aug_cfg=_bbox_aug_cfg(cfg),
+                               **kw)
     if world > 1:
         dist.barrier(group=group)
     total = time.perf_counter() - t0

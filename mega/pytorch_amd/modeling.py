@@ -1263,24 +1263,55 @@ class PostProcessor(nn.Module):
         self.score_thresh, self.nms, self.detections_per_img = rh.SCORE_THRESH, rh.NMS, rh.DETECTIONS_PER_IMG
         self.weights = tuple(rh.BBOX_REG_WEIGHTS)
         self.strict_gt = bool(getattr(cfg, "NMS_STRICT_GT", True))
+        # TEST.BBOX_AUG.ENABLED (box_head/inference.py:79-86 bbox_aug_enabled): every output is the image's CANDIDATES
+        # instead of its detections -- (NC-1)*R rows, class-major (row j*R + r = class j+1 of proposal r), the box decoded
+        # and clipped, the score -1 where it is not > SCORE_THRESH; the merge of the views runs later (bbox_aug.py)
+        aug = getattr(getattr(cfg, "TEST", None), "BBOX_AUG", None)
+        self.candidates = bool(getattr(aug, "ENABLED", False))
+
+    @staticmethod
+    def _candidate_tail(C1, R, device, B=None):
+        """labels [C1*R] (class-major) and the device count(s) C1*R of a candidate output: built by kernels on every call
+        (no cached tensor: a call captured into a hipGraph must not hand out memory that only a replay fills)"""
+        lab = torch.arange(1, C1 + 1, dtype=torch.int64, device=device).view(-1, 1).expand(C1, R).reshape(-1)
+        cnt = torch.full((1 if B is None else B,), C1 * R, dtype=torch.int32, device=device)
+        return lab, cnt
+
+    def padded(self, logits, deltas, props, nprop, size):
+        """One image's padded outputs + device-side count (ob [cap,4], os [cap], ol [cap] i64, oc [1] i32), no host sync:
+        its detections, or in candidate mode its candidates (cap = (NC-1)*R, oc = cap)."""
+        im_w, im_h = size
+        if self.candidates:
+            cb, cs = ops.postprocess_candidates(logits, deltas, props, nprop, self.weights, im_w, im_h, self.score_thresh)
+            lab, cnt = self._candidate_tail(cb.shape[0], cb.shape[1], cb.device)
+            return cb.view(-1, 4), cs.view(-1), lab, cnt
+        return ops.postprocess(logits, deltas, props, nprop, self.weights, im_w, im_h, self.score_thresh, self.nms,
+                               self.detections_per_img, self.strict_gt)
+
+    def padded_batched(self, logits, deltas, props, B, size, nprop=None):
+        """padded() for B images of R = rows / B each in one launch chain: (ob [B,cap,4], os [B,cap], ol [B,cap], oc [B])."""
+        im_w, im_h = size
+        if self.candidates:
+            cb, cs = ops.postprocess_candidates_batched(logits, deltas, props, B, self.weights, im_w, im_h,
+                                                        self.score_thresh, nprop=nprop)
+            lab, cnt = self._candidate_tail(cb.shape[1], cb.shape[2], cb.device, B)
+            return cb.view(B, -1, 4), cs.view(B, -1), lab.expand(B, -1), cnt
+        return ops.postprocess_batched(logits, deltas, props, B, self.weights, im_w, im_h, self.score_thresh, self.nms,
+                                       self.detections_per_img, self.strict_gt, nprop=nprop)
 
     def run(self, x, bl):
         """Sync-free form: padded outputs + device-side count (ob [cap,4], os [cap], ol [cap] i64, oc [1] i32)."""
         class_logits, box_regression = x
-        im_w, im_h = bl.size
-        return ops.postprocess(class_logits.float().contiguous(), box_regression.float().contiguous(),
-                               bl.bbox.float().contiguous(), None, self.weights, im_w, im_h,
-                               self.score_thresh, self.nms, self.detections_per_img, self.strict_gt)
+        return self.padded(class_logits.float().contiguous(), box_regression.float().contiguous(),
+                           bl.bbox.float().contiguous(), None, bl.size)
 
     def run_batch(self, x, boxes, size):
         """run() for several images with the same number of rows (x = the concatenated logits / deltas, boxes = the
         list of their [R,4] proposal boxes): one launch chain; returns one run()-style tuple per image."""
         class_logits, box_regression = x
         B = len(boxes)
-        ob, os_, ol, oc = ops.postprocess_batched(class_logits.float().contiguous(), box_regression.float().contiguous(),
-                                                  torch.cat([b.float() for b in boxes], dim=0), B, self.weights,
-                                                  size[0], size[1], self.score_thresh, self.nms,
-                                                  self.detections_per_img, self.strict_gt)
+        ob, os_, ol, oc = self.padded_batched(class_logits.float().contiguous(), box_regression.float().contiguous(),
+                                              torch.cat([b.float() for b in boxes], dim=0), B, size)
         return [(ob[b], os_[b], ol[b], oc[b:b + 1]) for b in range(B)]
 
     @staticmethod

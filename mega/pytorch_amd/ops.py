@@ -615,6 +615,84 @@ def postprocess_batched(logits, deltas, props, B, weights, im_w, im_h, score_thr
     return ob, os_, ol, oc
 
 
+def postprocess_candidates_batched(logits, deltas, props, B, weights, im_w, im_h, score_thresh, nprop=None):
+    """The candidates of B images of R = rows / B proposals each (include/mega_hip.h mega_postprocess_candidates_batched):
+    (boxes [B,NC-1,R,4], scores [B,NC-1,R]) -- class j + 1, proposal row r; the score is -1 where it is not > score_thresh
+    or r >= nprop[b]."""
+    _gpu(logits, deltas, props)
+    lib = _lib.load()
+    NC = logits.shape[1]
+    assert logits.shape[0] % B == 0
+    R = logits.shape[0] // B
+    assert logits.dtype == torch.float32 and deltas.dtype == torch.float32 and props.dtype == torch.float32
+    assert logits.is_contiguous() and deltas.is_contiguous() and props.is_contiguous()
+    assert deltas.shape == (B * R, NC * 4) and props.shape == (B * R, 4)
+    if nprop is not None:
+        _gpu(nprop)
+        assert nprop.dtype == torch.int32 and nprop.numel() == B and nprop.is_contiguous()
+    dev = logits.device
+    cb = torch.empty((B, NC - 1, R, 4), dtype=torch.float32, device=dev)
+    cs = torch.empty((B, NC - 1, R), dtype=torch.float32, device=dev)
+    wx, wy, ww, wh = weights
+    _tok = _pb("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4)
+    rc = lib.mega_postprocess_candidates_batched(_ptr(logits), _ptr(deltas), _ptr(props), _ptr(nprop), B, R, NC, wx, wy,
+                                                 ww, wh, float(im_w), float(im_h), float(score_thresh), _ptr(cb), _ptr(cs),
+                                                 _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_postprocess_candidates_batched")
+    return cb, cs
+
+
+def postprocess_candidates(logits, deltas, props, nprop, weights, im_w, im_h, score_thresh):
+    """One image: (boxes [NC-1,R,4], scores [NC-1,R]) as postprocess_candidates_batched."""
+    if nprop is not None:
+        nprop = nprop.reshape(1)
+    cb, cs = postprocess_candidates_batched(logits, deltas, props, 1, weights, im_w, im_h, score_thresh, nprop=nprop)
+    return cb[0], cs[0]
+
+
+BBOX_AUG_MAX_VIEWS = 16
+BBOX_AUG_MAX_ROWS = 8192
+
+
+def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh, max_det, strict_gt=True):
+    """Test-time box augmentation merge of F frames x K views (include/mega_hip.h mega_bbox_aug_merge).
+    cboxes [K,F,NC-1,R,4] / cscores [K,F,NC-1,R] f32 (the candidates of every view, each in its own image), view_sizes
+    [(w, h)] x K (view 0 = the identity view, whose image the results are in), view_flips [bool] x K.  Returns
+    (boxes [F,cap,4], scores [F,cap], labels [F,cap] i64, counts [F] i32 device), cap = (NC-1) * K * R: frame f's
+    detections are the first counts[f] rows.  Raises ValueError beyond K = 16 views or K * R = 8192 rows per class."""
+    _gpu(cboxes, cscores)
+    lib = _lib.load()
+    K, F, C1, R = cscores.shape
+    if K != len(view_sizes) or K != len(view_flips):
+        raise ValueError("bbox_aug_merge: %d views of candidates, %d sizes, %d flips" % (K, len(view_sizes), len(view_flips)))
+    if K > BBOX_AUG_MAX_VIEWS or K * R > BBOX_AUG_MAX_ROWS:
+        raise ValueError("bbox_aug_merge: %d views x %d rows per class; the merge takes at most %d views and %d rows "
+                         "per (frame, class)" % (K, R, BBOX_AUG_MAX_VIEWS, BBOX_AUG_MAX_ROWS))
+    assert cboxes.shape == (K, F, C1, R, 4) and cboxes.dtype == torch.float32 and cscores.dtype == torch.float32
+    assert cboxes.is_contiguous() and cscores.is_contiguous()
+    dev = cboxes.device
+    cap = C1 * K * R
+    ob = torch.empty((F, cap, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((F, cap), dtype=torch.float32, device=dev)
+    ol = torch.empty((F, cap), dtype=torch.int64, device=dev)
+    oc = torch.zeros((F,), dtype=torch.int32, device=dev)
+    nb = lib.mega_bbox_aug_merge_workspace_bytes(F, K, R, C1 + 1)
+    ws = _ws(nb, dev)
+    arr = ctypes.c_int * K
+    vw = arr(*[int(s[0]) for s in view_sizes])
+    vh = arr(*[int(s[1]) for s in view_sizes])
+    vf = arr(*[1 if f else 0 for f in view_flips])
+    _tok = _pb("bbox_aug_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
+    rc = lib.mega_bbox_aug_merge(_ptr(cboxes), _ptr(cscores), F, K, R, C1 + 1, ctypes.cast(vw, ctypes.c_void_p),
+                                 ctypes.cast(vh, ctypes.c_void_p), ctypes.cast(vf, ctypes.c_void_p), float(score_thresh),
+                                 float(nms_thresh), int(strict_gt), int(max_det), _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc),
+                                 _ptr(ws), nb, _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_bbox_aug_merge")
+    return ob, os_, ol, oc
+
+
 # ------------------------------------------------------------------------------------------------ relation module
 def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False):
     """-> [16, Nq, ldp] f32 with ldp = roundup(Nk, 32).  precise=False: fast sin/cos (bf16 mode).
@@ -901,6 +979,30 @@ def resize_bilinear_u8(frames_u8, out_hw, tables):
                                      tables.ksize_v, _stream())
     _pe(_tok)
     _lib.check(rc, "mega_resize_bilinear_u8")
+    return out
+
+
+def resize_bilinear_u8_flip(frames_u8, out_hw, tables, hflip=True):
+    """resize_bilinear_u8 followed by a left-right mirror (PIL resize(BILINEAR).transpose(FLIP_LEFT_RIGHT)), the mirror
+    written by the last pass.  tables may be None when out_hw is the input size (the mirror alone)."""
+    _gpu(frames_u8)
+    lib = _lib.load()
+    N, Hi, Wi, C = frames_u8.shape
+    Ho, Wo = out_hw
+    assert C == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    if (Ho, Wo) != (Hi, Wi):
+        assert tables is not None and tables.in_hw == (Hi, Wi) and tables.out_hw == (Ho, Wo)
+    out = torch.empty((N, Ho, Wo, 3), dtype=torch.uint8, device=frames_u8.device)
+    tmp = torch.empty((N, Hi, Wo, 3), dtype=torch.uint8, device=frames_u8.device) if (Hi != Ho and Wi != Wo) else None
+    t = tables
+    _tok = _pb("resize", 0.0, frames_u8.numel() + out.numel() * 3)
+    rc = lib.mega_resize_bilinear_u8_flip(_ptr(frames_u8), _ptr(out), _ptr(tmp), N, Hi, Wi, Ho, Wo,
+                                          _ptr(t.bounds_h) if t else None, _ptr(t.coef_h) if t else None,
+                                          t.ksize_h if t else 0, _ptr(t.bounds_v) if t else None,
+                                          _ptr(t.coef_v) if t else None, t.ksize_v if t else 0, int(bool(hflip)),
+                                          _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_resize_bilinear_u8_flip")
     return out
 
 
