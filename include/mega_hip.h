@@ -61,10 +61,10 @@ int mega_conv2d_nhwc_tile(int M, int Cout, int K);
  * same MFMA instruction, so the choice never changes a result bit. */
 int mega_conv2d_nhwc_plan(int M, int Cout, int K, int in_dtype);
 /* The shape-complete form: which kernel mega_conv2d_nhwc[_ws] really dispatches THIS layer to (same predicates as the
- * launch path): kind 2 = igemm2_kernel (round 6: 128 x 256 tiles at two blocks per CU -- the streaming class, 1x1 with K <= 512,
- * by default), kind 4 = igemm4_kernel matrix class (round 6: the igemm8 tiles on 4 waves of 512 registers, 128 x 128 outputs per
- * wave), 3 = igemm4 streaming class (only with MEGA_IGEMM4=2), kind 6 = conv3x3_c64_kernel (layer1's 3x3 64 -> 64 conv: 3x3, stride 1, pad 1, bf16 out, no residual,
- * enough tiles), 7 = igemm8 streaming class (1x1, K <= 512), 8 = igemm8 matrix class, 0 = igemm_kernel.  -1: bad shape. */
+ * launch path: one function decides for both): kind 6 = conv3x3_c64_kernel (layer1's 3x3 64 -> 64 conv: 3x3, stride 1, pad 1,
+ * 16-bit out, no residual, enough tiles), 7 = igemm8 streaming class (1x1, K <= 512), 8 = igemm8 matrix class, 0 = igemm_kernel.
+ * -1: bad shape.  The split count is the one of mega_conv2d_nhwc_ws (a function of K alone).  (Kinds 1-4 were round 6's three
+ * opt-in GEMM kernels: measured at or below igemm8, profiles/r06_streaming_class_experiments.txt, and removed.) */
 int mega_conv2d_nhwc_plan_ex(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int ldo,
                              int has_residual, int in_dtype, int out_dtype);
 
@@ -96,14 +96,11 @@ int mega_stem_conv_bn_relu_bf16_u8(const void* frames_u8, const void* w_n176_bf1
                                    void* out, int N, int H, int W, float mean0, float mean1, float mean2, int to_bgr,
                                    void* stream);
 
-/* The whole stem of resnet.py:355-366 in one kernel (bf16): conv 7x7/2 + FrozenBN + ReLU + F.max_pool2d(3, 2, 1); `in` =
+/* The whole stem of resnet.py:355-366 in one kernel (16-bit types): conv 7x7/2 + FrozenBN + ReLU + F.max_pool2d(3, 2, 1); `in` =
  * the preprocessed f32 NCHW image (u8 = 0) or the uint8 RGB frames [N][H][W][3] with the preprocessing on the patch load
  * (u8 = 1; mean / to_bgr as above); out NHWC bf16 [N][Hp][Wp][64], Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The stem's own
  * 64-channel map is never written.  Same bits as mega_stem_conv_bn_relu_bf16[_u8] + mega_maxpool3x3s2_nhwc. */
-int mega_stem_pool_bf16(const void* in, int u8, const void* w_n176_bf16, const float* scale, const float* bias, void* out,
-                        int N, int H, int W, float mean0, float mean1, float mean2, int to_bgr, void* stream);
-
-/* mega_stem_pool_bf16 for either 16-bit type: dtype = MEGA_BF16 or MEGA_F16 is the type of w_n176 and of `out`. */
+/* dtype = MEGA_BF16 or MEGA_F16 is the type of w_n176 and of `out`. */
 int mega_stem_pool_dt(const void* in, int u8, const void* w_n176, const float* scale, const float* bias, void* out, int N,
                       int H, int W, float mean0, float mean1, float mean2, int to_bgr, int dtype, void* stream);
 
@@ -144,11 +141,7 @@ int mega_nms_sorted(const float* boxes, const int* counts, const unsigned char* 
  *   rpn_out [B][Hf*Wf][ldc] f32: channel a = objectness logit of anchor a, channel A + 4a + j = delta j
  *   outputs: proposals [B][post_nms_top_n][4], prop_scores [B][post_nms_top_n], prop_cnt [B] (device) */
 size_t mega_rpn_select_workspace_bytes(int B, int pre_nms_top_n);
-int mega_rpn_select(const float* rpn_out, const float* cell_anchors, int B, int Hf, int Wf, int A, int ldc,
-                    int anchor_stride, int pre_nms_top_n, int post_nms_top_n, float nms_thresh, int strict_gt,
-                    float min_size, float im_w, float im_h, float* proposals, float* prop_scores, int* prop_cnt,
-                    void* ws, size_t ws_bytes, void* stream);
-/* The same with prop_index [B][post_nms_top_n] (NULL allowed): the flat anchor index (y * Wf + x) * A + a of every
+/* prop_index [B][post_nms_top_n] (NULL allowed): the flat anchor index (y * Wf + x) * A + a of every
  * kept proposal (-1 in unused rows) = the reference's index into permute_and_flatten's (N, H*W*A) order
  * (rpn/utils.py:10-14, rpn/inference.py:93-104) after NMS: what "bit-exact proposal indices" is checked on. */
 int mega_rpn_select_idx(const float* rpn_out, const float* cell_anchors, int B, int Hf, int Wf, int A, int ldc,
@@ -185,9 +178,6 @@ int mega_postprocess_batched(const float* logits, const float* deltas, const flo
  * without the background class and with the score threshold applied.  No workspace.
  *   cboxes [B][NC-1][R][4] (class j + 1, proposal row r), cscores [B][NC-1][R]: the softmax score, -1 when it is not
  *   > score_thresh or r >= nprop[b]. */
-int mega_postprocess_candidates(const float* logits, const float* deltas, const float* props, const int* nprop, int R,
-                                int NC, float wx, float wy, float ww, float wh, float im_w, float im_h,
-                                float score_thresh, float* cboxes, float* cscores, void* stream);
 int mega_postprocess_candidates_batched(const float* logits, const float* deltas, const float* props, const int* nprop,
                                         int B, int R, int NC, float wx, float wy, float ww, float wh, float im_w,
                                         float im_h, float score_thresh, float* cboxes, float* cscores, void* stream);
@@ -226,16 +216,11 @@ int mega_relation_attention(const void* q, int ldq, const void* k, int ldk, cons
 /* The key range of one call is split over mega_relation_attention_splits() block groups (flash-decoding style:
  * partial max / sum / output per split, merged by a second kernel) when ws holds at least
  * mega_relation_attention_workspace_bytes(); with ws == NULL the call runs unsplit. */
-/* bf16-mode pair of the two calls above with the logits kept in bf16 and in the attention kernel's own tile order:
- * out_bf16 / pos_tiled_bf16 = [16][ceil(Nk/32)][Nq][32] bf16 (16 * ceil(Nk/32) * Nq * 64 bytes, 16-byte aligned), the
+/* The 16-bit pair of the two calls above (mega_position_logits_tiled_dt, mega_relation_attention_tiled_pos_dt below) keeps the
+ * logits in 16 bits and in the attention kernel's own tile order:
+ * out16 / pos_tiled16 = [16][ceil(Nk/32)][Nq][32] bf16 (16 * ceil(Nk/32) * Nq * 64 bytes, 16-byte aligned), the
  * 32 keys of a tile stored as (h2, rq, e) with key = 8 rq + 4 h2 + e.  Half the bytes of the f32 form, written by the
  * matrix-core position kernel and read by the attention kernel in fully coalesced 2 KiB blocks one tile pair ahead. */
-int mega_position_logits_tiled(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
-                               const float* dim_mat, void* out_bf16, int Nq, int Nk, void* stream);
-int mega_relation_attention_tiled_pos(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,
-                                      const void* pos_tiled_bf16, const void* resid, int ldr, const float* bias_v,
-                                      void* out, int ldo, int Nq, int Nk, int groups, float scale, void* ws,
-                                      size_t ws_bytes, void* stream);
 int mega_relation_attention_splits(int Nq, int Nk, int groups);
 size_t mega_relation_attention_workspace_bytes(int Nq, int Nk, int groups);
 
@@ -299,34 +284,22 @@ int mega_dff_warp_scale(const void* feats, const float* flow, const void* scale,
  * Destinations must not overlap; addresses / strides / row lengths 2-byte aligned at least.  Bit-exact data movement. */
 int mega_copy_segments(const void* segs, int n, void* stream);
 
-/* dst[i] = bf16(src[i]) (round to nearest even), n contiguous elements, both pointers 16-byte aligned: the rounded copy
- * of the head's f32 activation stream that the bf16 Wq / Wk / Wv projections read
- * (roi_box_feature_extractors.py:584-597 run in one dtype; this is the mixed-precision seam of the bf16 mode). */
-int mega_cast_f32_to_bf16(const float* src, void* dst_bf16, size_t n, void* stream);
-
 /* The identity bottleneck of the backbone's full-resolution stage -- layer1 blocks 1, 2 of ResNet-50/101-C4
  * (backbone/resnet.py:324-344: 256 -> 64 (1x1) -> 64 (3x3, pad 1) -> 256 (1x1) channels, stride 1, FrozenBN as f32
  * scale / bias vectors (layers/batch_norm.py:19-31), residual = the block's input) -- in ONE persistent kernel:
  *   out = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + x),   x, out: NHWC bf16 [N][H][W][256],
  * w1 [64][256], w2 [64][3][3][64], w3 [256][64] bf16 (OHWI).  The 64-channel intermediates never leave the CU.  Same MFMA,
- * K order, roundings and epilogue arithmetic as the three mega_conv2d_nhwc launches it replaces: bit-identical. */
-int mega_bottleneck64_fwd(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                          const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
-                          void* stream);
+ * K order, roundings and epilogue arithmetic as the three mega_conv2d_nhwc launches it replaces: bit-identical.
+ * dtype = MEGA_BF16 / MEGA_F16: the 16-bit type of x, every w and out (both fused bottlenecks). */
+int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                             const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
+                             int dtype, void* stream);
 
 /* The stage's first block with the 1x1 downsample branch on the residual (layer1 block 0: 64 -> 64 -> 64 (3x3) -> 256,
  * backbone/resnet.py:266-276,:324-344), one persistent kernel:
  *   out = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + bnd(convd(x))),  x NHWC bf16 [N][H][W][64], out [N][H][W][256];
  * w1 [64][64], w2 [64][3][3][64], w3 / wd [256][64].  The identity branch is computed from the x patch already in LDS and
  * rounded to bf16 before the add (as the separate launch would): bit-identical to the four mega_conv2d_nhwc launches. */
-int mega_bottleneck64_ds_fwd(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                             const float* b2, const void* w3, const float* s3, const float* b3, const void* wd, const float* sd,
-                             const float* bd, void* out, int N, int H, int W, void* stream);
-
-/* The two fused bottlenecks above for either 16-bit type (dtype = MEGA_BF16 / MEGA_F16: the type of x, every w and out). */
-int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                             const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
-                             int dtype, void* stream);
 int mega_bottleneck64_ds_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
                                 const float* b2, const void* w3, const float* s3, const float* b3, const void* wd, const float* sd,
                                 const float* bd, void* out, int N, int H, int W, int dtype, void* stream);
@@ -342,12 +315,12 @@ int mega_split_f32_to_bf16x3(const float* src, void* dst_bf16, int rows, int K, 
  * activation x [M][C] lives in HBM as bf16 [M][2C] = [hi | lo], hi = bf16(x), lo = bf16(x - hi): x = hi + lo to ~2^-17. */
 
 /* dst [rows][2K] bf16 = [hi | lo] of src [rows][K] f32 (K % 8 == 0, both 16-byte aligned). */
-int mega_split_f32_to_planes(const float* src, void* dst_bf16, int rows, int K, void* stream);
+int mega_split_f32_to_planes_dt(const float* src, void* dst, int rows, int K, int dtype, void* stream);
 
 /* mega_roi_align_fwd on f32 NHWC features with the pooled rows leaving as planes: out bf16 [K][2 PH PW C] = [hi | lo] of the
  * f32 row [PH PW C] (same term order as the f32 kernel, ROIAlign_cuda.cu:64-122).  C % 4 == 0. */
-int mega_roi_align_fwd_planes(const float* feat, const float* rois, void* out_planes, int K, int C, int H, int W,
-                              float spatial_scale, int pooled_h, int pooled_w, int sampling_ratio, void* stream);
+int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois, void* out_planes, int K, int C, int H, int W,
+                                 float spatial_scale, int pooled_h, int pooled_w, int sampling_ratio, int dtype, void* stream);
 
 /* conv + FrozenBN (+ split residual) + activation on plane tensors, bf16 matrix cores, f32 accumulation (igemm8 SP kernels):
  *   in       bf16 [N][H][W][ldi]; the contraction runs over Cin channels per tap, SOURCE channel k < kwrap ? k : k - kwrap
@@ -359,39 +332,33 @@ int mega_roi_align_fwd_planes(const float* feat, const float* rois, void* out_pl
  *   relu     0 none, 1 ReLU, 2 LeakyReLU(0.1)
  * Cin % 64 == 0, kwrap % 64 == 0, Cout % 8 == 0, every tensor below 2 GiB (MEGA_ERR_ARG otherwise).  ws / ws_bytes: the
  * split-K workspace of mega_conv2d_nhwc_workspace_bytes(M, Cout, R S Cin) (long-K layers: f32 output without residual). */
-int mega_conv2d_nhwc_sp(const void* in, int ldi, int kwrap, const void* w, const float* scale, const float* bias,
-                        const void* residual, int ldr, void* out, int ldo, int out_mode, int N, int H, int W, int Cin,
-                        int Cout, int R, int S, int stride, int pad, int dil, int relu, void* ws, size_t ws_bytes,
-                        void* stream);
-
-/* The plane kernels above for either 16-bit type (dtype = MEGA_BF16 / MEGA_F16: the type of the [hi | lo] pairs and of the
- * weights).  MEGA_F16 carries the TWO-PASS form of the fp16 mode (conv_mode "h2"): ldi = 2C, Cin = 2C, kwrap = 0 reads the planes
- * as [hi | lo] against weights packed [W | W] per tap, W rounded to fp16 once -- x_hi.W + x_lo.W: exact activations (to ~2^-22)
- * against single-rounded weights, f32 accumulation, twice the matrix-core work of the one-pass fp16 mode. */
-int mega_split_f32_to_planes_dt(const float* src, void* dst, int rows, int K, int dtype, void* stream);
-int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois, void* out_planes, int K, int C, int H, int W,
-                                 float spatial_scale, int pooled_h, int pooled_w, int sampling_ratio, int dtype, void* stream);
 int mega_conv2d_nhwc_sp_dt(const void* in, int ldi, int kwrap, const void* w, const float* scale, const float* bias,
                            const void* residual, int ldr, void* out, int ldo, int out_mode, int N, int H, int W, int Cin,
                            int Cout, int R, int S, int stride, int pad, int dil, int relu, int dtype, void* ws, size_t ws_bytes,
                            void* stream);
 
-/* mega_copy_segments with an f32 -> bf16 conversion on the way (source blocks f32, destination blocks bf16; row_bytes =
+/* The three plane entry points above take either 16-bit type (dtype = MEGA_BF16 / MEGA_F16: the type of the [hi | lo] pairs and of
+ * the weights; the text above describes MEGA_BF16).  MEGA_F16 carries the TWO-PASS form of the fp16 mode (conv_mode "h2"): ldi = 2C, Cin = 2C, kwrap = 0 reads the planes
+ * as [hi | lo] against weights packed [W | W] per tap, W rounded to fp16 once -- x_hi.W + x_lo.W: exact activations (to ~2^-22)
+ * against single-rounded weights, f32 accumulation, twice the matrix-core work of the one-pass fp16 mode. */
+
+/* mega_copy_segments with an f32 -> 16-bit conversion on the way (source blocks f32, destination blocks dtype = MEGA_BF16 /
+ * MEGA_F16; row_bytes =
  * SOURCE bytes per row, a multiple of 32; 16-byte aligned on both sides): a concatenation of f32 row blocks delivered as the
  * rounded copy the bf16 projections read (roi_box_feature_extractors.py:812-814 pools with an f32 activation stream). */
-int mega_copy_cast_segments(const void* segs, int n, void* stream);
-
-/* mega_cast_f32_to_bf16 / mega_copy_cast_segments with the destination type as a code (MEGA_BF16 / MEGA_F16): the rounded
- * copies of the head's f32 activation stream that its 16-bit projections read. */
-int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int dtype, void* stream);
 int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, void* stream);
+
+/* dst[i] = half(src[i]) (round to nearest even; dtype = MEGA_BF16 / MEGA_F16), n contiguous elements, both pointers 16-byte
+ * aligned: the rounded copy of the head's f32 activation stream that the 16-bit Wq / Wk / Wv projections read
+ * (roi_box_feature_extractors.py:584-597 run in one dtype; this is the mixed-precision seam of the 16-bit modes). */
+int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int dtype, void* stream);
 
 /* hipGetErrorString of the last launch failure any entry point of this library reported (MEGA_ERR_LAUNCH). */
 const char* mega_last_error_string(void);
 
 /* Several independent relation-attention problems (the key frames of one engine step-batch at the same stage) in ONE
  * launch (+ one combine launch).  Every problem runs exactly the code and the key-range split of its own
- * mega_relation_attention / mega_relation_attention_tiled_pos call: identical bits.  n <= 16; all problems share groups,
+ * mega_relation_attention / mega_relation_attention_tiled_pos_dt call: identical bits.  n <= 16; all problems share groups,
  * scale, dtype and the kind of position term (none / f32 rows `pos` with ldp / tile-ordered bf16 `pos_tiled`). */
 typedef struct {
   const void* q; const void* k; const void* vt; const float* pos; const void* pos_tiled; const void* resid;
@@ -410,15 +377,13 @@ typedef struct {
 int mega_relation_attention_batched(const void* descs /* mega_attn_desc[n], host memory */, int n, int groups,
                                     float scale, int dtype, void* stream);
 
-/* mega_position_logits_tiled for n <= 16 (query boxes, key boxes) problems in one launch. */
+/* mega_position_logits_tiled_dt for n <= 16 (query boxes, key boxes) problems in one launch (mega_position_logits_tiled_batched_dt). */
 typedef struct { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; } mega_pos_desc;
-int mega_position_logits_tiled_batched(const void* descs /* mega_pos_desc[n], host memory */, int n, const float* wg_t,
-                                       const float* bg, const float* dim_mat, void* stream);
 
 /* Round 6: the head on IEEE-half operands (cfg.HEAD_DTYPE "float16": Q K^T, P V and the position term on
  * v_mfma_f32_32x32x16_f16 / 16x16x32_f16 -- the bf16 rate and bytes, 11 significant bits instead of 8).  The three
- * tile-ordered-logit entry points above with the 16-bit type as an argument: dtype = MEGA_BF16 (the calls above) or
- * MEGA_F16; the logits / Q / K / V^T are that type.  mega_relation_attention and mega_relation_attention_batched take
+ * tile-ordered-logit entry points take the 16-bit type as an argument: dtype = MEGA_BF16 or MEGA_F16; the logits / Q / K /
+ * V^T are that type.  mega_relation_attention and mega_relation_attention_batched take
  * MEGA_F16 through their own dtype argument.  Replaces the same reference code as the bf16 forms:
  * roi_box_feature_extractors.py:126-176 (position embedding), :567-646 (attention_module_multi_head). */
 int mega_position_logits_tiled_dt(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,

@@ -21,7 +21,6 @@ SIGNATURES = {
     "mega_stem_conv_bn_relu": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "mega_stem_conv_bn_relu_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "mega_stem_conv_bn_relu_bf16_u8": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float] * 3 + [c_int, c_void_p]),
-    "mega_stem_pool_bf16": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_float] * 3 + [c_int, c_void_p]),
     "mega_stem_pool_dt": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_float] * 3 + [c_int, c_int, c_void_p]),
     "mega_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
     "mega_avgpool2x2_ceil_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
@@ -32,8 +31,6 @@ SIGNATURES = {
     "mega_nms_sorted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_int, c_int] + [c_void_p] * 4 +
                         [c_size_t, c_void_p]),
     "mega_rpn_select_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_rpn_select": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_int, c_float, c_float, c_float] +
-                        [c_void_p] * 4 + [c_size_t, c_void_p]),
     "mega_rpn_select_idx": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_int, c_float, c_float, c_float] +
                             [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mega_postprocess_workspace_bytes": (c_size_t, [c_int, c_int]),
@@ -42,23 +39,17 @@ SIGNATURES = {
     "mega_postprocess_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mega_postprocess_batched": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int] + [c_float] * 8 + [c_int, c_int] +
                                  [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "mega_postprocess_candidates": (c_int, [c_void_p] * 4 + [c_int, c_int] + [c_float] * 7 + [c_void_p] * 3),
     "mega_postprocess_candidates_batched": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float] * 7 + [c_void_p] * 3),
     "mega_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 4),
     "mega_bbox_aug_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_float, c_float, c_int, c_int] +
                             [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mega_position_logits": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
-    "mega_position_logits_tiled": (c_int, [c_void_p] * 6 + [c_int] * 2 + [c_void_p]),
-    "mega_relation_attention_tiled_pos": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                                  c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                                  c_float, c_void_p, c_size_t, c_void_p]),
     "mega_relation_attention_splits": (c_int, [c_int, c_int, c_int]),
     "mega_relation_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mega_relation_attention": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                         c_int, c_void_p, c_size_t, c_void_p]),
     "mega_relation_attention_batched": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
-    "mega_position_logits_tiled_batched": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mega_position_logits_tiled_dt": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     "mega_position_logits_tiled_batched_dt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mega_relation_attention_tiled_pos_dt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
@@ -77,19 +68,11 @@ SIGNATURES = {
     "mega_fgfa_warp_aggregate": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "mega_fgfa_warp_aggregate_ring": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "mega_copy_segments": (c_int, [c_void_p, c_int, c_void_p]),
-    "mega_copy_cast_segments": (c_int, [c_void_p, c_int, c_void_p]),
-    "mega_bottleneck64_fwd": (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_void_p]),
-    "mega_bottleneck64_ds_fwd": (c_int, [c_void_p] * 14 + [c_int] * 3 + [c_void_p]),
     "mega_bottleneck64_fwd_dt": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
     "mega_bottleneck64_ds_fwd_dt": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_void_p]),
     "mega_cast_f32_to_half": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "mega_copy_cast_segments_dt": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "mega_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mega_split_f32_to_bf16x3": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "mega_split_f32_to_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "mega_roi_align_fwd_planes": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_int] * 3 + [c_void_p]),
-    "mega_conv2d_nhwc_sp": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                    c_int] + [c_int] * 11 + [c_void_p, c_size_t, c_void_p]),
     "mega_split_f32_to_planes_dt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mega_roi_align_fwd_planes_dt": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_int] * 4 + [c_void_p]),
     "mega_conv2d_nhwc_sp_dt": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,

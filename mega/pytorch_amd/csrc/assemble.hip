@@ -159,7 +159,7 @@ extern "C" int mega_split_f32_to_bf16x3(const float* src, void* dst, int rows, i
 }
 
 // dst[r][0:K] = hi, dst[r][K:2K] = lo of src[r][0:K]: the split-precision PLANES form of an f32 activation (hi = bf16(x),
-// lo = bf16(x - hi)) that mega_conv2d_nhwc_sp reads as its input / residual and writes as its output.
+// lo = bf16(x - hi)) that mega_conv2d_nhwc_sp_dt reads as its input / residual and writes as its output.
 extern "C" int mega_split_f32_to_planes_dt(const float* src, void* dst, int rows, int K, int dtype, void* stream) {
   mega_clear_error();
   if (rows == 0) return MEGA_OK;
@@ -174,10 +174,6 @@ extern "C" int mega_split_f32_to_planes_dt(const float* src, void* dst, int rows
   else
     hipLaunchKernelGGL((split3_f32_bf16_kernel<2, bf16_t>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, rows, K / 8);
   return mega_check_launch();
-}
-
-extern "C" int mega_split_f32_to_planes(const float* src, void* dst, int rows, int K, void* stream) {
-  return mega_split_f32_to_planes_dt(src, dst, rows, K, MEGA_BF16, stream);
 }
 
 // dst[i] = bf16(src[i]) for n contiguous elements (both 16-byte aligned).  The aggregation head keeps its activation
@@ -197,10 +193,6 @@ extern "C" int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int 
   else
     hipLaunchKernelGGL(cast_f32_bf16_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n8, n);
   return mega_check_launch();
-}
-
-extern "C" int mega_cast_f32_to_bf16(const float* src, void* dst, size_t n, void* stream) {
-  return mega_cast_f32_to_half(src, dst, n, MEGA_BF16, stream);
 }
 
 struct MegaCopySegC {
@@ -253,10 +245,6 @@ extern "C" int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, vo
   }
   flush();
   return mega_check_launch();
-}
-
-extern "C" int mega_copy_cast_segments(const void* segs, int n, void* stream) {
-  return mega_copy_cast_segments_dt(segs, n, MEGA_BF16, stream);
 }
 
 // segs[n]: copy rows x row_bytes bytes from src (+ r * src_stride) to dst (+ r * dst_stride).  Segments must not

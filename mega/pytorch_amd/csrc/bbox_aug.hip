@@ -1,6 +1,6 @@
 // Test-time box augmentation: the merge of engine/bbox_aug.py:53-66 (im_detect_bbox_aug) on device.
 //
-// Input: the candidates of K views of F frames, as mega_postprocess_candidates writes them for every view --
+// Input: the candidates of K views of F frames, as mega_postprocess_candidates_batched writes them for every view --
 // boxes [K][F][NC-1][R][4] in the view's own image (decoded, clipped), scores [K][F][NC-1][R] (-1 at or below the
 // score threshold).  Per (frame, class), the K*R rows are taken in (view, proposal row) order -- the reference's
 // concatenation order -- and each row's box is mapped into view 0's image as it is loaded:

@@ -623,12 +623,6 @@ extern "C" int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const flo
   return mega_check_launch();
 }
 
-extern "C" int mega_bottleneck64_fwd(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
-                                     const float* s2, const float* b2, const void* w3, const float* s3, const float* b3,
-                                     void* out, int N, int H, int W, void* stream) {
-  return mega_bottleneck64_fwd_dt(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, out, N, H, W, MEGA_BF16, stream);
-}
-
 // The stage's first block with the 1x1 downsample branch: x NHWC bf16 [N][H][W][64] -> out [N][H][W][256],
 //   out = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + bnd(convd(x))).  Bit-identical to the four launches it replaces.
 extern "C" int mega_bottleneck64_ds_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
@@ -672,9 +666,3 @@ extern "C" int mega_bottleneck64_ds_fwd_dt(const void* x, const void* w1, const 
   return mega_check_launch();
 }
 
-extern "C" int mega_bottleneck64_ds_fwd(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
-                                        const float* s2, const float* b2, const void* w3, const float* s3, const float* b3,
-                                        const void* wd, const float* sd, const float* bd, void* out, int N, int H, int W,
-                                        void* stream) {
-  return mega_bottleneck64_ds_fwd_dt(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, bd, out, N, H, W, MEGA_BF16, stream);
-}

@@ -566,7 +566,7 @@ __global__ void post_prepare_kernel(const float* __restrict__ logits, const floa
   cboxes += (size_t)b * (NC - 1) * R;
   cscores += (size_t)b * (NC - 1) * R;
   if (flags) flags += (size_t)b * (NC - 1) * R;     // the kept flags of this call start from zero (written here, not by a
-                                                    // memset node); null: candidates only (mega_postprocess_candidates)
+                                                    // memset node); null: candidates only (mega_postprocess_candidates_batched)
   if (probs_out) probs_out += (size_t)b * R * NC;
   const int nprop = nprop_ptr ? min(nprop_ptr[b], R) : R;
   const bool live = r < nprop;
@@ -891,15 +891,6 @@ extern "C" int mega_rpn_select_idx(const float* rpn_out, const float* cell_ancho
   return mega_check_launch();
 }
 
-extern "C" int mega_rpn_select(const float* rpn_out, const float* cell_anchors, int B, int Hf, int Wf, int A, int ldc,
-                               int anchor_stride, int pre_nms_top_n, int post_nms_top_n, float nms_thresh,
-                               int strict_gt, float min_size, float im_w, float im_h, float* proposals,
-                               float* prop_scores, int* prop_cnt, void* ws, size_t ws_bytes, void* stream) {
-  return mega_rpn_select_idx(rpn_out, cell_anchors, B, Hf, Wf, A, ldc, anchor_stride, pre_nms_top_n, post_nms_top_n,
-                             nms_thresh, strict_gt, min_size, im_w, im_h, proposals, prop_scores, prop_cnt, nullptr, ws,
-                             ws_bytes, stream);
-}
-
 // Box-head post-processor for one image (roi_heads/box_head/inference.py:45-149).
 //   logits [R][NC], deltas [R][NC*4], props [R][4], nprop (device int, may be null -> R)
 //   outputs (capacity (NC-1)*R rows): out_boxes [.][4], out_scores, out_labels (i64), out_cnt (device int)
@@ -967,13 +958,6 @@ extern "C" int mega_postprocess_candidates_batched(const float* logits, const fl
                      (const float4*)props, nprop, R, NC, wx, wy, ww, wh, logf(1000.f / 16.f), im_w, im_h, score_thresh,
                      (float4*)cboxes, cscores, (float*)nullptr, (unsigned char*)nullptr);
   return mega_check_launch();
-}
-
-extern "C" int mega_postprocess_candidates(const float* logits, const float* deltas, const float* props, const int* nprop,
-                                           int R, int NC, float wx, float wy, float ww, float wh, float im_w, float im_h,
-                                           float score_thresh, float* cboxes, float* cscores, void* stream) {
-  return mega_postprocess_candidates_batched(logits, deltas, props, nprop, 1, R, NC, wx, wy, ww, wh, im_w, im_h,
-                                             score_thresh, cboxes, cscores, stream);
 }
 
 // Library-internal (common.h): the lazy NMS and P4 of the post-processor, for the box-augmentation merge (bbox_aug.hip).

@@ -176,8 +176,7 @@ __global__ __launch_bounds__(C64_NT, 2) void conv3x3_c64_kernel(ConvParams p, in
 // 1 when mega_conv64_launch takes this layer (bf16 3x3 / stride 1 / pad 1 / dilation 1, 64 -> 64 channels, bf16 out,
 // no residual, no split-K, enough tiles to fill the chip)
 int mega_conv64_supports(const ConvParams& p, int out_f32) {
-  static const bool off = getenv("MEGA_CONV64") != nullptr && getenv("MEGA_CONV64")[0] == '0';
-  if (off || out_f32) return 0;
+  if (out_f32) return 0;
   if (!(p.R == 3 && p.S == 3 && p.Cin == 64 && p.Cout == 64 && p.stride == 1 && p.pad == 1 && p.dil == 1)) return 0;
   if (p.res || p.ksplit != 1 || p.ldo != 64) return 0;
   const long tiles = (long)p.N * cdiv(p.H, C64_T) * cdiv(p.W, C64_T);

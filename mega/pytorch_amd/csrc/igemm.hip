@@ -453,170 +453,115 @@ int launch_finalize(const ConvParams& p, hipStream_t st) {
   return mega_check_launch();
 }
 
-// Tile choice, from measurements on MI355X (tools/bench_kernels.py --tiles ..., profiles/README.md): 128x128 at two
-// blocks per CU wins every shape of the path except the very long-K 1024->1024 3x3 RPN conv, where 256x256 at one
-// block per CU is ~10 % faster; 256x128 never wins (one block of 4 waves per CU hides too little latency).  Small
-// grids shrink the tile to keep >= ~1.5 rounds of blocks over the 256 CUs.
 // Split-K depends on K ALONE (never on M): a row of a layer is then summed in the same order whatever batch it is part
 // of, which keeps results batch-invariant (tests: reference call convention == batched engine, bit for bit).  Only
 // the box head's first FC (K = 100352 on R-101) qualifies: three ranges of 523 K-tiles (240 blocks on 256 CUs at 3750 rows).
 inline int choose_ksplit(int K) { return K >= 32768 ? 3 : 1; }   // (3 x 20 x 4 = 240 blocks of 192 rows for the first FC of a 20-frame batch)
 
-// kind 0: igemm_kernel<.., bm, bn> (this file);  kind 8: igemm8_kernel (igemm8.hip: LDS-DMA, 8 waves, bm x 256), bf16 only.
-// MEGA_IGEMM_TILE forces a choice (experiments / tests): "128x64" or "8:256" / "8:192".
-inline void choose_tile(int M, int Cout, int K, int z, bool bf16, int& kind, int& bm, int& bn) {
-  kind = 0;
+// igemm8 runs one block per CU: the row count (256 or 192) that wastes the fewest CU-rounds (cost ~ rounds x rows; 192 rows
+// are ~12 % slower per row).  *half_round: the launch has at least half a round of such tiles (128) -- below that the
+// register-staged tiles at two blocks per CU win.
+inline int igemm8_rows(int M, int Cout, int z, bool* half_round = nullptr) {
+  const long t256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z, t192 = (long)cdiv(M, 192) * cdiv(Cout, 256) * z;
+  const long c256 = cdiv((int)t256, 256) * 256L * 8, c192 = cdiv((int)t192, 256) * 192L * 9;
+  if (half_round) *half_round = t256 >= 128 || t192 >= 128;
+  return c192 < c256 ? 192 : 256;
+}
+
+// The geometric part of ConvParams (shape, Ho / Wo, GEMM shape, operand sizes against the kernels' 32-bit byte offsets;
+// ksplit = 1), shared by every entry point.  ldi: pixel stride of `in` in elements.  MEGA_OK or MEGA_ERR_ARG.
+inline int conv_geometry(ConvParams& p, int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,
+                         int ldi, size_t esz, size_t byte_limit) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 || dil <= 0 || pad < 0) return MEGA_ERR_ARG;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.dil = dil;
+  p.Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
+  p.Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
+  if (p.Ho <= 0 || p.Wo <= 0) return MEGA_ERR_ARG;
+  p.M = N * p.Ho * p.Wo;
+  p.K = R * S * Cin;
+  const size_t ib = (size_t)N * H * W * ldi * esz, wb = (size_t)Cout * p.K * esz;
+  if (ib >= byte_limit || wb >= byte_limit) return MEGA_ERR_ARG;
+  p.in_bytes = (unsigned)ib;
+  p.w_bytes = (unsigned)wb;
+  p.ksplit = 1;
+  p.partial = nullptr;
+  return MEGA_OK;
+}
+
+// Which kernel a launch runs on.  `kernel` is also the kind mega_conv2d_nhwc_plan_ex reports.
+enum { KERNEL_TILE = 0,       // igemm_kernel<.., bm, bn> (this file): register-staged tiles
+       KERNEL_CONV64 = 6,     // conv64.hip: layer1's 3x3 64 -> 64 conv, persistent
+       KERNEL_IGEMM8S = 7,    // igemm8.hip (LDS-DMA, 8 waves, bm x 256), streaming class (1x1, K <= 512, no split-K)
+       KERNEL_IGEMM8 = 8 };   // igemm8.hip, matrix class
+struct ConvPlan { int kernel, bm, bn; };
+
+// THE dispatch rule: conv2d_impl launches what this returns and mega_conv2d_nhwc_plan_ex reports it.  half: 16-bit
+// operands (bf16 / f16; false: f32).  p.ksplit must be set: the launch passes its own count; the report has no ksplit argument
+// and assumes choose_ksplit(K), which is what mega_conv2d_nhwc_ws launches with (a mega_conv2d_nhwc_ks launch with another
+// count can land elsewhere: ksplit scales the tile counts below).
+// MEGA_IGEMM_TILE (experiments / tests; read on every call) forces "BMxBN" register-staged tiles or igemm8 "8:256" / "8:192";
+// set to anything, it keeps layer1's 3x3 conv off conv64: that is how the bit-equality tests compare the kernels.
+// Measured on MI355X (tools/bench_kernels.py --tiles ..., profiles/README.md): igemm8 wins from half a round of its tiles on
+// (K = 64, one K-tile, included: layer1's 64 -> 256 convs, 0.164 -> 0.151 ms per 20 frames); below that 128x128 at two
+// blocks per CU wins every shape except the very long-K 1024 -> 1024 3x3 RPN conv, where 256x256 at one block per CU is
+// ~10 % faster; 256x128 never wins (one block of 4 waves per CU hides too little latency).  Small grids shrink the tile to
+// keep >= ~1.5 rounds of blocks over the 256 CUs.
+inline ConvPlan plan_conv(const ConvParams& p, bool half, bool f32_out) {
   const char* force = getenv("MEGA_IGEMM_TILE");
-  if (force && sscanf(force, "8:%d", &bm) == 1) { kind = 8; bn = 256; return; }
-  if (force && sscanf(force, "4:%d", &bm) == 1) { kind = 4; bn = 256; return; }
-  if (force && sscanf(force, "2:%d", &bm) == 1) { kind = 2; bm = 128; bn = 256; return; }
-  if (force && sscanf(force, "s:%d", &bm) == 1) { kind = 1; bm = 32; bn = 256; return; }
-  if (force && sscanf(force, "%dx%d", &bm, &bn) == 2) return;
-  const long b256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z;
-  const long b128 = (long)cdiv(M, 128) * cdiv(Cout, 128) * z;
-  const long b12864 = (long)cdiv(M, 128) * cdiv(Cout, 64) * z;
-  static const int use8 = getenv("MEGA_IGEMM8") ? atoi(getenv("MEGA_IGEMM8")) : 1;
-  // K = 64 (one K-tile: layer1's 64 -> 256 convs) runs on igemm8 too, bit-identically and 8 % faster (0.164 -> 0.151 ms
-  // per 20 frames each).  Rounds 1-2 kept them on the 128x128 tiles so that the igemm8 symbols of a profile stayed the
-  // matrix-core-bound layers; since round 3 the streaming layers have their own igemm8 symbol (CLS = 1), so they go over by
-  // default (MEGA_IGEMM8_MIN_KTILES=2 restores the old dispatch).
-  static const int min_kt = getenv("MEGA_IGEMM8_MIN_KTILES") ? atoi(getenv("MEGA_IGEMM8_MIN_KTILES")) : 1;
-  if (bf16 && use8 && Cout >= 256 && K >= 64 * min_kt) {
-    // igemm8 runs one block per CU: pick the row count that wastes the fewest CU-rounds (cost ~ rounds x rows)
-    const long t256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z, t192 = (long)cdiv(M, 192) * cdiv(Cout, 256) * z;
-    const long c256 = cdiv((int)t256, 256) * 256L * 8, c192 = cdiv((int)t192, 256) * 192L * 9;   // 192: ~12 % slower per row
-    if (t256 >= 128 || t192 >= 128) {
-      kind = 8; bn = 256; bm = c192 < c256 ? 192 : 256;
-      return;
-    }
+  if (!force && half && !f32_out && mega_conv64_supports(p, 0)) return {KERNEL_CONV64, 256, 64};
+  const int M = p.M, Cout = p.Cout, K = p.K, z = p.ksplit;
+  int bm = 0, bn = 0;
+  bool want8 = false;
+  if (force && sscanf(force, "8:%d", &bm) == 1) want8 = true;
+  else if (force && sscanf(force, "%dx%d", &bm, &bn) == 2) {      // (a size that is not instantiated runs on 64x64)
+    for (const ConvPlan& t : {ConvPlan{0, 256, 256}, {0, 256, 128}, {0, 128, 128}, {0, 128, 64}})
+      if (bm == t.bm && bn == t.bn) return t;
+    return {KERNEL_TILE, 64, 64};
+  } else if (half && Cout >= 256 && K >= 64) bm = igemm8_rows(M, Cout, z, &want8);
+  if (want8) {
+    if (!(half && mega_igemm8_supports(p))) return {KERNEL_TILE, 128, 128};     // a shape igemm8 cannot take
+    return {mega_igemm8_streaming(p.R * p.S, K) && z == 1 ? KERNEL_IGEMM8S : KERNEL_IGEMM8, bm, 256};
   }
-  if (K >= 8192 && Cout >= 1024 && b256 >= 700) { bm = 256; bn = 256; }
-  else if (Cout > 64 && b128 >= 384) { bm = 128; bn = 128; }
-  else if (b12864 >= 384) { bm = 128; bn = 64; }
-  else { bm = 64; bn = 64; }
+  const long b256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z, b128 = (long)cdiv(M, 128) * cdiv(Cout, 128) * z;
+  const long b12864 = (long)cdiv(M, 128) * cdiv(Cout, 64) * z;
+  if (K >= 8192 && Cout >= 1024 && b256 >= 700) return {KERNEL_TILE, 256, 256};
+  if (Cout > 64 && b128 >= 384) return {KERNEL_TILE, 128, 128};
+  if (b12864 >= 384) return {KERNEL_TILE, 128, 64};
+  return {KERNEL_TILE, 64, 64};
 }
 
 template <typename T, typename OT>
-int dispatch_tile(const ConvParams& p, hipStream_t st) {
-  int kind = 0, bm = 0, bn = 0, rc;
-  constexpr bool is_bf16 = sizeof(T) == 2;                     // (a 16-bit operand type: bf16 or f16)
-  choose_tile(p.M, p.Cout, p.K, p.ksplit, is_bf16, kind, bm, bn);
-  if (kind == 8 && !(is_bf16 && mega_igemm8_supports(p))) {    // forced onto a shape it cannot take
-    kind = 0; bm = 128; bn = 128;
+int launch_plan(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+  int rc = MEGA_ERR_ARG;
+  if constexpr (sizeof(T) == 2) {      // (plan_conv sends 16-bit operands only to these)
+    if (pl.kernel == KERNEL_CONV64) return mega_conv64_launch(p, Half16<T>::CODE, st);
+    if (pl.kernel == KERNEL_IGEMM8 || pl.kernel == KERNEL_IGEMM8S) rc = mega_igemm8_launch(p, pl.bm, sizeof(OT) == 4, Half16<T>::CODE, st);
   }
-  if constexpr (is_bf16 && sizeof(OT) == 2) {
-    // stream1x1 (persistent, wave-owned 32 x 256 tiles, weights resident in LDS): layer3's / layer2's conv3.  Measured SLOWER than
-    // the tile kernels (0.173 against 0.118 ms on layer3's conv3: its row-strided 8-byte epilogue accesses and 32-byte operand
-    // pieces bind the CU's address path, profiles/r06_streaming_class_experiments.txt) -- opt-in with MEGA_STREAM1X1=1;
-    // MEGA_IGEMM_TILE=s:32 forces it (shapes it does not take fall through)
-    static const int use_s = getenv("MEGA_STREAM1X1") ? atoi(getenv("MEGA_STREAM1X1")) : 0;
-    if ((kind == 1 || (kind == 8 && use_s && !getenv("MEGA_IGEMM_TILE"))) && mega_stream1x1_supports(p, 0))
-      return mega_stream1x1_launch(p, Half16<T>::CODE, st);
+  if (pl.kernel == KERNEL_TILE) {
+    if (pl.bm == 256 && pl.bn == 256) rc = launch<T, OT, 256, 256>(p, st);
+    else if (pl.bm == 256 && pl.bn == 128) rc = launch<T, OT, 256, 128>(p, st);
+    else if (pl.bm == 128 && pl.bn == 128) rc = launch<T, OT, 128, 128>(p, st);
+    else if (pl.bm == 128 && pl.bn == 64) rc = launch<T, OT, 128, 64>(p, st);
+    else rc = launch<T, OT, 64, 64>(p, st);
   }
-  if (kind == 1) { kind = is_bf16 && mega_igemm8_supports(p) ? 8 : 0; bm = kind ? 256 : 128; bn = kind ? 256 : 128; }
-  if constexpr (is_bf16) {
-    // igemm2 (4 waves, 128 x 256 tile, K-tile 32, TWO blocks per CU).  Measured (profiles/r06_streaming_class_experiments.txt):
-    // +6-10 % on layer2's conv3 (K = 128), +-1 % on layer3's conv3, slower on everything with a long K loop -- opt-in:
-    // MEGA_IGEMM2=1 the streaming class (1x1, K <= 512) with K <= 128, =2 the whole streaming class, =3 every igemm8 launch it
-    // supports; MEGA_IGEMM_TILE=2:128 forces it.  Default 0: the product path stays on igemm8.
-    static const int use2 = getenv("MEGA_IGEMM2") ? atoi(getenv("MEGA_IGEMM2")) : 0;
-    {
-      const bool streaming2 = mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1;
-      if (kind == 2 || (kind == 8 && use2 && (use2 > 2 || (streaming2 && (use2 > 1 || p.K <= 128))) && !getenv("MEGA_IGEMM_TILE"))) {
-        if (mega_igemm2_supports(p, sizeof(OT) == 4)) return mega_igemm2_launch(p, sizeof(OT) == 4, Half16<T>::CODE, st);
-        if (kind == 2) kind = mega_igemm8_supports(p) ? 8 : 0;
-        if (kind == 0) { bm = 128; bn = 128; } else if (bm != 192) bm = 256;
-      }
-    }
-    // igemm4 (4 waves x 512 registers, 128 x 128 outputs per wave): the matrix-core-bound launch class -- 3x3 convs and every
-    // layer with more than 8 K-tiles -- when its epilogue serves the shape; MEGA_IGEMM4=0 keeps everything on igemm8,
-    // MEGA_IGEMM4=2 also sends the streaming class (1x1, K <= 512) over; MEGA_IGEMM_TILE=4:256 / 4:192 forces it
-    static const int use4 = getenv("MEGA_IGEMM4") ? atoi(getenv("MEGA_IGEMM4")) : 0;
-    const bool streaming = mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1;
-    if (kind == 4 || (kind == 8 && use4 && (use4 > 1 || !streaming) && !getenv("MEGA_IGEMM_TILE"))) {
-      if (mega_igemm4_supports(p, sizeof(OT) == 4)) {
-        rc = mega_igemm4_launch(p, bm == 192 ? 192 : 256, sizeof(OT) == 4, Half16<T>::CODE, st);
-        if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<T, OT>(p, st);
-        return rc;
-      }
-      if (kind == 4) kind = mega_igemm8_supports(p) ? 8 : 0;
-      if (kind == 0) { bm = 128; bn = 128; }
-    }
-    if (kind == 8) {
-      rc = mega_igemm8_launch(p, bm, sizeof(OT) == 4, Half16<T>::CODE, st);
-      if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<T, OT>(p, st);
-      return rc;
-    }
-  }
-  if (kind == 8 || kind == 4 || kind == 2) rc = MEGA_ERR_ARG;
-  else if (bm == 256 && bn == 256) rc = launch<T, OT, 256, 256>(p, st);
-  else if (bm == 256 && bn == 128) rc = launch<T, OT, 256, 128>(p, st);
-  else if (bm == 128 && bn == 128) rc = launch<T, OT, 128, 128>(p, st);
-  else if (bm == 128 && bn == 64) rc = launch<T, OT, 128, 64>(p, st);
-  else rc = launch<T, OT, 64, 64>(p, st);
   if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<T, OT>(p, st);
   return rc;
 }
 
 }  // namespace
 
-// kind * 1e6 + bm * 1e3 + bn of the kernel a launch is dispatched to.  kinds: 0 igemm_kernel (this file), 8 igemm8 matrix
-// class, 7 igemm8 streaming class (1x1, K <= 512), 6 conv64.hip.  The shape-complete form asks the SAME predicates the
-// launch path uses (mega_conv64_supports, mega_igemm8_supports): profiler families, the roofline attribution and
-// mega_conv2d_nhwc_tile name the kernel that really runs (the (M, Cout, K) form guessed conv64 from K = 576).
-static int plan_of(const ConvParams& p, bool bf16_in, bool f32_out) {
-  if (bf16_in && !f32_out && !getenv("MEGA_IGEMM_TILE") && mega_conv64_supports(p, 0)) return 6 * 1000000 + 256 * 1000 + 64;
-  int kind = 0, bm = 0, bn = 0;
-  choose_tile(p.M, p.Cout, p.K, choose_ksplit(p.K), bf16_in, kind, bm, bn);
-  if (kind == 1 || kind == 8) {      // stream1x1 first, then igemm2 (the launch path's own rule: dispatch_tile)
-    static const int use_s = getenv("MEGA_STREAM1X1") ? atoi(getenv("MEGA_STREAM1X1")) : 0;
-    ConvParams q = p;
-    q.ksplit = choose_ksplit(p.K);
-    if (bf16_in && !f32_out && (kind == 1 || (use_s && !getenv("MEGA_IGEMM_TILE"))) && mega_stream1x1_supports(q, 0)) return 1 * 1000000 + 32 * 1000 + 256;
-    if (kind == 1) { kind = 8; bm = 256; bn = 256; }
-  }
-  if (kind == 2 || kind == 8) {      // igemm2 first (the launch path's own rule: dispatch_tile)
-    static const int use2 = getenv("MEGA_IGEMM2") ? atoi(getenv("MEGA_IGEMM2")) : 0;
-    ConvParams q = p;
-    q.ksplit = choose_ksplit(p.K);
-    const bool streaming2 = mega_igemm8_streaming(p.R * p.S, p.K) && q.ksplit == 1;
-    if (bf16_in && (kind == 2 || (use2 && (use2 > 2 || (streaming2 && (use2 > 1 || p.K <= 128))) && !getenv("MEGA_IGEMM_TILE"))) && mega_igemm2_supports(q, f32_out))
-      return 2 * 1000000 + 128 * 1000 + 256;
-    if (kind == 2) { kind = 8; bm = 256; }
-  }
-  if ((kind == 8 || kind == 4) && !(bf16_in && mega_igemm8_supports(p))) { kind = 0; bm = 128; bn = 128; }
-  if (kind == 8 || kind == 4) {      // (the launch path's own rule: dispatch_tile)
-    static const int use4 = getenv("MEGA_IGEMM4") ? atoi(getenv("MEGA_IGEMM4")) : 0;
-    const bool streaming = mega_igemm8_streaming(p.R * p.S, p.K) && choose_ksplit(p.K) == 1;
-    ConvParams q = p;
-    q.ksplit = choose_ksplit(p.K);
-    const bool take4 = (kind == 4 || (use4 && (use4 > 1 || !streaming) && !getenv("MEGA_IGEMM_TILE"))) && mega_igemm4_supports(q, f32_out || q.ksplit > 1);
-    if (take4) kind = streaming ? 3 : 4;     // 4: igemm4 matrix class, 3: igemm4 streaming class
-    else kind = streaming ? 7 : 8;
-    if (bm != 192) bm = 256;
-  }
-  return kind * 1000000 + bm * 1000 + bn;
-}
-
+// kind * 1e6 + bm * 1e3 + bn of the kernel a launch is dispatched to (kinds: ConvPlan), from plan_conv itself: profiler
+// families, the roofline attribution and mega_conv2d_nhwc_tile name the kernel that really runs.  -1: not a launchable shape.
 extern "C" int mega_conv2d_nhwc_plan_ex(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,
                                         int ldo, int has_residual, int in_dtype, int out_dtype) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 || dil <= 0 || pad < 0) return -1;
   ConvParams p = {};
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.dil = dil;
-  p.Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
-  p.Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
-  if (p.Ho <= 0 || p.Wo <= 0) return -1;
-  p.M = N * p.Ho * p.Wo;
-  p.K = R * S * Cin;
+  if (conv_geometry(p, N, H, W, Cin, Cout, R, S, stride, pad, dil, Cin, in_dtype == MEGA_F32 ? 4 : 2, 0xFFFFFFF0ull) != MEGA_OK) return -1;
   p.ldo = ldo > 0 ? ldo : Cout;
   p.ldr = p.ldo;
   p.res = has_residual ? (const void*)&p : nullptr;      // (only tested against null)
-  p.ksplit = 1;
-  const size_t esz = in_dtype == MEGA_F32 ? 4 : 2;
-  const size_t ib = (size_t)N * H * W * Cin * esz, wb = (size_t)Cout * p.K * esz;
-  p.in_bytes = ib >= 0xFFFFFFF0ull ? 0xFFFFFFF0u : (unsigned)ib;
-  p.w_bytes = wb >= 0xFFFFFFF0ull ? 0xFFFFFFF0u : (unsigned)wb;
-  return plan_of(p, in_dtype != MEGA_F32, out_dtype == MEGA_F32);
+  p.ksplit = choose_ksplit(p.K);
+  const ConvPlan pl = plan_conv(p, in_dtype != MEGA_F32, out_dtype == MEGA_F32);
+  return pl.kernel * 1000000 + pl.bm * 1000 + pl.bn;
 }
 
 // the (M, Cout, K) form: a 1x1 layer / linear of that GEMM shape (bf16 or f32 output does not change the tile)
@@ -674,24 +619,15 @@ static int conv2d_impl(const void* in, const void* w, const float* scale, const 
                        int R, int S, int stride, int pad, int dil, int relu, int ldo, int ldr,
                        int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream) {
   mega_clear_error();
-  if (!in || !w || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
-      dil <= 0 || pad < 0)
-    return MEGA_ERR_ARG;
+  if (!in || !w || !out) return MEGA_ERR_ARG;
+  if (in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
+  if (Cin % (in_dtype == MEGA_F32 ? 32 : 64) != 0 || (out_dtype != in_dtype && out_dtype != MEGA_F32)) return MEGA_ERR_ARG;
   ConvParams p = {};
+  if (conv_geometry(p, N, H, W, Cin, Cout, R, S, stride, pad, dil, Cin, in_dtype == MEGA_F32 ? 4 : 2, 0xFFFFFFF0ull) != MEGA_OK) return MEGA_ERR_ARG;
   p.in = in; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.out = out;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.R = R; p.S = S;
-  p.stride = stride; p.pad = pad; p.dil = dil;
-  p.Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
-  p.Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
-  if (p.Ho <= 0 || p.Wo <= 0) return MEGA_ERR_ARG;
-  p.M = N * p.Ho * p.Wo;
-  p.K = R * S * Cin;
   p.ldo = ldo > 0 ? ldo : Cout;
   p.ldr = ldr > 0 ? ldr : Cout;
   p.relu = relu;
-  p.ksplit = 1;
-  p.partial = nullptr;
-  if (ksplit > 0 && in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (ksplit > 0 || ws) {   // with a workspace the K range of long-K layers is split (mega_conv2d_nhwc_workspace_bytes)
     const int z = ksplit > 0 ? clamp_ksplit(p.K, in_dtype, ksplit) : choose_ksplit(p.K);
     if (z > 1) {
@@ -701,36 +637,12 @@ static int conv2d_impl(const void* in, const void* w, const float* scale, const 
       p.partial = (float*)ws;
     }
   }
-  {
-    if (in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
-    const size_t esz = in_dtype == MEGA_F32 ? 4 : 2;
-    const size_t ib = (size_t)N * H * W * Cin * esz, wb = (size_t)Cout * p.K * esz;
-    if (ib >= 0xFFFFFFF0ull || wb >= 0xFFFFFFF0ull) return MEGA_ERR_ARG;  // 32-bit buffer offsets
-    p.in_bytes = (unsigned)ib;
-    p.w_bytes = (unsigned)wb;
-  }
   hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == MEGA_BF16) {
-    if (Cin % 64 != 0) return MEGA_ERR_ARG;
-    // layer1's 3x3 64 -> 64 conv: its own persistent streaming kernel (a forced tile, MEGA_IGEMM_TILE, keeps it on the
-    // generic path: that is how the bit-equality test compares the two)
-    if (out_dtype == MEGA_BF16 && !getenv("MEGA_IGEMM_TILE") && mega_conv64_supports(p, 0)) return mega_conv64_launch(p, MEGA_BF16, st);
-    if (out_dtype == MEGA_BF16) return dispatch_tile<bf16_t, bf16_t>(p, st);
-    if (out_dtype == MEGA_F32) return dispatch_tile<bf16_t, float>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (in_dtype == MEGA_F16) {      // IEEE half operands: the same kernels instantiated for f16_t (same tiles, same K order)
-    if (Cin % 64 != 0) return MEGA_ERR_ARG;
-    if (out_dtype == MEGA_F16 && !getenv("MEGA_IGEMM_TILE") && mega_conv64_supports(p, 0)) return mega_conv64_launch(p, MEGA_F16, st);
-    if (out_dtype == MEGA_F16) return dispatch_tile<f16_t, f16_t>(p, st);
-    if (out_dtype == MEGA_F32) return dispatch_tile<f16_t, float>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (in_dtype == MEGA_F32) {
-    if (Cin % 32 != 0 || out_dtype != MEGA_F32) return MEGA_ERR_ARG;
-    return dispatch_tile<float, float>(p, st);
-  }
-  return MEGA_ERR_ARG;
+  const bool f32_out = out_dtype == MEGA_F32;
+  const ConvPlan pl = plan_conv(p, in_dtype != MEGA_F32, f32_out);
+  if (in_dtype == MEGA_BF16) return f32_out ? launch_plan<bf16_t, float>(p, pl, st) : launch_plan<bf16_t, bf16_t>(p, pl, st);
+  if (in_dtype == MEGA_F16) return f32_out ? launch_plan<f16_t, float>(p, pl, st) : launch_plan<f16_t, f16_t>(p, pl, st);
+  return launch_plan<float, float>(p, pl, st);      // (IEEE half / bf16: the same kernels instantiated per operand type)
 }
 
 extern "C" int mega_conv2d_nhwc(const void* in, const void* w, const float* scale, const float* bias,
@@ -786,14 +698,15 @@ extern "C" int mega_conv2d_nhwc_subpixel(const void* in, const void* w4, const f
   const long b128 = (long)cdiv(p.M, 128) * cdiv(p.Cout, 128) * p.ksplit, b12864 = (long)cdiv(p.M, 128) * cdiv(p.Cout, 64) * p.ksplit;
   // (the sub-pixel read-out is the tiles' vector path: whole tiles of columns only)
   if (p.Cout % 64 != 0) return MEGA_ERR_ARG;
-  // large launches on the LDS-DMA tiles (igemm8.hip, ABL = 6 = the same read-out there): choose_tile's rule -- Cout a multiple of
-  // 256 and at least half a round of tiles; same K order, same MFMA: the same bits as the register-staged tiles
+  // large launches on the LDS-DMA tiles (igemm8.hip, ABL = 6 = the same read-out there): plan_conv's rule for whole tiles of
+  // columns -- Cout a multiple of 256 and at least half a round of tiles; same K order, same MFMA: the same bits as the
+  // register-staged tiles
   if (dtype != MEGA_F32 && p.ksplit == 1 && p.Cout % 256 == 0 && !getenv("MEGA_IGEMM_TILE") && mega_igemm8_supports(p)) {
-    const long t256 = (long)cdiv(p.M, 256) * (p.Cout / 256), t192 = (long)cdiv(p.M, 192) * (p.Cout / 256);
-    const long c256 = cdiv((int)t256, 256) * 256L * 8, c192 = cdiv((int)t192, 256) * 192L * 9;
-    if (t256 >= 128 || t192 >= 128) return mega_igemm8_launch(p, c192 < c256 ? 192 : 256, 0, dtype, st);
+    bool half_round;
+    const int rows = igemm8_rows(p.M, p.Cout, 1, &half_round);
+    if (half_round) return mega_igemm8_launch(p, rows, 0, dtype, st);
   }
-  const int tile = (b128 >= 384 && p.Cout % 128 == 0) ? 0 : (b12864 >= 384 ? 1 : 2);     // (choose_tile's rule for the register-staged tiles)
+  const int tile = (b128 >= 384 && p.Cout % 128 == 0) ? 0 : (b12864 >= 384 ? 1 : 2);     // (plan_conv's rule for the register-staged tiles)
   auto go = [&](auto tag) -> int {
     typedef decltype(tag) T;
     int rc = tile == 0 ? launch<T, T, 128, 128, true>(p, st) : (tile == 1 ? launch<T, T, 128, 64, true>(p, st) : launch<T, T, 64, 64, true>(p, st));
@@ -806,7 +719,7 @@ extern "C" int mega_conv2d_nhwc_subpixel(const void* in, const void* w4, const f
 }
 
 // Split-precision activation planes (igemm_params.h, igemm8.hip SP kernels).  An f32 activation x [N,H,W,C] lives in HBM as
-// bf16 [N,H,W,2C] = [hi | lo] (mega_split_f32_to_planes; ~2^-17 relative).  This entry point runs conv + FrozenBN (+ split
+// bf16 [N,H,W,2C] = [hi | lo] (mega_split_f32_to_planes_dt; ~2^-17 relative).  This entry point runs conv + FrozenBN (+ split
 // residual) + activation on such tensors with the bf16 matrix cores:
 //   in       bf16 [N,H,W,ldi]; the contraction runs over Cin channels per tap whose SOURCE channel is k < kwrap ? k : k - kwrap
 //            (kwrap = 0: no wrap).  Split precision ("bf16 x 3"): ldi = 2C, Cin = 3C, kwrap = 2C, w = [Wh | Wh | Wl] per tap
@@ -826,24 +739,14 @@ extern "C" int mega_conv2d_nhwc_sp_dt(const void* in, int ldi, int kwrap, const 
                                       void* ws, size_t ws_bytes, void* stream) {
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
-  if (!in || !w || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
-      dil <= 0 || pad < 0 || out_mode < 0 || out_mode > 2 || ldi <= 0 || kwrap < 0 || Cin % 64 != 0)
-    return MEGA_ERR_ARG;
+  if (!in || !w || !out || out_mode < 0 || out_mode > 2 || ldi <= 0 || kwrap < 0 || Cin % 64 != 0) return MEGA_ERR_ARG;
   ConvParams p = {};
+  if (conv_geometry(p, N, H, W, Cin, Cout, R, S, stride, pad, dil, ldi, 2, 0x7FF00000ull) != MEGA_OK) return MEGA_ERR_ARG;
   p.in = in; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.out = out;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.R = R; p.S = S;
-  p.stride = stride; p.pad = pad; p.dil = dil;
-  p.Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
-  p.Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
-  if (p.Ho <= 0 || p.Wo <= 0) return MEGA_ERR_ARG;
-  p.M = N * p.Ho * p.Wo;
-  p.K = R * S * Cin;
   p.sp = 1; p.ldi = ldi; p.kwrap = kwrap; p.split_out = out_mode == 1;
   p.ldo = ldo > 0 ? ldo : (out_mode == 1 ? 2 * Cout : Cout);
   p.ldr = ldr > 0 ? ldr : 2 * Cout;
   p.relu = relu;
-  p.ksplit = 1;
-  p.partial = nullptr;
   if (ws) {
     const int z = choose_ksplit(p.K);
     if (z > 1) {
@@ -852,25 +755,8 @@ extern "C" int mega_conv2d_nhwc_sp_dt(const void* in, int ldi, int kwrap, const 
       p.partial = (float*)ws;
     }
   }
-  {
-    const size_t ib = (size_t)N * H * W * ldi * 2, wb = (size_t)Cout * p.K * 2;
-    if (ib >= 0x7FF00000ull || wb >= 0x7FF00000ull) return MEGA_ERR_ARG;  // 32-bit buffer offsets
-    p.in_bytes = (unsigned)ib;
-    p.w_bytes = (unsigned)wb;
-  }
   hipStream_t st = (hipStream_t)stream;
-  // one block per CU: the row count that wastes the fewest CU-rounds (the rule of choose_tile)
-  const long t256 = (long)cdiv(p.M, 256) * cdiv(Cout, 256) * p.ksplit, t192 = (long)cdiv(p.M, 192) * cdiv(Cout, 256) * p.ksplit;
-  const long c256 = cdiv((int)t256, 256) * 256L * 8, c192 = cdiv((int)t192, 256) * 192L * 9;
-  int rc = mega_igemm8_launch(p, c192 < c256 ? 192 : 256, out_mode == 2, dtype, st);
+  int rc = mega_igemm8_launch(p, igemm8_rows(p.M, Cout, p.ksplit), out_mode == 2, dtype, st);   // (the SP kernels exist on igemm8 only)
   if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<bf16_t, float>(p, st);      // (no residual in split-K launches: type-free)
   return rc;
-}
-
-extern "C" int mega_conv2d_nhwc_sp(const void* in, int ldi, int kwrap, const void* w, const float* scale, const float* bias,
-                                   const void* residual, int ldr, void* out, int ldo, int out_mode, int N, int H, int W,
-                                   int Cin, int Cout, int R, int S, int stride, int pad, int dil, int relu, void* ws,
-                                   size_t ws_bytes, void* stream) {
-  return mega_conv2d_nhwc_sp_dt(in, ldi, kwrap, w, scale, bias, residual, ldr, out, ldo, out_mode, N, H, W, Cin, Cout, R, S, stride,
-                                pad, dil, relu, MEGA_BF16, ws, ws_bytes, stream);
 }

@@ -19,7 +19,7 @@ struct ConvParams {
   float* partial;    // [ksplit][M][Cout] f32 when ksplit > 1
   // ---- igemm8 only.  Split-precision ("hi | lo planes") activations, sp != 0 (igemm8.hip, SP kernels): an f32 activation
   //      x [M][C] is stored as bf16 [M][2C] = [hi | lo], hi = bf16(x), lo = bf16(x - hi)  (x = hi + lo to ~2^-17).
-  int sp;            // 1: the fields below apply (mega_conv2d_nhwc_sp); 0: plain tensors (every other entry point)
+  int sp;            // 1: the fields below apply (mega_conv2d_nhwc_sp_dt); 0: plain tensors (every other entry point)
   int ldi;           // pixel stride of `in` in elements (2C for a split input; Cin when the input is a plain tensor)
   int kwrap;         // contraction channel at which the SOURCE channel index wraps to 0 (0: never).  Cin = 3C, kwrap = 2C
                      // reads the planes as [hi | lo | hi]: against weights packed [Wh | Wh | Wl] per tap the K = 3C
@@ -41,17 +41,6 @@ int mega_igemm8_launch(const ConvParams& p, int bm, int out_f32, int half_dtype,
 int mega_igemm8_supports(const ConvParams& p);
 // 1 when a launch of `taps` = R * S kernel taps and GEMM depth K belongs to igemm8's streaming class (1x1, K <= 512)
 int mega_igemm8_streaming(int taps, int K);
-// igemm4.hip: the same tiles on 4 waves of 512 registers (128 x 128 outputs per wave), for the shapes its buffer-addressed
-// epilogue serves (mega_igemm4_supports) -- the matrix-core-bound launch class by default (choose_tile, igemm.hip)
-int mega_igemm4_supports(const ConvParams& p, int out_f32);
-int mega_igemm4_launch(const ConvParams& p, int bm, int out_f32, int half_dtype, hipStream_t st);
-// igemm2.hip: 128 x 256 tiles, K-tile 32, 4 waves, two blocks per CU -- the streaming launch class (1x1, K <= 512) by default
-int mega_igemm2_supports(const ConvParams& p, int out_f32);
-int mega_igemm2_launch(const ConvParams& p, int out_f32, int half_dtype, hipStream_t st);
-// stream1x1.hip: persistent 1x1 / stride-1 conv with K = 128 / 256 (layer3's / layer2's conv3 + residual): weights resident in LDS,
-// a wave owns a 32 x 256 output tile, operands straight from global memory into MFMA fragments; bit-identical to the tile kernels
-int mega_stream1x1_supports(const ConvParams& p, int out_f32);
-int mega_stream1x1_launch(const ConvParams& p, int half_dtype, hipStream_t st);
 // conv64.hip: persistent 3x3 / 64 -> 64 channel kernel (layer1's conv2); bit-identical to the generic tiles
 int mega_conv64_supports(const ConvParams& p, int out_f32);
 int mega_conv64_launch(const ConvParams& p, int half_dtype, hipStream_t st);

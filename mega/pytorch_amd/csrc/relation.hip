@@ -856,11 +856,6 @@ static int position_logits_tiled_impl(const float* rois_q, const float* rois_k, 
   return mega_check_launch();
 }
 
-extern "C" int mega_position_logits_tiled(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
-                                          const float* dim_mat, void* out_bf16, int Nq, int Nk, void* stream) {
-  return position_logits_tiled_impl(rois_q, rois_k, wg_t, bg, dim_mat, out_bf16, Nq, Nk, MEGA_BF16, stream);
-}
-
 // round 6: the tile-ordered logits in the head's 16-bit operand type (dtype = MEGA_BF16 / MEGA_F16)
 extern "C" int mega_position_logits_tiled_dt(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
                                              const float* dim_mat, void* out16, int Nq, int Nk, int dtype, void* stream) {
@@ -1052,11 +1047,6 @@ static int position_logits_tiled_batched_impl(const void* descs, int n, const fl
   return mega_check_launch();
 }
 
-extern "C" int mega_position_logits_tiled_batched(const void* descs, int n, const float* wg_t, const float* bg,
-                                                  const float* dim_mat, void* stream) {
-  return position_logits_tiled_batched_impl(descs, n, wg_t, bg, dim_mat, MEGA_BF16, stream);
-}
-
 extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
                                                      const float* dim_mat, int dtype, void* stream) {
   return position_logits_tiled_batched_impl(descs, n, wg_t, bg, dim_mat, dtype, stream);
@@ -1068,14 +1058,6 @@ extern "C" int mega_relation_attention(const void* q, int ldq, const void* k, in
                                        void* ws, size_t ws_bytes, void* stream) {
   return relation_attention_impl(q, ldq, k, ldk, vt, ldv, pos, ldp, nullptr, resid, ldr, bias_v, out, ldo, Nq, Nk,
                                  groups, scale, dtype, ws, ws_bytes, stream);
-}
-
-extern "C" int mega_relation_attention_tiled_pos(const void* q, int ldq, const void* k, int ldk, const void* vt,
-                                                 int ldv, const void* pos_tiled_bf16, const void* resid, int ldr,
-                                                 const float* bias_v, void* out, int ldo, int Nq, int Nk, int groups,
-                                                 float scale, void* ws, size_t ws_bytes, void* stream) {
-  return relation_attention_impl(q, ldq, k, ldk, vt, ldv, nullptr, 0, pos_tiled_bf16, resid, ldr, bias_v, out, ldo, Nq,
-                                 Nk, groups, scale, MEGA_BF16, ws, ws_bytes, stream);
 }
 
 extern "C" int mega_relation_attention_tiled_pos_dt(const void* q, int ldq, const void* k, int ldk, const void* vt,

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const T* __restrict__ in,
 // slice [x C/8, (x+1) C/8): its working set per frame is 1/8 of the map (1.2 MB for 2048 channels: L2-resident), a
 // block covers 256 / (CV/8) consecutive bins of that slice.  Same arithmetic, same results.
 // PLANES (f32 input only): the pooled values leave as split-precision planes -- row k of `out` is bf16 [hi | lo] of the
-// [PH PW C] f32 values (hi = bf16(v), lo = bf16(v - hi)): the operand mega_conv2d_nhwc_sp's fc0 reads, written here instead
+// [PH PW C] f32 values (hi = bf16(v), lo = bf16(v - hi)): the operand mega_conv2d_nhwc_sp_dt's fc0 reads, written here instead
 // of an f32 tensor that a second pass would have to read back and split (3 + 3 GB per 40-frame batch at C = 2048).
 // PT: the 16-bit type of the planes (bf16_t, or f16_t for the fp16 two-pass mode)
 template <typename T, bool XCD_SLICED, bool PLANES = false, typename PT = bf16_t>
@@ -1012,15 +1012,9 @@ extern "C" int mega_stem_pool_dt(const void* in, int u8, const void* w_n176, con
   return mega_check_launch();
 }
 
-extern "C" int mega_stem_pool_bf16(const void* in, int u8, const void* w_n176_bf16, const float* scale, const float* bias,
-                                   void* out, int N, int H, int W, float mean0, float mean1, float mean2, int to_bgr,
-                                   void* stream) {
-  return mega_stem_pool_dt(in, u8, w_n176_bf16, scale, bias, out, N, H, W, mean0, mean1, mean2, to_bgr, MEGA_BF16, stream);
-}
-
 // mega_roi_align_fwd for f32 NHWC features with the result as split-precision planes: out bf16 [K][2 PH PW C] =
 // [hi | lo] of the f32 pooled row [PH PW C] (the same arithmetic, term by term, as the f32 kernel -- ROIAlign_cuda.cu:64-122 --
-// then hi = bf16(v), lo = bf16(v - hi)).  C % 4 == 0.  The A operand of the split-precision fc0 (mega_conv2d_nhwc_sp).
+// then hi = bf16(v), lo = bf16(v - hi)).  C % 4 == 0.  The A operand of the split-precision fc0 (mega_conv2d_nhwc_sp_dt).
 extern "C" int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois, void* out, int K, int C, int H, int W,
                                             float spatial_scale, int pooled_h, int pooled_w, int sampling_ratio, int dtype,
                                             void* stream) {
@@ -1063,8 +1057,3 @@ extern "C" int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois
   return mega_check_launch();
 }
 
-extern "C" int mega_roi_align_fwd_planes(const float* feat, const float* rois, void* out, int K, int C, int H, int W,
-                                         float spatial_scale, int pooled_h, int pooled_w, int sampling_ratio, void* stream) {
-  return mega_roi_align_fwd_planes_dt(feat, rois, out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio, MEGA_BF16,
-                                      stream);
-}

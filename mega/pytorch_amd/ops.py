@@ -131,8 +131,8 @@ def _igemm_family(lib, M, Cout, K, dtype, shape=None):
     # one family = one rocprofv3 symbol: igemm8_kernel<OT, ...> is instantiated per OUTPUT type, so a bf16 launch that writes
     # f32 (fc0's split-K partial sums, the RPN head's f32 logits) is a different symbol from the bf16-output launches of the
     # same tile ("_f32out")
-    f32out = shape is not None and dtype in _HALF and (shape[-1] == torch.float32 or (kind in (2, 3, 4, 7, 8) and lib.mega_conv2d_nhwc_workspace_bytes(M, Cout, K) > 0))
-    return "igemm%s_%s_%dx%d%s" % ({8: "8", 7: "8s", 4: "4", 3: "4s", 2: "2", 1: "s"}.get(kind, ""), {torch.bfloat16: "bf16", torch.float16: "f16"}.get(dtype, "f32"),
+    f32out = shape is not None and dtype in _HALF and (shape[-1] == torch.float32 or (kind in (7, 8) and lib.mega_conv2d_nhwc_workspace_bytes(M, Cout, K) > 0))
+    return "igemm%s_%s_%dx%d%s" % ({8: "8", 7: "8s"}.get(kind, ""), {torch.bfloat16: "bf16", torch.float16: "f16"}.get(dtype, "f32"),
                                    t // 1000, t % 1000, "_f32out" if f32out else "")
 
 
@@ -540,7 +540,7 @@ def rpn_select(rpn_out, cell_anchors, Hf, Wf, anchor_stride, pre_nms, post_nms, 
                                  float(nms_thresh), int(strict_gt), float(min_size), float(im_w), float(im_h),
                                  _ptr(props), _ptr(scores), _ptr(cnt), _ptr(index), _ptr(ws), nb, _stream())
     _pe(_tok)
-    _lib.check(rc, "mega_rpn_select")
+    _lib.check(rc, "mega_rpn_select_idx")
     if hold is not None:
         hold.append(ws)
     return (props, scores, cnt, index) if want_index else (props, scores, cnt)
@@ -1129,7 +1129,7 @@ def split_conv_weight_x3(w_ohwi):
 
 def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_mode="planes", x3=True,
               out=None):
-    """conv + FrozenBN (+ residual) + activation on split-precision planes (mega_conv2d_nhwc_sp, igemm8 SP kernels).
+    """conv + FrozenBN (+ residual) + activation on split-precision planes (mega_conv2d_nhwc_sp_dt, igemm8 SP kernels).
     x: Planes [N,H,W,C].  x3=True: w = split_conv_weight_x3(W) [Cout,R,S,3C]; the contraction reads the planes as
     [hi | lo | hi] -- x.W to ~2^-16 with f32 accumulation.  x3=False: w plain bf16 [Cout,R,S,C], only the hi plane is read
     (bf16 compute over a wide residual stream).  residual: Planes [N,Ho,Wo,Cout] (hi + lo added in f32).

@@ -5,7 +5,7 @@ tag=${1:-r06}
 src=gpurun_out/$tag
 dst=profiles
 for f in bench_n1 bench_n1_driver_cli bench_n1_100step_blocks bench_n1_bf16x3 bench_n1_wide_trunk bench_n1_float16 bench_n1_f16x2 \
-         bench_n1_forced_sharded bench_n1_igemm2_k128 bench_n1_igemm2_streaming bench_n1_bf16_head_stream bench_n1_unfused_layer1 \
+         bench_n1_forced_sharded bench_n1_bf16_head_stream bench_n1_unfused_layer1 \
          bench_n1_two_batches_per_block config1 config1_f32 config2 config5; do
   [ -s $src/$f.json ] && cp $src/$f.json $dst/${tag}_$f.json
 done

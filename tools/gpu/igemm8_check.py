@@ -34,6 +34,12 @@ CASES += [                                                     # K = 64: ONE K-t
     (3, 150, 250, 64, 256, 1, 1, 0, 1, 0, False, False),      # layer1 downsample
     (1, 13, 15, 64, 320, 1, 1, 0, 1, 1, False, True),         # N tail, f32 out, M < one tile
 ]
+CASES += [                                                     # the streaming class (1x1, K <= 512) at its hot shapes
+    (9, 38, 63, 256, 1024, 1, 1, 0, 1, 1, True, False),       # layer3 conv3 (M = 21546: 10-row tail tile)
+    (9, 38, 63, 256, 1024, 1, 1, 0, 1, 2, False, False),      # LeakyReLU, no residual
+    (2, 75, 125, 128, 512, 1, 1, 0, 1, 1, True, False),       # layer2 conv3 (K = 128)
+    (8, 38, 63, 256, 2048, 1, 1, 0, 1, 0, True, False),       # eight N tiles
+]
 
 
 def run(case, force, reps=1):

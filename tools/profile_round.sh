@@ -44,9 +44,6 @@ timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype wide --no-cpu-b
 # round 6's modes as the main configuration
 timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype float16 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_float16.json 2> $out/bench_n1_float16.err
 timeout 300 python bench.py --full --steps 20 --warmup 5 --dtype f16x2 --no-cpu-baseline --no-f32-leg --no-h2d-leg --min-seconds 2 > $out/bench_n1_f16x2.json 2> $out/bench_n1_f16x2.err
-# round 6's opt-in GEMM kernels end to end (same box): igemm2 on the K <= 128 streaming layers, on the whole streaming class
-MEGA_IGEMM2=1 timeout 300 python bench.py $leg > $out/bench_n1_igemm2_k128.json 2> $out/bench_n1_igemm2_k128.err
-MEGA_IGEMM2=2 timeout 300 python bench.py $leg > $out/bench_n1_igemm2_streaming.json 2> $out/bench_n1_igemm2_streaming.err
 # A/B legs on the same box: the round-3 head (bf16 activation stream), the unfused layer1 blocks, two batches per block
 timeout 300 python bench.py $leg --head-stream bfloat16 > $out/bench_n1_bf16_head_stream.json 2> $out/bench_n1_bf16_head_stream.err
 MEGA_FUSE_BOTTLENECK=0 timeout 300 python bench.py $leg > $out/bench_n1_unfused_layer1.json 2> $out/bench_n1_unfused_layer1.err
