@@ -540,106 +540,68 @@ class GeneralizedRCNNDFF(nn.Module):
 DETECTION_META_ARCHITECTURES.register("GeneralizedRCNNDFF", GeneralizedRCNNDFF)
 
 
-class FgfaClipEngine(object):
-    """Clip-level driver for GeneralizedRCNNFGFA (BASELINE configs[4]): the MI355X-first way to run the reference's
-    per-key-frame loop (generalized_rcnn_fgfa.py:144-219; feed: data/datasets/vid_fgfa.py test mode).
+class _TwoGraphEngine(object):
+    """What FgfaClipEngine, DffClipEngine and BaseClipEngine share: a video as groups of `group` frames, each group as TWO
+    hipGraphs on two streams with the detection counts read a batch of groups later.
 
-    The reference (and `model(images)` here) runs ~200 launches per key frame at batch 1, re-concatenates the window's
-    21 images and 21 x 3072-channel maps every step, and reads the detection count back before the next frame: on
-    MI355X that is host-bound and its single-frame launches fill a fraction of the chip.  Here
-      * backbone + EmbedNet (+ the per-frame halves of FlowNetS's first conv) run for `lookahead` upcoming frames in ONE
-        batch (the kernels are batch-invariant: same bits), once per frame of the video;
-      * a frame's maps live in ring slot `frame id mod R`, R = T + group - 1: the window of key frame k is the frames
-        clamp(k - key + t, 0, L - 1), t = 0 .. T-1 (what the reference's deque holds: frame 0 replicated at the start, the
-        last frame at the end), i.e. a row of a device index table (`order[b]` = [slot of the key frame, slot of window
-        position t ...]); FlowNetS takes a key frame's pairs in slot order over the whole ring and the warp kernel visits the
-        window in window order through the table (mega_fgfa_warp_aggregate_ring) -- the bits of the contiguous call;
-      * `group` consecutive key frames (default 10) share ONE FlowNetS pass over exactly their group x T pairs (its coarse
-        levels have 840-12 768 GEMM rows at 21 pairs and leave half the chip idle: 1.05 ms per key frame at 21 pairs, 0.84 at
-        42, 0.77 at 84) and ONE batched box-head pass; the flow fields come out in window order per key frame
-        (mega_fgfa_warp_aggregate_ring_pos).  Same box, batched head: group 1 / 2 / 4 / 5 / 10 / 20 = 518 / 595 / 630 / 638 /
-        665 / 669 FPS (with the box head replayed per key frame the optimum was 2: profiles/r06_c5_group_ab.txt);
-      * the key frame is TWO hipGraphs on two streams: A = FlowNetS + warp of a group, B = RPN selection, res5 + ROIAlign +
-        fc6 / fc7, predictor, post-processing (fixed 300 proposal rows per frame, the device-side proposal counts go to the
-        post-processor) of the group's key frames as ONE batched launch chain (batch_head; or one replay per key frame);
-        B of one group runs beside A of the next (its one-block-per-frame selection / NMS kernels and 300-row GEMMs leave
-        most of the chip idle); detection counts are read a batch of steps later.
-    Detections are identical to `model(images)` frame by frame (tests/test_e2e_gpu.py::test_fgfa_engine_equals_model)."""
+      * graph A (`_body_a`, the subclass's) = the whole-chip work of a group on the static inputs that `_groups` loads:
+        -> C4 maps [group,h,w,1024];
+      * graph B = RPN selection, res5 + ROIAlign + fc6 / fc7, predictor, post-processing (fixed 300 proposal rows per frame,
+        the device-side proposal counts go to the post-processor) of the group's maps as ONE batched launch chain (batch_head:
+        `_body_bb`), or one replay of `_body_b` per map, dealt to `lanes` streams.  With one lane graph B forks its one-block
+        proposal selection to a side stream beside res5 (fork_select); with several lanes it does NOT: two lanes of forked
+        graphs replayed concurrently segfault inside hipGraphLaunch on this runtime (ROCm 7.0.2; reproducibly at 2 lanes, not at
+        3 or 4: profiles/r06_dff_engine_lanes.txt) -- and two plain lanes are as fast as three forked ones (1260 vs 1270 FPS);
+      * A's maps are copied into one of DEPTH staging buffers, B (pipeline=True: on a second stream) takes them from there: B
+        of one group runs beside A of the next ones (its one-block-per-frame selection / NMS kernels and 300-row GEMMs leave
+        most of the chip idle).  pipeline=False: both graphs on one stream;
+      * `run` reads the detection counts back once per `sync_every` frames (`_flush`).
+    The first group of a size runs eagerly (packs weights, warms the allocator), the second captures, the rest replay; graphs=False
+    (and every CPU run) stays eager.  A subclass gives `_alloc` (static inputs for a frame size), `_groups` (the plan of a
+    `run` call: loads one group's static inputs, yields its number of real frames) and `_body_a`."""
 
-    DEPTH = 3        # groups the first stream may run ahead of the second (staging buffers of aggregated maps)
-    lanes = 1        # graph-B lanes (streams): 1 hides the box head beside FlowNetS here; DffClipEngine uses more
-    fork_select = True   # graph B forks the one-block proposal selection to a side stream beside res5
-    batch_head = False   # graph B on all maps of a group in ONE batched replay (_body_bb) instead of one replay per map
+    DEPTH = 3        # groups the first stream may run ahead of the second (staging buffers of graph A's maps)
+    SYNC_EVERY = 1   # frames between two read-backs of detection counts (run's default; the subclasses' own)
 
-    def __init__(self, model, lookahead=20, graphs=True, pipeline=True, group=10, lanes=1, batch_head=True):
+    def __init__(self, model, group, graphs, pipeline, lanes, batch_head):
         self.m = model
-        self.batch_head = bool(batch_head)
-        self.lanes = max(1, int(lanes))
-        self.fork_select = self.lanes == 1   # (see DffClipEngine: forked graphs on several lanes crash the HIP runtime)
-        self.pipeline = pipeline             # graphs A and B on two streams (see _step); False: one graph on one stream
-        self.parts = model.dtype in (torch.bfloat16, torch.float16)    # FlowNetS's first conv per frame, kept in a ring
-        self.group = max(1, int(group))      # key frames per FlowNetS pass
-        self._sb = None
-        self.T = model.all_frame_interval
-        self.key = model.key_frame_location
-        self.R = self.T + self.group - 1
-        self.lookahead = lookahead
+        self.group = max(1, int(group))      # frames per graph A
         self.use_graphs = graphs
-        self.graph = None
-        self.fgraphs = {}
+        self.pipeline = pipeline             # graphs A and B on two streams (see _step); False: one graph on one stream
+        self.lanes = max(1, int(lanes))      # graph-B lanes (streams) of the per-frame box head
+        self.fork_select = self.lanes == 1   # graph B forks the one-block proposal selection to a side stream beside res5
+        self.batch_head = bool(batch_head)   # graph B on all maps of a group in ONE batched replay (_body_bb), else one per map
+        self.device = None                   # of the static inputs (_prepare)
+        self._sig = None                     # (H, W, device) they were allocated for
+        self.graph = None                    # None -> "armed" (one eager group done) -> (graph A, [graph B per lane])
+        self.fgraphs = {}                    # _graphed: input shape -> {in, out, graph}
+        self._sb = None                      # graph B's streams, one per lane
+        self._sides = {}                     # lane -> the side stream of its forked proposal selection
         self.replays = 0
-        self.feat_ring = None
-        self.keep_intermediates = False      # tests / diagnostics: self._dbg = per key frame (flow, aggregated map, proposals, ...)
 
-    # ---- features of a batch of frames (backbone + EmbedNet), replayed from a hipGraph per batch size
-    def _features(self, imgs):
-        m = self.m
-
-        def body(x):
-            f = _nhwc(m.backbone(x)[0])
-            out = torch.cat([f, m.embednet.run(f)], dim=-1)
-            if self.parts:               # + FlowNetS's first conv per frame (FlowNetS.conv1_parts)
-                return out, m.flownet.conv1_parts(x, m.dtype)
-            return out, None
-        if not (self.use_graphs and imgs.is_cuda):
-            return body(imgs)
-        ent = self.fgraphs.setdefault(tuple(imgs.shape), {})
-        if "seen" not in ent:            # first use of a shape: eager (packs weights, warms the allocator)
+    def _graphed(self, body, x):
+        """body(x) -> tuple of tensors (or None), replayed from a hipGraph per shape of x: the first use of a shape runs eagerly
+        (packs weights, warms the allocator), the second captures; the outputs are clones."""
+        if not (self.use_graphs and x.is_cuda):
+            return body(x)
+        ent = self.fgraphs.setdefault(tuple(x.shape), {})
+        if "seen" not in ent:
             ent["seen"] = True
-            return body(imgs)
+            return body(x)
         if "graph" not in ent:
-            ent["in"] = imgs.clone()
+            ent["in"] = x.clone()
             torch.cuda.current_stream().synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
                 ent["out"] = body(ent["in"])
             ent["graph"] = g
-        ent["in"].copy_(imgs)
+        ent["in"].copy_(x)
         ent["graph"].replay()
         return tuple(None if t is None else t.clone() for t in ent["out"])
 
-    # ---- a group of key frames on the ring state, in two halves (these bodies are what the graphs capture)
-    def _body_a(self):
-        """FlowNetS on the pairs of the group's key frames + flow-guided aggregation -> aggregated C4 maps [group,h,w,1024]"""
-        m = self.m
-        G, T = self.group, self.T
-        nfeat = m.backbone.out_channels
-        if self.parts:                  # key frame b = ring slot order[b][0]; ONE trunk pass over exactly the G x T pairs
-            flow = m.flownet.run_parts_multi(self.ab_ring, m.dtype, self.order)
-            flows = [flow[b * T:(b + 1) * T] for b in range(G)]
-            if not self.keep_intermediates:     # the group's warps in ONE launch (a key frame alone is 1.17 rounds of blocks)
-                return ops.fgfa_warp_aggregate_group(self.feat_ring, flow, nfeat, self.order, self.key)
-            aggs = [ops.fgfa_warp_aggregate(self.feat_ring, flows[b], nfeat, 0, order=self.order[b], flow_pos=self.key)
-                    for b in range(G)]
-        else:                           # (exact-f32 mode: the generic pair path, a key frame's pairs in slot order over the ring)
-            flows = [m.flownet.pairs(self.img_ring, None, m.dtype, order=self.order[b]) for b in range(G)]
-            aggs = [ops.fgfa_warp_aggregate(self.feat_ring, flows[b], nfeat, 0, order=self.order[b]) for b in range(G)]
-        if self.keep_intermediates:
-            self._dbg_a = [(flows[b], aggs[b]) for b in range(G)]
-        return torch.stack(aggs, dim=0)
-
+    # ---- graph B's bodies (what the graphs capture)
     def _body_b(self, agg, size, lane=0):
-        """RPN + conv5 box head + post-processing on ONE aggregated map [h,w,1024]"""
+        """RPN + conv5 box head + post-processing on ONE map [h,w,1024]"""
         m = self.m
         W, H = size
         feats = (_nchw_view(agg.unsqueeze(0)),)
@@ -648,10 +610,9 @@ class FgfaClipEngine(object):
         if agg.is_cuda and not ops.profiling() and self.fork_select:
             # the proposal selection is ONE block (top-k, decode, NMS of one frame: ~0.38 ms on 1 of 256 CUs) and res5 on the
             # whole map does not need its result: fork it to a side stream (one per lane), join before ROIAlign
-            sides = self.__dict__.setdefault("_sides", {})
-            if lane not in sides:
-                sides[lane] = torch.cuda.Stream(device=agg.device)
-            side = sides[lane]
+            if lane not in self._sides:
+                self._sides[lane] = torch.cuda.Stream(device=agg.device)
+            side = self._sides[lane]
             hold = []
             props, _, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key", select_stream=side, hold=hold)
             y = fe.full_map(feats)
@@ -663,8 +624,6 @@ class FgfaClipEngine(object):
             x = fe(feats, [props[0]])
         logits, deltas = box.predictor(x)
         pp = box.post_processor
-        if self.keep_intermediates:
-            self._dbg_b = (props, logits, deltas, x, cnt)
         return pp.padded(logits.float().contiguous(), deltas.float().contiguous(), props[0].contiguous(), cnt, (W, H))
 
     def _body_bb(self, aggs, size):
@@ -678,13 +637,13 @@ class FgfaClipEngine(object):
         box = m.roi_heads.box
         fe = box.feature_extractor
         if aggs.is_cuda and not ops.profiling():
-            sides = self.__dict__.setdefault("_sides", {})
-            if 0 not in sides:
-                sides[0] = torch.cuda.Stream(device=aggs.device)
+            if 0 not in self._sides:
+                self._sides[0] = torch.cuda.Stream(device=aggs.device)
+            side = self._sides[0]
             hold = []
-            props, _, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key", select_stream=sides[0], hold=hold)
+            props, _, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key", select_stream=side, hold=hold)
             y = fe.full_map(feats)
-            torch.cuda.current_stream(aggs.device).wait_stream(sides[0])
+            torch.cuda.current_stream(aggs.device).wait_stream(side)
             del hold
         else:
             props, _, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key")
@@ -697,42 +656,37 @@ class FgfaClipEngine(object):
 
     def _eager(self, size, n):
         aggs = self._body_a()
-        if self.batch_head and not self.keep_intermediates:
+        if self.batch_head:
             ob, os_, ol, oc = self._body_bb(aggs, size)
             return [(ob[b], os_[b], ol[b], oc[b:b + 1]) for b in range(n)]
-        outs = []
-        for b in range(n):
-            outs.append(self._body_b(aggs[b], size))
-            if self.keep_intermediates:
-                self._dbg = self._dbg_a[b] + self._dbg_b
-        return outs
+        return [self._body_b(aggs[b], size) for b in range(n)]
 
     def _step(self, size, n):
-        """the group on the ring state (order holds `group` rows; the first n are real key frames) -> n output tuples"""
-        if not (self.use_graphs and self.feat_ring.is_cuda):
+        """the group on the static inputs (`group` frames; the first n are real) -> n output tuples"""
+        if not (self.use_graphs and self.device.type == "cuda"):
             return self._eager(size, n)
         if self.graph is None:
             self.graph = "armed"
             return self._eager(size, n)
         cur = torch.cuda.current_stream()
         if self.graph == "armed":
-            # Graph A (FlowNetS + warp of the group: whole-chip GEMMs) replays on the current stream, graph B (RPN, box head,
-            # post-processing of ONE key frame: ~0.8 ms of one-block kernels and GEMMs on 2394 / 300 rows) on a second stream
-            # (pipeline=True), so that B of a group runs BESIDE A of the following groups.  A's maps are copied (on A's stream,
-            # 10 MB) into one of DEPTH staging buffers; B takes them from there, so A runs up to DEPTH groups ahead of B: with a
-            # lead of one group A stalled 0.9 ms per key frame behind B's stretched (contended) replays (tools/gpu/trace_c5.sh).
+            # Graph A (whole-chip GEMMs) replays on the current stream, graph B (~0.8 ms of one-block kernels and GEMMs on
+            # 2394 / 300 rows per frame) on a second stream (pipeline=True), so that B of a group runs BESIDE A of the following
+            # groups.  A's maps are copied (on A's stream, 10 MB) into one of DEPTH staging buffers; B takes them from there, so A
+            # runs up to DEPTH groups ahead of B: with a lead of one group A stalled 0.9 ms per key frame behind B's stretched
+            # (contended) replays (tools/gpu/trace_c5.sh).
             # The graphs replay concurrently: each has its own memory pool (torch's default for separately captured graphs).
             cur.synchronize()
             nl = 1 if self.batch_head else (self.lanes if self.pipeline else 1)
             if self._sb is None and self.pipeline:
-                self._sb = [torch.cuda.Stream(device=self.feat_ring.device) for _ in range(nl)]
+                self._sb = [torch.cuda.Stream(device=self.device) for _ in range(nl)]
             ga = torch.cuda.CUDAGraph()
             with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                 self._agg_out = self._body_a()
             self._agg_stage = [self._agg_out.clone() for _ in range(self.DEPTH)]
-            # graph B once per LANE (its own input, outputs, pool and side stream): the key frames of a group are dealt to the
+            # graph B once per LANE (its own input, outputs, pool and side stream): the frames of a group are dealt to the
             # lanes round-robin, each lane replaying on its own stream -- B is a latency chain of small launches (0.8-0.9 ms per
-            # key frame), and when graph A is short (DffClipEngine: 10 pairs per 10 frames) ONE lane of B is the bottleneck
+            # frame), and when graph A is short (DffClipEngine: 10 pairs per 10 frames) ONE lane of B is the bottleneck
             self._agg_in, self._out, gbs = [], [], []
             for l in range(nl):
                 self._agg_in.append(self._agg_out.clone() if self.batch_head else self._agg_out[0].clone())
@@ -776,26 +730,115 @@ class FgfaClipEngine(object):
                 self._eb[j][l].record(sb)
         for o in outs:
             for t in o:
-                t.record_stream(cur)          # read on the current stream after the join in run()'s flush
+                t.record_stream(cur)          # read on the current stream after the join in _flush
         self.replays += n
         return outs
 
-    def _reset(self, frames):
-        """rings for a video of this size (kept, with the captured graphs that read them, when the size repeats)"""
-        m = self.m
-        dev = frames.device
+    def _prepare(self, frames):
+        """static inputs for frames of this size on this device (kept, with the captured graphs that read them, when both repeat)"""
         H, W = frames.shape[-2:]
-        sig = (H, W, str(dev))
-        if self.feat_ring is None or self._sig != sig:
-            f, ab = self._features(frames[0:1].float())
-            self.feat_ring = f.new_zeros((self.R,) + tuple(f.shape[1:]))
-            self.ab_ring = None if ab is None else ab.new_zeros((self.R,) + tuple(ab.shape[1:]))
-            self.img_ring = None if self.parts else frames.new_zeros((self.R, 3, H, W), dtype=torch.float32)
-            self.order = torch.zeros((self.group, self.T + 1), dtype=torch.int32, device=dev)
+        sig = (H, W, str(frames.device))
+        if self._sig != sig:
+            self.device = frames.device
+            self._alloc(frames)
             self._sig = sig
             self.graph = None
-        self.slot_fid = [-1] * self.R
-        self.cache = {}                                  # frame id -> ([h,w,3072], conv1 halves) computed ahead of need
+
+    def _flush(self, pending, out, size):
+        """the pending frames' detection counts in ONE read-back -> their BoxLists appended to out"""
+        if not pending:
+            return
+        for s_ in (self._sb or []):
+            torch.cuda.current_stream().wait_stream(s_)           # (the second halves of the pending frames)
+        counts = torch.cat([p[3] for p in pending]).tolist()
+        for (ob, os_, ol, _), n in zip(pending, counts):
+            out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), size))
+        del pending[:]
+
+    @torch.no_grad()
+    def run(self, frames, first=0, last=None, sync_every=None):
+        """frames: preprocessed f32 [L,3,H,W] on the device (the whole video: inference.resident_video builds it from a
+        feed.FrameSource).  Frames first..last-1 -> list[BoxList]."""
+        last = frames.shape[0] if last is None else last
+        sync_every = self.SYNC_EVERY if sync_every is None else sync_every
+        H, W = frames.shape[-2:]
+        self._prepare(frames)
+        out, pending = [], []
+        for n in self._groups(frames, first, last):
+            pending.extend(self._step((W, H), n))
+            if len(pending) >= sync_every:
+                self._flush(pending, out, (W, H))
+        self._flush(pending, out, (W, H))
+        return out
+
+
+class FgfaClipEngine(_TwoGraphEngine):
+    """Clip-level driver for GeneralizedRCNNFGFA (BASELINE configs[4]): the MI355X-first way to run the reference's
+    per-key-frame loop (generalized_rcnn_fgfa.py:144-219; feed: data/datasets/vid_fgfa.py test mode).
+
+    The reference (and `model(images)` here) runs ~200 launches per key frame at batch 1, re-concatenates the window's
+    21 images and 21 x 3072-channel maps every step, and reads the detection count back before the next frame: on
+    MI355X that is host-bound and its single-frame launches fill a fraction of the chip.  Here
+      * backbone + EmbedNet (+ the per-frame halves of FlowNetS's first conv) run for `lookahead` upcoming frames in ONE
+        batch (the kernels are batch-invariant: same bits), once per frame of the video;
+      * a frame's maps live in ring slot `frame id mod R`, R = T + group - 1: the window of key frame k is the frames
+        clamp(k - key + t, 0, L - 1), t = 0 .. T-1 (what the reference's deque holds: frame 0 replicated at the start, the
+        last frame at the end), i.e. a row of a device index table (`order[b]` = [slot of the key frame, slot of window
+        position t ...]); FlowNetS takes a key frame's pairs in slot order over the whole ring and the warp kernel visits the
+        window in window order through the table (mega_fgfa_warp_aggregate_ring) -- the bits of the contiguous call;
+      * `group` consecutive key frames (default 10) share ONE FlowNetS pass over exactly their group x T pairs (its coarse
+        levels have 840-12 768 GEMM rows at 21 pairs and leave half the chip idle: 1.05 ms per key frame at 21 pairs, 0.84 at
+        42, 0.77 at 84) and ONE batched box-head pass; the flow fields come out in window order per key frame
+        (mega_fgfa_warp_aggregate_ring_pos).  Same box, batched head: group 1 / 2 / 4 / 5 / 10 / 20 = 518 / 595 / 630 / 638 /
+        665 / 669 FPS (with the box head replayed per key frame the optimum was 2: profiles/r06_c5_group_ab.txt);
+      * graph A (_TwoGraphEngine) = FlowNetS + warp of a group; one lane of graph B hides the box head beside it.
+    run(): key frames first..last-1 (first = 0 starts a new video; first > 0 continues the previous call's video on the ring
+    state).  Detections are identical to `model(images)` frame by frame (tests/test_e2e_gpu.py::test_fgfa_engine_equals_model)."""
+
+    SYNC_EVERY = 16
+
+    def __init__(self, model, lookahead=20, graphs=True, pipeline=True, group=10, lanes=1, batch_head=True):
+        super().__init__(model, group, graphs, pipeline, lanes, batch_head)
+        self.parts = model.dtype in (torch.bfloat16, torch.float16)    # FlowNetS's first conv per frame, kept in a ring
+        self.T = model.all_frame_interval
+        self.key = model.key_frame_location
+        self.R = self.T + self.group - 1
+        self.lookahead = lookahead
+
+    def _features(self, imgs):
+        """backbone + EmbedNet of a batch of frames -> (NHWC [n,h,w,3072], conv1 halves or None)"""
+        m = self.m
+
+        def body(x):
+            f = _nhwc(m.backbone(x)[0])
+            out = torch.cat([f, m.embednet.run(f)], dim=-1)
+            # + FlowNetS's first conv per frame (FlowNetS.conv1_parts)
+            return out, (m.flownet.conv1_parts(x, m.dtype) if self.parts else None)
+        return self._graphed(body, imgs)
+
+    def _body_a(self):
+        """FlowNetS on the pairs of the group's key frames + flow-guided aggregation -> aggregated C4 maps [group,h,w,1024]"""
+        m = self.m
+        nfeat = m.backbone.out_channels
+        if self.parts:
+            # key frame b = ring slot order[b][0]; ONE trunk pass over exactly the G x T pairs, then the group's warps in ONE
+            # launch (a key frame alone is 1.17 rounds of blocks)
+            flow = m.flownet.run_parts_multi(self.ab_ring, m.dtype, self.order)
+            return ops.fgfa_warp_aggregate_group(self.feat_ring, flow, nfeat, self.order, self.key)
+        # exact-f32 mode: the generic pair path, a key frame's pairs in slot order over the ring
+        flows = [m.flownet.pairs(self.img_ring, None, m.dtype, order=self.order[b]) for b in range(self.group)]
+        return torch.stack([ops.fgfa_warp_aggregate(self.feat_ring, flows[b], nfeat, 0, order=self.order[b])
+                            for b in range(self.group)], dim=0)
+
+    def _alloc(self, frames):
+        """rings for a video of this size"""
+        H, W = frames.shape[-2:]
+        f, ab = self._features(frames[0:1].float())
+        self.feat_ring = f.new_zeros((self.R,) + tuple(f.shape[1:]))
+        self.ab_ring = None if ab is None else ab.new_zeros((self.R,) + tuple(ab.shape[1:]))
+        self.img_ring = None if self.parts else frames.new_zeros((self.R, 3, H, W), dtype=torch.float32)
+        self.order = torch.zeros((self.group, self.T + 1), dtype=torch.int32, device=frames.device)
+        self.slot_fid = None
 
     def _ensure(self, frames, fids):
         """the frames `fids` resident in their ring slots (slot = id mod R); features of the next `lookahead` new frames in one
@@ -823,29 +866,12 @@ class FgfaClipEngine(object):
                 self.img_ring[s].copy_(frames[fid])
             self.slot_fid[s] = fid
 
-    @torch.no_grad()
-    def run(self, frames, first=0, last=None, sync_every=16):
-        """frames: preprocessed f32 [L,3,H,W] on the device (the whole video: inference.resident_video builds it from a
-        feed.FrameSource).  Key frames first..last-1 (first = 0 starts a new video; first > 0 continues the previous call's video
-        on the ring state).  -> list[BoxList]."""
+    def _groups(self, frames, first, last):
         L = frames.shape[0]
-        last = L if last is None else last
-        H, W = frames.shape[-2:]
         T, key, G, R = self.T, self.key, self.group, self.R
-        out, pending = [], []
-
-        def flush():
-            if not pending:
-                return
-            for s_ in (self._sb or []):
-                torch.cuda.current_stream().wait_stream(s_)           # (the second halves of the pending key frames)
-            counts = torch.cat([p[3] for p in pending]).tolist()
-            for (ob, os_, ol, _), n in zip(pending, counts):
-                out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), (W, H)))
-            del pending[:]
-
-        if first == 0 or self.feat_ring is None:
-            self._reset(frames)
+        if first == 0 or self.slot_fid is None:              # a new video: nothing resident
+            self.slot_fid = [-1] * R
+            self.cache = {}                                  # frame id -> ([h,w,3072], conv1 halves) computed ahead of need
         # the index tables of every group of this call, uploaded ONCE (a pinned upload per group cost the host a pinned
         # allocation and the stream a host round trip per group)
         plan, rows = [], []
@@ -859,118 +885,60 @@ class FgfaClipEngine(object):
             rows.append([[k % R] + [f % R for f in w] for k, w in zip(keys, wins)])
             idx += n
         if not plan:
-            return out
+            return
         od = torch.tensor(rows, dtype=torch.int32)                               # [groups, G, 1 + T]
         od = od.pin_memory().to(self.order.device, non_blocking=True) if self.order.is_cuda else od
         for gi, (n, fids) in enumerate(plan):
             self._ensure(frames, fids)
             self.order.copy_(od[gi])
-            pending.extend(self._step((W, H), n))
-            if len(pending) >= sync_every:
-                flush()
-        flush()
-        return out
+            yield n
 
 
-class DffClipEngine(FgfaClipEngine):
+class DffClipEngine(_TwoGraphEngine):
     """Clip-level driver for GeneralizedRCNNDFF (generalized_rcnn_dff.py:19-138, feed: vid_dff.py test mode --
-    a key frame every `interval` = 10 frames): the two-graph / two-stream form of FgfaClipEngine for deep feature flow.
+    a key frame every `interval` = 10 frames): the two-graph / two-stream form (_TwoGraphEngine) for deep feature flow.
 
     `model(images)` runs, per frame and at batch 1, FlowNetS on ONE image pair (its coarse levels have 40-600 GEMM rows), a warp,
     the RPN and the conv5 box head, and reads the detection count back: host- and latency-bound (600 FPS on R-101).  Here
       * the backbone runs on `lookahead` upcoming KEY frames in one batch;
       * graph A = FlowNetS on the `interval` pairs (frame, key frame) of a key-frame interval in ONE pass + their warp x scale
-        (mega_dff_warp_scale) -> `interval` feature maps;
-      * graph B = RPN selection, res5 + ROIAlign + fc6 / fc7, predictor, post-processing of one frame, replayed per frame on a
-        second stream beside graph A of the following intervals (FgfaClipEngine._step).
-    Detections are identical to `model(images)` frame by frame (tests/test_e2e_gpu.py::test_dff_engine_equals_model)."""
+        (mega_dff_warp_scale) -> `interval` feature maps (group = the key-frame interval, vid_dff.py:62: frame_id % 10 == 0);
+      * graph B on the interval's frames; replayed per frame (batch_head=False) it wants two lanes: graph A is short here
+        and ONE lane of B is the bottleneck.
+    run(): `first` must be a key frame (a multiple of the interval).  Detections are identical to `model(images)` frame by
+    frame (tests/test_e2e_gpu.py::test_dff_engine_equals_model)."""
+
+    SYNC_EVERY = 20
 
     def __init__(self, model, interval=10, lookahead=8, graphs=True, pipeline=True, lanes=2, batch_head=True):
-        self.m = model
-        self.batch_head = bool(batch_head)   # the box head of the interval's frames as ONE batched graph (else per frame, on lanes)
-        self.pipeline = pipeline
-        self.lanes = max(1, int(lanes))      # graph-B lanes: two frames' box heads in flight (FgfaClipEngine._step)
-        # With several lanes graph B does NOT fork its proposal selection to a side stream: two lanes of forked graphs replayed
-        # concurrently segfault inside hipGraphLaunch on this runtime (ROCm 7.0.2; reproducibly at 2 lanes, not at 3 or 4:
-        # profiles/r06_dff_engine_lanes.txt) -- and two plain lanes are as fast as three forked ones (1260 vs 1270 FPS)
-        self.fork_select = self.lanes == 1
-        self.group = int(interval)           # frames per graph A = the key-frame interval (vid_dff.py:62: frame_id % 10 == 0)
-        self._sb = None
+        super().__init__(model, interval, graphs, pipeline, lanes, batch_head)
         self.lookahead = lookahead
-        self.use_graphs = graphs
-        self.graph = None
-        self.fgraphs = {}
-        self.replays = 0
-        self.feat_ring = None
-        self.keep_intermediates = False
 
     def _features(self, imgs):
-        """backbone of a batch of key frames -> NHWC [n,h,w,1024] (replayed from a hipGraph per batch size)"""
-        m = self.m
-
-        def body(x):
-            return _nhwc(m.backbone(x)[0]).contiguous()
-        if not (self.use_graphs and imgs.is_cuda):
-            return body(imgs)
-        ent = self.fgraphs.setdefault(tuple(imgs.shape), {})
-        if "seen" not in ent:
-            ent["seen"] = True
-            return body(imgs)
-        if "graph" not in ent:
-            ent["in"] = imgs.clone()
-            torch.cuda.current_stream().synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                ent["out"] = body(ent["in"])
-            ent["graph"] = g
-        ent["in"].copy_(imgs)
-        ent["graph"].replay()
-        return ent["out"].clone()
+        """backbone of a batch of key frames -> NHWC [n,h,w,1024]"""
+        return self._graphed(lambda x: (_nhwc(self.m.backbone(x)[0]).contiguous(),), imgs)[0]
 
     def _body_a(self):
         """FlowNetS on the interval's pairs (frame, key frame) + warp x scale -> [interval,h,w,1024]"""
         m = self.m
         n = self.group
         flow, scale = m.flownet.pairs(self.key_img.expand(n, -1, -1, -1), self.cur_imgs, m.dtype)      # :132 cat([cur, key])
-        aggs = [ops.dff_warp_scale(self.key_feat, flow[i].contiguous(), scale[i].contiguous()) for i in range(n)]
-        if self.keep_intermediates:
-            self._dbg_a = [(flow[i], aggs[i]) for i in range(n)]
-        return torch.stack(aggs, dim=0)
+        return torch.stack([ops.dff_warp_scale(self.key_feat, flow[i].contiguous(), scale[i].contiguous()) for i in range(n)], dim=0)
 
-    @torch.no_grad()
-    def run(self, frames, first=0, last=None, sync_every=20):
-        """frames: preprocessed f32 [L,3,H,W] on the device.  Frames first..last-1 (first a multiple of the interval)
-        -> list[BoxList]."""
-        L = frames.shape[0]
-        last = L if last is None else last
+    def _alloc(self, frames):
         H, W = frames.shape[-2:]
+        f = self._features(frames[0:1].float())
+        self.key_feat = torch.zeros_like(f[0])
+        self.key_img = frames.new_zeros((1, 3, H, W), dtype=torch.float32)
+        self.cur_imgs = frames.new_zeros((self.group, 3, H, W), dtype=torch.float32)
+
+    def _groups(self, frames, first, last):
+        L = frames.shape[0]
         I = self.group
         if first % I:
             raise ValueError("DffClipEngine.run: first = %d is not a key frame (multiple of %d)" % (first, I))
-        out, pending = [], []
-
-        def flush():
-            if not pending:
-                return
-            for s_ in (self._sb or []):
-                torch.cuda.current_stream().wait_stream(s_)
-            counts = torch.cat([p[3] for p in pending]).tolist()
-            for (ob, os_, ol, _), n in zip(pending, counts):
-                out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), (W, H)))
-            del pending[:]
-
-        sig = (H, W, str(frames.device))
-        if self.feat_ring is None or self._sig != sig:
-            f = self._features(frames[0:1].float())
-            self.key_feat = torch.zeros_like(f[0])
-            self.feat_ring = self.key_feat                        # (what FgfaClipEngine._step asks for the device)
-            self.key_img = frames.new_zeros((1, 3, H, W), dtype=torch.float32)
-            self.cur_imgs = frames.new_zeros((I, 3, H, W), dtype=torch.float32)
-            self._sig = sig
-            self.graph = None
         cache = {}
-        k0 = first
-        while k0 < last:
+        for k0 in range(first, last, I):
             if k0 not in cache:                                   # the backbone of the next `lookahead` key frames in one batch
                 ids = [k for k in range(k0, L, I)][:self.lookahead]
                 ids = ids + [ids[-1]] * (self.lookahead - len(ids))
@@ -982,75 +950,32 @@ class DffClipEngine(FgfaClipEngine):
             self.cur_imgs[:n].copy_(frames[k0:k0 + n])
             if n < I:                                             # a short last interval: the graph's shape stays, the tail repeats
                 self.cur_imgs[n:].copy_(frames[k0 + n - 1:k0 + n].expand(I - n, -1, -1, -1))
-            pending.extend(self._step((W, H), n))
-            k0 += I
-            if len(pending) >= sync_every:
-                flush()
-        flush()
-        return out
+            yield n
 
 
-class BaseClipEngine(FgfaClipEngine):
+class BaseClipEngine(_TwoGraphEngine):
     """Clip-level driver for the single-frame GeneralizedRCNN (BASELINE configs[0], detector/generalized_rcnn.py:16-65): no
-    cross-frame state, so graph A is simply the backbone on `group` consecutive frames (one batched launch chain instead of
-    `group` single-frame ones) and graph B -- RPN selection, res5 + ROIAlign + fc6 / fc7, predictor, post-processing of one
-    frame -- replays per frame on two lanes / streams beside it (FgfaClipEngine._step).  Detections are identical to
-    `model(image)` frame by frame (tests/test_e2e_gpu.py::test_base_engine_equals_model)."""
+    cross-frame state, so graph A (_TwoGraphEngine) is simply the backbone on `group` consecutive frames (one batched launch
+    chain instead of `group` single-frame ones) and graph B the box head of those frames beside it (per frame: on two lanes).
+    Detections are identical to `model(image)` frame by frame (tests/test_e2e_gpu.py::test_base_engine_equals_model)."""
+
+    SYNC_EVERY = 40
 
     def __init__(self, model, group=20, graphs=True, pipeline=True, lanes=2, batch_head=True):
-        self.m = model
-        self.batch_head = bool(batch_head)   # the box head of the group's frames as ONE batched graph (else per frame, on lanes)
-        self.pipeline = pipeline
-        self.group = int(group)
-        self.lanes = max(1, int(lanes))
-        self.fork_select = self.lanes == 1
-        self._sb = None
-        self.use_graphs = graphs
-        self.graph = None
-        self.replays = 0
-        self.feat_ring = None
-        self.keep_intermediates = False
+        super().__init__(model, group, graphs, pipeline, lanes, batch_head)
 
     def _body_a(self):
-        maps = _nhwc(self.m.backbone(self.cur_imgs)[0]).contiguous()            # [group,h,w,1024]
-        if self.keep_intermediates:
-            self._dbg_a = [(None, maps[i]) for i in range(self.group)]
-        return maps
+        return _nhwc(self.m.backbone(self.cur_imgs)[0]).contiguous()            # [group,h,w,1024]
 
-    @torch.no_grad()
-    def run(self, frames, first=0, last=None, sync_every=40):
-        """frames: preprocessed f32 [L,3,H,W] on the device.  Frames first..last-1 -> list[BoxList]."""
-        L = frames.shape[0]
-        last = L if last is None else last
+    def _alloc(self, frames):
         H, W = frames.shape[-2:]
+        self.cur_imgs = frames.new_zeros((self.group, 3, H, W), dtype=torch.float32)
+
+    def _groups(self, frames, first, last):
         G = self.group
-        out, pending = [], []
-
-        def flush():
-            if not pending:
-                return
-            for s_ in (self._sb or []):
-                torch.cuda.current_stream().wait_stream(s_)
-            counts = torch.cat([p[3] for p in pending]).tolist()
-            for (ob, os_, ol, _), n in zip(pending, counts):
-                out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), (W, H)))
-            del pending[:]
-
-        sig = (H, W, str(frames.device))
-        if self.feat_ring is None or self._sig != sig:
-            self.cur_imgs = frames.new_zeros((G, 3, H, W), dtype=torch.float32)
-            self.feat_ring = self.cur_imgs                        # (what FgfaClipEngine._step asks for the device)
-            self._sig = sig
-            self.graph = None
-        k0 = first
-        while k0 < last:
+        for k0 in range(first, last, G):
             n = min(G, last - k0)
             self.cur_imgs[:n].copy_(frames[k0:k0 + n])
-            if n < G:
+            if n < G:                                             # a short last group: the graph's shape stays, the tail repeats
                 self.cur_imgs[n:].copy_(frames[k0 + n - 1:k0 + n].expand(G - n, -1, -1, -1))
-            pending.extend(self._step((W, H), n))
-            k0 += n
-            if len(pending) >= sync_every:
-                flush()
-        flush()
-        return out
+            yield n

@@ -327,8 +327,6 @@ def method_line(args, dev, method):
     if method == "dff":       # the clip engine (fgfa.DffClipEngine): one FlowNetS pass per key-frame interval, two graphs / streams
         from mega.pytorch_amd import fgfa as fgfa_mod
         eng = fgfa_mod.DffClipEngine(model, interval=10, lookahead=8, lanes=args.lanes or 2, batch_head=args.batch_head != 0)
-        if os.environ.get("MEGA_NO_FORK_SELECT") == "0":      # (experiments: the forked selection on several lanes)
-            eng.fork_select = True
         eng.run(video, first=0, last=80)
         eb, pos = [], 80
         while pos + 40 <= L and sum(eb) < 1.0:
