@@ -496,6 +496,28 @@ int mega_seq_nms(const float* box, const float* score, const long long* seg_off,
                  long long N, float link_iou, float nms_iou, int rescore_max, unsigned char* keep, float* new_score,
                  long long* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* Detection overlay of the demo (mega/pytorch_amd/demo.py defines it), in place on F original-size frames, no host round
+ * trip.  Per frame: rows i < counts[f] with score > thr (strict), drawn in descending score order (equal scores: ascending
+ * row); box -> original frame by ONE f32 multiply per coordinate (x * sx, y * sy; sx = f32(W / resized width) computed by
+ * the caller) and truncation toward zero; degenerate boxes, boxes wholly outside the image and classes outside [0, NC)
+ * are dropped.  All outlines (thickness odd: the pixels within Chebyshev distance (thickness - 1) / 2 of the 1-pixel
+ * rectangle, colour palette[class]) are drawn in that order, then all labels "<name>: D.DD" on top: the rectangle (sum of
+ * the glyph advances wide, gh high, its bottom on the box's top edge, moved inside the box at the image's top, clamped
+ * horizontally) filled with the class colour c and blended with white by glyph coverage a: (c (255 - a) + 255 a + 127) /
+ * 255.  D.DD are the digits of "%.2f" for scores in [0, 1] (rint of the exact f64 product score * 100).
+ *   frames [F][H][W][3] u8 (in / out); boxes [F][R][4] f32 xyxy; scores [F][R] f32; labels [F][R] i64 (labels_i64 = 1) or
+ *   i32; counts [F] i32; palette [NC][3] u8; class_glyphs [NC][ML] i32: the glyphs of each class name, ended by a value
+ *   outside [0, G) (ML <= 18); fmt_glyphs [13] i32: the glyphs of '0'..'9', ':', ' ', '.'; cov [G][gh][gw] u8 coverage,
+ *   adv [G] i32 advances (a glyph shows its first min(adv, gw) columns); G <= 256.
+ * select_only = 1 stops after the selection pass (timing).  thickness even or < 1: MEGA_ERR_ARG; R > 512:
+ * MEGA_ERR_LIMIT, both before any launch.  R = 0 is a no-op.  Workspace: mega_overlay_detections_workspace_bytes(F, R). */
+size_t mega_overlay_detections_workspace_bytes(int F, int R);
+int mega_overlay_detections(unsigned char* frames, int F, int H, int W, const float* boxes, const float* scores,
+                            const void* labels, int labels_i64, const int* counts, int R, float sx, float sy, float thr,
+                            int thickness, const unsigned char* palette, int NC, const int* class_glyphs, int ML,
+                            const int* fmt_glyphs, const unsigned char* cov, const int* adv, int G, int gh, int gw,
+                            int select_only, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,10 @@ SIGNATURES = {
     "mega_seq_nms_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
     "mega_seq_nms": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int] + [c_void_p] * 4 +
                      [c_size_t, c_void_p]),
+    "mega_overlay_detections_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mega_overlay_detections": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                        c_float, c_float, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "mega_last_error_string": (ctypes.c_char_p, []),
 }
 

@@ -108,7 +108,7 @@ class FrameSource(object):
 
     img_dir / pattern follow the reference's conventions (`img_dir % (pattern % frame_id)`,
     vid_mega.py:108-109, vid.py `_img_dir`/`pattern`).  fetch(ids) returns the RESIZED uint8 frames [n,H,W,3] on
-    the device; prefetch(ids) starts the host decodes early."""
+    the device, fetch_original(ids) the decoded frames before the resize; prefetch(ids) starts the host decodes early."""
 
     def __init__(self, img_dir, pattern, seg_len, device, min_size=600, max_size=1000, workers=8, cache_frames=64,
                  opener=None, hflip=False):
@@ -210,6 +210,11 @@ class FrameSource(object):
         if ent is not None:
             self._drop_ahead()
         return self._resized(self._to_device(ids))
+
+    def fetch_original(self, ids):
+        """the decoded, UNRESIZED uint8 frames `ids` [n,Hi,Wi,3] on the device (what the demo draws on): the same host
+        decode cache and pinned staging as fetch(); the read-ahead batch, if any, is left alone"""
+        return self._to_device(ids)
 
     def _resized(self, dev):
         if self.out_hw == self.in_hw:

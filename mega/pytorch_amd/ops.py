@@ -1437,3 +1437,44 @@ def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     _pe(_tok)
     _lib.check(rc, "mega_seq_nms")
     return keep, new_score, stats
+
+
+# ------------------------------------------------------------------------------------------------ demo overlay
+def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, thickness, palette, atlas,
+                       select_only=False):
+    """Draw the detections of F frames in place on the original-size frames (include/mega_hip.h mega_overlay_detections;
+    mega/pytorch_amd/demo.py defines the picture).  frames [F,H,W,3] u8, boxes [F,R,4] f32 xyxy in the resized frame
+    (resized_hw = its (height, width)), scores [F,R] f32, labels [F,R] i64 or i32, counts [F] i32, palette [NC,3] u8,
+    atlas: demo.LabelAtlas.to(device) (cells [G,gh,gw] u8, advances [G] i32, class_glyphs [NC,ML] i32, fmt_glyphs [13] i32).
+    Returns frames.  No synchronisation; nothing is copied to the host."""
+    _gpu(frames, boxes, scores, labels, counts, palette, atlas.cells, atlas.advances, atlas.class_glyphs, atlas.fmt_glyphs)
+    lib = _lib.load()
+    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    R = boxes.shape[1]
+    assert frames.dtype == torch.uint8 and frames.shape == (F, H, W, 3) and frames.is_contiguous()
+    assert boxes.dtype == torch.float32 and boxes.shape == (F, R, 4) and boxes.is_contiguous()
+    assert scores.dtype == torch.float32 and scores.shape == (F, R) and scores.is_contiguous()
+    assert labels.dtype in (torch.int64, torch.int32) and labels.shape == (F, R) and labels.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.shape == (F,) and counts.is_contiguous()
+    assert palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3 and palette.is_contiguous()
+    NC = palette.shape[0]
+    G, gh, gw = atlas.cells.shape
+    assert atlas.cells.dtype == torch.uint8 and atlas.cells.is_contiguous()
+    assert atlas.advances.dtype == torch.int32 and atlas.advances.shape == (G,)
+    assert atlas.class_glyphs.dtype == torch.int32 and atlas.class_glyphs.shape[0] == NC and atlas.class_glyphs.is_contiguous()
+    assert atlas.fmt_glyphs.dtype == torch.int32 and atlas.fmt_glyphs.shape == (13,)
+    ML = atlas.class_glyphs.shape[1]
+    rh, rw = int(resized_hw[0]), int(resized_hw[1])
+    # BoxList.resize: the ratio is a Python float (f64 division), the multiply an f32 tensor op with the ratio rounded to f32
+    sx, sy = float(torch.tensor(W / rw, dtype=torch.float32)), float(torch.tensor(H / rh, dtype=torch.float32))
+    nb = lib.mega_overlay_detections_workspace_bytes(F, R)
+    ws = _ws(max(nb, 1), frames.device)
+    _tok = _pb("overlay")
+    rc = lib.mega_overlay_detections(_ptr(frames), F, H, W, _ptr(boxes), _ptr(scores), _ptr(labels),
+                                     int(labels.dtype == torch.int64), _ptr(counts), R, sx, sy, float(thr), int(thickness),
+                                     _ptr(palette), NC, _ptr(atlas.class_glyphs), ML, _ptr(atlas.fmt_glyphs),
+                                     _ptr(atlas.cells), _ptr(atlas.advances), G, gh, gw, int(bool(select_only)), _ptr(ws), nb,
+                                     _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_overlay_detections")
+    return frames
