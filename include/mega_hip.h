@@ -251,7 +251,10 @@ int mega_resize_bilinear_u8_flip(const unsigned char* in, unsigned char* out, un
  * against the key frame's, softmax over frames, weighted feature sum -- one fused kernel.  Replaces
  * GeneralizedRCNNFGFA.get_grid / resample / compute_weight + the softmax / sum of _forward_test
  * (mega_core/modeling/detector/generalized_rcnn_fgfa.py:45-76,:201-211).
- *   feats [T][H][W][Cf+Ce] NHWC, flow [T][2][H][W] f32, out [H][W][Cf], weights_out [T][H][W] f32 or NULL. */
+ *   feats [T][H][W][Cf+Ce] NHWC, flow [T][2][H][W] f32, out [H][W][Cf], weights_out [T][H][W] f32 or NULL.
+ * Shape limits, shared by the four mega_fgfa_warp_aggregate* entry points (ve = 8 elements per 16-byte vector in bf16, 4 in
+ * f32): Cf / ve <= 256 and 256 % (Cf / ve) == 0, T < 63, H * W * (Cf + Ce) < 2^31.  Any other shape returns MEGA_ERR_ARG
+ * before any launch (until the one-pass kernel was removed, such a shape silently ran on that slower kernel). */
 int mega_fgfa_warp_aggregate(const void* feats, const float* flow, void* out, float* weights_out, int T, int H,
                              int W, int Cf, int Ce, int key, int dtype, void* stream);
 /* The same with the T maps and flow fields held in a ring of T slots (the window's deques of
@@ -446,7 +449,8 @@ int mega_flow_conv1_combine(const float* ab, const float* bias, const int* order
                             int nwin, int dtype, void* stream);
 /* mega_fgfa_warp_aggregate_ring with the flow fields in WINDOW order: flow [T][2][H][W] = the T pairs (key frame, window
  * position t) and nothing else; key_pos = the key frame's window position (cfg KEY_FRAME_LOCATION).  What a FlowNetS pass over
- * the exact pairs of several key frames (mega_flow_conv1_combine with nwin > 0) hands to the warp. */
+ * the exact pairs of several key frames (mega_flow_conv1_combine with nwin > 0) hands to the warp.  Shape limits: see
+ * mega_fgfa_warp_aggregate. */
 int mega_fgfa_warp_aggregate_ring_pos(const void* feats, const float* flow, void* out, float* weights_out, int T, int H,
                                       int W, int Cf, int Ce, const int* order, int key_pos, int dtype, void* stream);
 /* ... for G key frames in one launch: order [G][1 + T], flow [G][T][2][H][W], out [G][H][W][Cf], weights_out [G][T][H][W] or

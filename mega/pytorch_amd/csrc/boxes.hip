@@ -783,12 +783,12 @@ extern "C" int mega_nms_sorted(const float* boxes, const int* counts, const unsi
   if (ws_bytes < mega_nms_workspace_bytes(P, nmax)) return MEGA_ERR_WS;
   hipStream_t st = (hipStream_t)stream;
   const int cb = cdiv(nmax, 64);
-  static const int lazy_min = getenv("MEGA_NMS_LAZY_MIN") ? atoi(getenv("MEGA_NMS_LAZY_MIN")) : 1024;
+  constexpr int kNmsLazyMin = 1024;
   // Lazy form: one block per problem walks the sorted list and evaluates only the kept boxes' rows, stopping at
   // max_keep -- it pays when few boxes are kept out of many (the RPN: 300 of 6000) or the list is long; many small
   // problems that keep everything (post-processing with R = 1024: 30 classes x B images, max_keep = R) are better
   // served by the mask + scan pair, whose work is spread over nmax^2 / 4096 blocks per problem.
-  if (nmax >= lazy_min && (4 * max_keep <= nmax || nmax > 2048)) {
+  if (nmax >= kNmsLazyMin && (4 * max_keep <= nmax || nmax > 2048)) {
     const size_t lds = (((size_t)nmax * 17 + 15) & ~(size_t)15) + (size_t)nmax * 2 + 16;
     if (hipFuncSetAttribute((const void*)nms_lazy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return MEGA_ERR_LAUNCH;

@@ -21,7 +21,6 @@
 //                       f32 -> mfma_32x32x2_f32 (exact f32, parity mode).  The key range can be split over
 //                       blockIdx.z (a call has only Nq/128 * 16 blocks for 256 CUs); partial (m, l, O) are then
 //                       merged by attn_combine_kernel.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -143,11 +142,7 @@ __global__ __launch_bounds__(256) void pos_logits_mfma_kernel(const float4* __re
                                                               const float* __restrict__ wgt,
                                                               const float* __restrict__ bg,
                                                               const float* __restrict__ dim_mat,
-                                                              float* __restrict__ out, bf16_t* __restrict__ out_t,
-                                                              int Nq, int Nk, int ldp) {
-  // out_t != null: logits as bf16 in the attention kernel's own order, [16][ceil(Nk/32)][Nq][32] where the 32 keys of
-  // a tile are stored (h2, rq, e) with key = 8 rq + 4 h2 + e -- the 16 keys one attention lane consumes per tile are
-  // 32 contiguous bytes and a wave's read is one contiguous 2 KiB block.
+                                                              float* __restrict__ out, int Nq, int Nk, int ldp) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = lane & 15, g = lane >> 4;          // pair within the tile / k-group (A, B);  head = row (B, D)
   const int q = blockIdx.y;
@@ -194,22 +189,15 @@ __global__ __launch_bounds__(256) void pos_logits_mfma_kernel(const float4* __re
     float4 o;
     o.x = fast_log(fmaxf(acc[0], 0.f) + 1e-6f); o.y = fast_log(fmaxf(acc[1], 0.f) + 1e-6f);
     o.z = fast_log(fmaxf(acc[2], 0.f) + 1e-6f); o.w = fast_log(fmaxf(acc[3], 0.f) + 1e-6f);
-    if (out_t) {
-      const int kf = k0 + 4 * g, kt = kf >> 5, kk = kf & 31;
-      bf16_t* dst = out_t + (((size_t)row * ((Nk + 31) >> 5) + kt) * Nq + q) * 32 + ((kk >> 2) & 1) * 16 + (kk >> 3) * 4;
-      uint2 pk;
-      pk.x = (unsigned)f32_to_bf16(o.x) | ((unsigned)f32_to_bf16(o.y) << 16);
-      pk.y = (unsigned)f32_to_bf16(o.z) | ((unsigned)f32_to_bf16(o.w) << 16);
-      *reinterpret_cast<uint2*>(dst) = pk;
-    } else {
-      float* dst = out + ((size_t)row * Nq + q) * ldp + k0 + 4 * g;
-      if (k0 + 4 * g + 3 < ldp) *reinterpret_cast<float4*>(dst) = o;    // ldp % 4 == 0: pad columns may be written
-    }
+    float* dst = out + ((size_t)row * Nq + q) * ldp + k0 + 4 * g;
+    if (k0 + 4 * g + 3 < ldp) *reinterpret_cast<float4*>(dst) = o;    // ldp % 4 == 0: pad columns may be written
   }
 }
 
-// Tiled-bf16 variant with coalesced output.  The tile-ordered logits [16][ceil(Nk/32)][Nq][32] are contiguous over q
-// for a fixed (head, key tile): a block therefore owns 8 consecutive queries x 64 keys (two key tiles), computes its
+// Tiled 16-bit variant with coalesced output: the logits in the attention kernel's own order, [16][ceil(Nk/32)][Nq][32]
+// where the 32 keys of a tile are stored (h2, rq, e) with key = 8 rq + 4 h2 + e -- the 16 keys one attention lane consumes
+// per tile are 32 contiguous bytes and a wave's read is one contiguous 2 KiB block.  They are contiguous over q for a
+// fixed (head, key tile): a block therefore owns 8 consecutive queries x 64 keys (two key tiles), computes its
 // 512 pairs as 32 MFMA tiles (8 per wave, same operand layout as pos_logits_mfma_kernel), stages the 16 KiB of bf16
 // logits in LDS in their final order and writes 32 runs of 512 contiguous bytes (16 B per lane) instead of 8-byte
 // pieces scattered over 16 head planes.  Each lane needs only the sine OR the cosine of its 16 arguments:
@@ -389,7 +377,7 @@ struct AttnParams {
   const void* K2;             // [Nk-N1][ldk]  keys N1 .. Nk-1 (second segment; unused when N1 == Nk)
   const void* Vt2;            // [G*64][ldv2]  keys N1 .. Nk-1; its columns may start at any 2-byte (bf16) / 4-byte (f32) address
   const float* pos;           // [G][Nq][ldp] additive logits or null
-  const unsigned short* pos_t;   // or: 16-bit (T) logits in tile order [G][ceil(Nk/32)][Nq][32] (see pos_logits_mfma_kernel)
+  const unsigned short* pos_t;   // or: 16-bit (T) logits in tile order [G][ceil(Nk/32)][Nq][32] (see pos_logits_tiled_body)
   const void* resid;          // [Nq][ldr] residual (feats_cur) or null
   const float* bias_v;        // [G*64] or null
   void* out;                  // [Nq][ldo]
@@ -399,7 +387,6 @@ struct AttnParams {
   int Nq, Nk, N1, G;
   float scale;
   int nsplit, tiles_per_split;
-  int vmask_always;           // experiments: mask the V^T tail in every tile (the pre-round-3 form) instead of the last one
   int io_f32;                 // resid / out are f32 rows whatever T is (the head's f32 activation stream in bf16 mode)
 };
 
@@ -500,7 +487,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const int split) 
           }
         }
         uint4 v = make_uint4(r.x, r.y, r.z, r.w);
-        if (p.vmask_always || k0 + 32 > p.Nk) {   // only a tile that reaches past Nk has tail keys (wave-uniform branch):
+        if (k0 + 32 > p.Nk) {                     // only a tile that reaches past Nk has tail keys (wave-uniform branch):
           T* e = reinterpret_cast<T*>(&v);         // zero them (pad columns of Vt are not guaranteed finite)
 #pragma unroll
           for (int t = 0; t < VE; ++t) e[t] = (key + t < p.Nk) ? e[t] : (T)0;
@@ -757,10 +744,10 @@ struct AttnBatch {
 };
 static_assert(sizeof(AttnBatch) <= 4096, "AttnBatch travels as the kernel argument");
 
-// MINB = blocks per CU the register allocation aims at: 2 or 3 (<= 168 VGPRs: three waves per SIMD; default since the
-// second key segment, see mega_relation_attention_batched; MEGA_ATTN_OCC3=0 selects the 2-block bound).
-template <typename T, bool POS_TILED, int MINB, bool SEG>
-__global__ __launch_bounds__(256, MINB) void attn_batched_kernel(AttnBatch b) {
+// Blocks per CU the register allocation aims at: 3 (<= 168 VGPRs: three waves per SIMD) for the two-segment build with
+// the tiled position term, 2 for every other one; see mega_relation_attention_batched for the VGPR figures.
+template <typename T, bool POS_TILED, bool SEG>
+__global__ __launch_bounds__(256, (POS_TILED && SEG) ? 3 : 2) void attn_batched_kernel(AttnBatch b) {
   const int z = blockIdx.z;
   const AttnParams& p = b.p[b.zprob[z]];
   if ((int)blockIdx.x * 128 >= p.Nq) return;          // (block-uniform: the grid is sized for the largest problem)
@@ -824,55 +811,43 @@ extern "C" int mega_position_logits(const float* rois_q, const float* rois_k, co
                        (const float4*)rois_k, wg_t, bg, dim_mat, out, Nq, Nk, ldp);
   else if (ldp % 4 == 0 && (reinterpret_cast<size_t>(out) & 15) == 0)
     hipLaunchKernelGGL(pos_logits_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, out, (bf16_t*)nullptr, Nq, Nk, ldp);
+                       (const float4*)rois_k, wg_t, bg, dim_mat, out, Nq, Nk, ldp);
   else
     hipLaunchKernelGGL((pos_logits_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
                        (const float4*)rois_k, wg_t, bg, dim_mat, out, Nq, Nk, ldp);
   return mega_check_launch();
 }
 
-static int position_logits_tiled_impl(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
-                                      const float* dim_mat, void* out_bf16, int Nq, int Nk, int dtype, void* stream) {
-  mega_clear_error();
-  if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
-  if (Nq == 0 || Nk == 0) return MEGA_OK;
-  if (!rois_q || !rois_k || !wg_t || !bg || !dim_mat || !out_bf16 || Nq < 0 || Nk < 0 ||
-      (reinterpret_cast<size_t>(out_bf16) & 15))
-    return MEGA_ERR_ARG;
-  static const bool legacy = getenv("MEGA_POS_LEGACY") != nullptr;     // A/B switch (experiments)
-  if (dtype == MEGA_F16) {
-    dim3 grid(cdiv(Nk, 64), cdiv(Nq, 8));
-    hipLaunchKernelGGL(pos_logits_tiled_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out_bf16, Nq, Nk);
-  } else if (legacy) {
-    dim3 grid(cdiv(Nk, 256), Nq);
-    hipLaunchKernelGGL(pos_logits_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, (float*)nullptr, (bf16_t*)out_bf16, Nq, Nk, 0);
-  } else {
-    dim3 grid(cdiv(Nk, 64), cdiv(Nq, 8));
-    hipLaunchKernelGGL(pos_logits_tiled_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out_bf16, Nq, Nk);
-  }
-  return mega_check_launch();
-}
-
 // round 6: the tile-ordered logits in the head's 16-bit operand type (dtype = MEGA_BF16 / MEGA_F16)
 extern "C" int mega_position_logits_tiled_dt(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
                                              const float* dim_mat, void* out16, int Nq, int Nk, int dtype, void* stream) {
-  return position_logits_tiled_impl(rois_q, rois_k, wg_t, bg, dim_mat, out16, Nq, Nk, dtype, stream);
+  mega_clear_error();
+  if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
+  if (Nq == 0 || Nk == 0) return MEGA_OK;
+  if (!rois_q || !rois_k || !wg_t || !bg || !dim_mat || !out16 || Nq < 0 || Nk < 0 || (reinterpret_cast<size_t>(out16) & 15))
+    return MEGA_ERR_ARG;
+  dim3 grid(cdiv(Nk, 64), cdiv(Nq, 8));
+  if (dtype == MEGA_F16)
+    hipLaunchKernelGGL(pos_logits_tiled_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
+                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out16, Nq, Nk);
+  else
+    hipLaunchKernelGGL(pos_logits_tiled_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
+                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out16, Nq, Nk);
+  return mega_check_launch();
 }
 
 // Number of key-range splits the attention core uses for (Nq, Nk) -- a function of the problem alone, so a problem
 // gets the same bits in a single launch and inside a batched launch.  The engine batches 10-20 problems per launch
-// (>= 480 blocks without any split), so a problem only asks for MEGA_ATTN_BLOCKS = 48 blocks of its own: no MEGA shape
+// (>= 480 blocks without any split), so a problem only asks for kAttnTargetBlocks = 48 blocks of its own: no MEGA shape
 // (Nq >= 300: 3 x 16 blocks) splits any more, and the partial-sum round trip + combine launch (0.21 ms per 10 key
 // frames, +1.3 % FPS measured with the splits off) disappears.  Round 1 used 768 for single launches, round 2 256.
+constexpr int kAttnTargetBlocks = 48;
+
 extern "C" int mega_relation_attention_splits(int Nq, int Nk, int groups) {
   if (Nq <= 0 || Nk <= 0 || groups <= 0) return 1;
-  static const int target = getenv("MEGA_ATTN_BLOCKS") ? atoi(getenv("MEGA_ATTN_BLOCKS")) : 48;
   const int blocks = cdiv(Nq, 128) * groups;
   const int ntiles = cdiv(Nk, 32);
-  int s = cdiv(target, blocks);
+  int s = cdiv(kAttnTargetBlocks, blocks);
   if (s > ntiles / 4) s = ntiles / 4;
   if (s > 16) s = 16;
   return s < 1 ? 1 : s;
@@ -910,8 +885,6 @@ static int attn_fill(AttnParams& p, const void* q, int ldq, const void* k, int l
   if (nsplit > 1 && (!ws || ws_bytes < mega_relation_attention_workspace_bytes(Nq, Nk, groups))) nsplit = 1;
   const int ntiles = cdiv(Nk, 32);
   p.tiles_per_split = cdiv(ntiles, nsplit);
-  static const int vmask_always = (getenv("MEGA_ATTN_VMASK_ALWAYS") && getenv("MEGA_ATTN_VMASK_ALWAYS")[0] == '1') ? 1 : 0;
-  p.vmask_always = vmask_always;      // (experiments; read once: not on the per-launch path)
   nsplit = cdiv(ntiles, p.tiles_per_split);   // no empty splits
   p.nsplit = nsplit;
   p.part_o = (float*)ws;
@@ -988,29 +961,22 @@ extern "C" int mega_relation_attention_batched(const void* descs, int n, int gro
   b.nz = nz;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(cdiv(max_q, 128), groups, nz);
-  // (three blocks per CU: with the second key segment the tiled-position variant needs 170 VGPRs under a 2-block bound -- two
-  //  over the 168 that still fit three waves per SIMD -- and exactly 168, without spills, under a 3-block bound)
   // Builds: SEG = some problem of the launch has a second key segment (the seam code costs the one-segment launches 5 %:
-  // they keep their own build); MINB = blocks per CU the register allocation aims at -- the two-segment tiled-position
-  // variant needs 170 VGPRs under a 2-block bound, two over the 168 that still fit three waves per SIMD, and exactly 168,
-  // without spills, under a 3-block bound (886 against 1020 us at stage 0); every other variant fits 166 under the 2-block
-  // bound and is 4 % faster that way.  MEGA_ATTN_OCC3 = 0 / 1 forces the bound for all variants (A/B).
-  static const int occ_env = getenv("MEGA_ATTN_OCC3") == nullptr ? -1 : (getenv("MEGA_ATTN_OCC3")[0] == '1' ? 1 : 0);
-  const bool occ3 = occ_env >= 0 ? occ_env == 1 : (any_seg && tiled);
-#define MEGA_ATTN_LAUNCH(T, TILED)                                                                                   \
-  do {                                                                                                               \
-    if (any_seg && occ3) hipLaunchKernelGGL((attn_batched_kernel<T, TILED, 3, true>), grid, dim3(256), 0, st, b);    \
-    else if (any_seg) hipLaunchKernelGGL((attn_batched_kernel<T, TILED, 2, true>), grid, dim3(256), 0, st, b);       \
-    else if (occ3) hipLaunchKernelGGL((attn_batched_kernel<T, TILED, 3, false>), grid, dim3(256), 0, st, b);         \
-    else hipLaunchKernelGGL((attn_batched_kernel<T, TILED, 2, false>), grid, dim3(256), 0, st, b);                   \
+  // they keep their own build).  The two-segment tiled-position build is compiled for three blocks per CU, every other one
+  // for two (attn_batched_kernel's launch bounds): it needs 170 VGPRs under a 2-block bound, two over the 168 that still
+  // fit three waves per SIMD, and exactly 168, without spills, under a 3-block bound (886 against 1020 us at stage 0);
+  // every other variant fits 166 under the 2-block bound and is 4 % faster that way.
+#define MEGA_ATTN_LAUNCH(T, TILED)                                                                              \
+  do {                                                                                                          \
+    if (any_seg) hipLaunchKernelGGL((attn_batched_kernel<T, TILED, true>), grid, dim3(256), 0, st, b);          \
+    else hipLaunchKernelGGL((attn_batched_kernel<T, TILED, false>), grid, dim3(256), 0, st, b);                 \
   } while (0)
   if (dtype == MEGA_BF16 && tiled) MEGA_ATTN_LAUNCH(bf16_t, true);
   else if (dtype == MEGA_BF16) MEGA_ATTN_LAUNCH(bf16_t, false);
   else if (dtype == MEGA_F16 && tiled) MEGA_ATTN_LAUNCH(f16_t, true);
   else if (dtype == MEGA_F16) MEGA_ATTN_LAUNCH(f16_t, false);
-  else if (dtype == MEGA_F32 && any_seg) hipLaunchKernelGGL((attn_batched_kernel<float, false, 2, true>), grid, dim3(256), 0, st, b);
-  else if (dtype == MEGA_F32) hipLaunchKernelGGL((attn_batched_kernel<float, false, 2, false>), grid, dim3(256), 0, st, b);
-#undef MEGA_ATTN_LAUNCH      // (f32: 192 / 211 VGPRs, two blocks per CU either way; a 3-block bound would spill)
+  else if (dtype == MEGA_F32) MEGA_ATTN_LAUNCH(float, false);      // (f32: 192 / 211 VGPRs, two blocks per CU)
+#undef MEGA_ATTN_LAUNCH
   else return MEGA_ERR_ARG;
   if (any_split) {
     const int blocks = (int)((max_total + 255) / 256 > 4096 ? 4096 : (max_total + 255) / 256);
@@ -1023,8 +989,8 @@ extern "C" int mega_relation_attention_batched(const void* descs, int n, int gro
 
 struct MegaPosDescC { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; };
 
-static int position_logits_tiled_batched_impl(const void* descs, int n, const float* wg_t, const float* bg,
-                                              const float* dim_mat, int dtype, void* stream) {
+extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
+                                                     const float* dim_mat, int dtype, void* stream) {
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (n == 0) return MEGA_OK;
@@ -1045,11 +1011,6 @@ static int position_logits_tiled_batched_impl(const void* descs, int n, const fl
   if (dtype == MEGA_F16) hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
   else hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
   return mega_check_launch();
-}
-
-extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
-                                                     const float* dim_mat, int dtype, void* stream) {
-  return position_logits_tiled_batched_impl(descs, n, wg_t, bg, dim_mat, dtype, stream);
 }
 
 extern "C" int mega_relation_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,

@@ -4,8 +4,6 @@
 //   * ROIAlign forward                                           (mega_core/csrc/cuda/ROIAlign_cuda.cu:15-122,
 //                                                                 csrc/cpu/ROIAlign_cpu.cpp:18-219)
 // Activations are NHWC so that a pixel's channels are one contiguous, coalesced run.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace {
@@ -899,30 +897,27 @@ extern "C" int mega_roi_align_fwd(const void* feat, const float* rois, void* out
   if (in_nhwc && out_nhwc && dtype == out_dtype && C % (dtype != MEGA_F32 ? 8 : 4) == 0) {
     const int CV = C / (dtype != MEGA_F32 ? 8 : 4);
     const long long total = (long long)K * pooled_h * pooled_w * CV;
-    static const bool no_slice = getenv("MEGA_ROI_NO_XCD_SLICE") != nullptr;       // A/B switch (experiments)
-    const bool sliced = !no_slice && CV % 8 == 0 && CV / 8 >= 16 && total / 8 >= 256 * 64;
+    const bool xcd_slices = CV % 8 == 0 && CV / 8 >= 16;         // >= 16 channel vectors for each of the 8 XCDs
+    const bool sliced = xcd_slices && total / 8 >= 256 * 64;
     long long nb = ((sliced ? total / 8 : total) + 255) / 256;
     if (nb > 131072) nb = 131072;
     dim3 vgrid((unsigned)(sliced ? nb * 8 : nb));
-    static const bool no_sep = getenv("MEGA_ROI_NO_SEPARABLE") != nullptr;         // A/B switch (experiments)
-    // the separable per-ROI form: adaptive grid only (sampling_ratio > 0 spreads a bin's samples over a sparse patch);
-    // ROIs whose patch exceeds its tables fall back inside the kernel, so no bound on the boxes is assumed here
-    if (dtype == MEGA_F16 && !no_sep && sampling_ratio <= 0 && pooled_w <= RS_MAXPW && pooled_h <= RS_MAXPW) {
-      if (!no_slice && CV % 8 == 0 && CV / 8 >= 16)
-        hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<f16_t, 8>), dim3((unsigned)(K * 8)), dim3(256), 0, st,
-                           (const f16_t*)feat, rois, (f16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
-      else
-        hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<f16_t, 1>), dim3((unsigned)K), dim3(256), 0, st,
-                           (const f16_t*)feat, rois, (f16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
-      return mega_check_launch();
-    }
-    if (dtype == MEGA_BF16 && !no_sep && sampling_ratio <= 0 && pooled_w <= RS_MAXPW && pooled_h <= RS_MAXPW) {
-      if (!no_slice && CV % 8 == 0 && CV / 8 >= 16)
-        hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<bf16_t, 8>), dim3((unsigned)(K * 8)), dim3(256), 0, st,
-                           (const bf16_t*)feat, rois, (bf16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
-      else
-        hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<bf16_t, 1>), dim3((unsigned)K), dim3(256), 0, st,
-                           (const bf16_t*)feat, rois, (bf16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
+    // the separable per-ROI form: 16-bit types, adaptive grid only (sampling_ratio > 0 spreads a bin's samples over a sparse
+    // patch); ROIs whose patch exceeds its tables fall back inside the kernel, so no bound on the boxes is assumed here
+    const bool separable = (dtype == MEGA_F16 || dtype == MEGA_BF16) && sampling_ratio <= 0 && pooled_w <= RS_MAXPW &&
+                           pooled_h <= RS_MAXPW;
+    if (separable) {
+      auto launch_sep = [&](auto elem) {
+        using T = decltype(elem);
+        if (xcd_slices)
+          hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<T, 8>), dim3((unsigned)(K * 8)), dim3(256), 0, st, (const T*)feat,
+                             rois, (T*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
+        else
+          hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<T, 1>), dim3((unsigned)K), dim3(256), 0, st, (const T*)feat, rois,
+                             (T*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
+      };
+      if (dtype == MEGA_F16) launch_sep(f16_t{});
+      else launch_sep(bf16_t{});
       return mega_check_launch();
     }
     if (dtype == MEGA_BF16 && sliced)
@@ -1030,9 +1025,9 @@ extern "C" int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois
   dim3 vgrid((unsigned)(sliced ? nb * 8 : nb));
   hipStream_t st = (hipStream_t)stream;
   // the separable per-ROI form (adaptive grid, one block per ROI x XCD channel slice), as the 16-bit kernels: the sums differ
-  // from the exact-term-order kernel at f32 round-off (~1e-7 relative); MEGA_ROI_NO_SEPARABLE=1 keeps the latter
-  static const bool no_sep = getenv("MEGA_ROI_NO_SEPARABLE") != nullptr;
-  if (!no_sep && sliced && sampling_ratio <= 0 && pooled_w <= RS_MAXPW && pooled_h <= RS_MAXPW) {
+  // from the exact-term-order kernel at f32 round-off (~1e-7 relative)
+  const bool separable = sliced && sampling_ratio <= 0 && pooled_w <= RS_MAXPW && pooled_h <= RS_MAXPW;
+  if (separable) {
     if (dtype == MEGA_F16)
       hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<float, 8, true, f16_t>), dim3((unsigned)(K * 8)), dim3(256), 0, st, feat, rois,
                          (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);

@@ -474,7 +474,7 @@ def roi_align_planes(feat, rois, spatial_scale, pooled, sampling_ratio, dtype=to
     """roi_align on f32 NHWC features, the pooled rows as split-precision planes: -> Planes [K, ph*pw*C] (t = bf16 / f16
     [K, 2*ph*pw*C]), without the f32 tensor in between.  Large launches (C / 4 a multiple of 8 channel vectors, adaptive grid) run
     the separable per-ROI form of the 16-bit kernels: split_planes(roi_align(...)) to f32 round-off; small ones the
-    exact-term-order kernel: bit for bit (MEGA_ROI_NO_SEPARABLE=1: always)."""
+    exact-term-order kernel: bit for bit."""
     _gpu(feat, rois)
     lib = _lib.load()
     B, H, W, C = feat.shape
@@ -1277,19 +1277,22 @@ def dff_warp_scale(feats, flow, scale):
     return out
 
 
-def fgfa_warp_aggregate(feats, flow, Cf, key, want_weights=False, order=None, flow_pos=None):
+def fgfa_warp_aggregate(feats, flow, Cf, key, want_weights=False, order=None, flow_pos=None, out=None):
     """feats NHWC [T,H,W,Cf+Ce], flow [T,2,H,W] f32 -> aggregated key-frame features [H,W,Cf] (+ weights [T,H,W]).
     order (i32 [1 + T] on the device): feats is a ring of S >= T slots, order[0] = the key frame's slot, order[1 + t] = the
     slot of window position t (`key` is ignored); same bits as the call on the frames in window order.  flow is indexed by
     slot like feats ([S,2,H,W]) or, with flow_pos = the key frame's window position, by window position ([T,2,H,W]: exactly
-    the window's pairs, in window order)."""
-    _gpu(feats, flow, order)
+    the window's pairs, in window order).  out: the result tensor to write ([H,W,Cf], contiguous, of feats' dtype).
+    A shape the kernel cannot take (see include/mega_hip.h) raises the library's "bad argument" error before any launch."""
+    _gpu(feats, flow, order, out)
     lib = _lib.load()
     S, H, W, C = feats.shape
     T = S if order is None else order.numel() - 1
     assert feats.is_contiguous() and flow.is_contiguous() and flow.dtype == torch.float32
     assert flow.shape == ((T if flow_pos is not None else S), 2, H, W) and (flow_pos is None or order is not None)
-    out = torch.empty((H, W, Cf), dtype=feats.dtype, device=feats.device)
+    if out is None:
+        out = torch.empty((H, W, Cf), dtype=feats.dtype, device=feats.device)
+    assert tuple(out.shape) == (H, W, Cf) and out.dtype == feats.dtype and out.is_contiguous()
     wts = torch.empty((T, H, W), dtype=torch.float32, device=feats.device) if want_weights else None
     _tok = _pb("fgfa_warp", 0.0, 4.0 * feats.numel() * feats.element_size())
     if order is not None:

@@ -1,5 +1,7 @@
 """CPU: the C-ABI library loads without a GPU and exports every symbol include/mega_hip.h declares
-(no compute calls here), and the ctypes signature table covers exactly that set."""
+(no compute calls here), the ctypes signature table covers exactly that set, and the library reads no environment
+variable that is not listed here."""
+import glob
 import os
 import re
 
@@ -41,3 +43,28 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.mega_conv2d_nhwc_ks_workspace_bytes(10, 8, 64 * 4, 1, 1) == 0           # one range: no workspace
     assert lib.mega_conv2d_nhwc_ks_workspace_bytes(10, 8, 64 * 4, 1, 3) == 2 * 10 * 8 * 4   # 4 K-tiles in 3 ranges of 2 -> 2 ranges
     assert lib.mega_conv2d_nhwc_ks_workspace_bytes(10, 8, 64 * 4, 1, 100) == 4 * 10 * 8 * 4   # never more ranges than K-tiles
+
+
+# Every MEGA_* environment variable the HIP sources may read.  A kernel switch is a hidden global input: a variable left over
+# in a shell silently changes which kernel runs, so a new one has to be added here on purpose.
+ALLOWED_GETENV = {
+    "MEGA_IGEMM_TILE",            # igemm.hip: forces the conv GEMM tile (tests/test_conv_dispatch.py and the conv tests set it)
+    "MEGA_IGEMM8_ABLATE",         # igemm8.hip, inside #ifdef MEGA_EXPERIMENTS: not in the product build
+    "MEGA_IGEMM8_TIMELINE_OUT",   # igemm8.hip, inside #ifdef MEGA_EXPERIMENTS
+}
+
+
+def test_hip_sources_read_only_the_listed_environment_variables():
+    csrc = os.path.join(ROOT, "mega", "pytorch_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert files
+    found = {}
+    for path in files:
+        src = open(path).read()
+        names = re.findall(r'getenv\s*\(\s*"([^"]*)"', src)
+        # every getenv call must name its variable literally, or this scan would miss it
+        assert len(names) == len(re.findall(r"\bgetenv\b", src)), os.path.basename(path) + ": getenv without a literal name"
+        for n in names:
+            found.setdefault(n, set()).add(os.path.basename(path))
+    extra = {n: sorted(f) for n, f in found.items() if n not in ALLOWED_GETENV}
+    assert not extra, "environment switches not in ALLOWED_GETENV: %r" % extra

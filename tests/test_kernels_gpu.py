@@ -391,6 +391,22 @@ def test_fgfa_warp_aggregate(dev, dtype, shape):
     assert err < (1e-5 if dtype == torch.float32 else 1e-2), err
 
 
+def test_fgfa_warp_aggregate_rejects_unsupported_shape(dev):
+    """A shape the two-pass kernel cannot take is a "bad argument" error before any launch: Cf = 24 in bf16 is 3 channel
+    vectors per pixel and 256 % 3 != 0 (the kernel deals its 256 threads to frame groups of Cf / 8).  The operands are valid
+    device tensors; the output keeps its sentinel."""
+    ops = _ops()
+    T, H, W, Cf, Ce = 3, 4, 5, 24, 8
+    g = torch.Generator().manual_seed(5)
+    feats = torch.randn((T, H, W, Cf + Ce), generator=g).to(torch.bfloat16).to(dev)
+    flow = torch.randn((T, 2, H, W), generator=g).to(dev)
+    out = torch.full((H, W, Cf), -7.0, dtype=torch.bfloat16, device=dev)
+    with pytest.raises(RuntimeError, match="bad argument"):
+        ops.fgfa_warp_aggregate(feats, flow, Cf, 1, out=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), torch.full((H, W, Cf), -7.0, dtype=torch.bfloat16))
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("shape", [(2, 7, 9, 8), (3, 38, 63, 32), (1, 1, 5, 8)])
 def test_avgpool2x2_ceil(dev, dtype, shape):
@@ -701,7 +717,7 @@ def test_igemm8_bit_equal_to_register_staged_tiles(dev):
 
 
 def test_multi_cat_equals_torch_cat(dev):
-    """ops.multi_cat (mega_copy_segments: every concatenation of a call in one launch per copy width) == torch.cat,
+    """ops.multi_cat (mega_copy_segments: every concatenation of a call in one launch) == torch.cat,
     bit for bit: row blocks (16-byte rows), f32 boxes, and 2-byte-aligned V^T column blocks (75 keys = 150 bytes)
     taken as views of wider buffers; empty pieces; more segments than one launch holds."""
     ops = _ops()
