@@ -483,6 +483,23 @@ size_t mega_vid_eval_workspace_bytes(long long N, int C, int R);
 int mega_vid_eval_ap(const unsigned char* match, const double* pred_ignore, const int* gorder, const long long* seg_off,
                      const int* n_pos, int C, int R, long long N, double* ap, void* ws, size_t ws_bytes, void* stream);
 
+/* ImageNet VID proposal recall: the greedy one-to-one matching of
+ * mega_core/data/datasets/evaluation/vid/vid_eval.py:72-119 (eval_proposals_vid), for F frames and nL proposal limits in
+ * one launch, one wave per (frame, limit).  Inputs, flat over frames:
+ *   box [N][4] f32 in the prediction's frame size, off [F+1] i64 (frame f's proposals are off[f] .. off[f+1]), order [N]
+ *   i32: proposal indices, each frame's run in the order the evaluation takes them (objectness descending, equal values by
+ *   ascending position); only the first min(limits[l], off[f+1] - off[f]) of a run are used; ratio [F][2] f32 as for
+ *   mega_vid_eval_match; gt_box [G][4] f32, gt_off [F+1] i64; limits [nL] i32, each <= max_limit <= 1024; max_gt = the
+ *   largest GT count of a frame (<= 4096).
+ * Per (frame, limit), min(proposals, GT boxes) rounds: the live (proposal, GT) pair of largest IoU (boxlist_iou: +1
+ * convention, f32; ties: the lower GT index, then the lower position in the frame's order) is recorded and both are
+ * removed.  A NaN IoU is never chosen.
+ * Outputs, indexed by the GT box's own position in gt_box: gt_overlap [nL][G] f32 (0 for a GT box that is never matched),
+ * gt_prop [nL][G] i32: the matched proposal's position in its frame's order, or -1. */
+int mega_proposal_recall_match(const float* box, const long long* off, const int* order, const float* ratio,
+                               const float* gt_box, const long long* gt_off, const int* limits, int F, int nL, long long N,
+                               long long G, int max_limit, int max_gt, float* gt_overlap, int* gt_prop, void* stream);
+
 /* Seq-NMS video-level rescoring (mega/pytorch_amd/seq_nms.py defines it; the reference has no counterpart).  One
  * workgroup per (video, class) task; per task, until no box is alive: forward DP in f64 over the frames (S = score + the
  * best S of an alive box of the previous frame with IoU > link_iou, arg-max P: smallest position on equal S), the best

@@ -88,6 +88,8 @@ SIGNATURES = {
     "mega_vid_eval_match": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_longlong, c_int] + [c_void_p] * 4),
     "mega_vid_eval_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
     "mega_vid_eval_ap": (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong] + [c_void_p] * 2 + [c_size_t, c_void_p]),
+    "mega_proposal_recall_match": (c_int, [c_void_p] * 7 + [c_int, c_int, c_longlong, c_longlong, c_int, c_int] +
+                                   [c_void_p] * 3),
     "mega_seq_nms_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
     "mega_seq_nms": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int] + [c_void_p] * 4 +
                      [c_size_t, c_void_p]),

@@ -30,6 +30,7 @@ SOURCES = {
     "seq_nms.hip": ["-ffp-contract=off"],     # the f32 IoU in the order seq_nms.py defines
     "bbox_aug.hip": ["-ffp-contract=off"],    # flip / resize of the merged boxes round like BoxList's separate f32 ops
     "overlay.hip": ["-ffp-contract=off"],     # box rescale is one f32 multiply, the score digits one f64 multiply
+    "proposal_recall.hip": ["-ffp-contract=off"],   # rescale + IoU round like the reference's separate f32 torch ops
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -105,6 +105,9 @@ def _mega_cfg(r50):
         "MODEL": {
             "DEVICE": "cuda",
             "META_ARCHITECTURE": "GeneralizedRCNNMEGA",
+            # True: the detector returns the key frame's RPN proposals (field "objectness") instead of detections
+            # (rpn/rpn.py:186-197, roi_heads/roi_heads.py:65); vid_eval.evaluate_proposals scores them
+            "RPN_ONLY": False,
             "BACKBONE": {"CONV_BODY": "R-50-C4" if r50 else "R-101-C4"},
             "RESNETS": {"NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "STRIDE_IN_1X1": True,
                         "TRANS_FUNC": "BottleneckWithFixedBatchNorm", "STEM_FUNC": "StemWithFixedBatchNorm",

@@ -25,7 +25,7 @@ from torch import nn
 from . import ops
 from .modeling import (DETECTION_META_ARCHITECTURES, ROI_BOX_FEATURE_EXTRACTORS, ROI_BOX_PREDICTOR, CombinedROIHeads,
                        PostProcessor, ResNetHead, _Packed, _nhwc, _nchw_view, _pack_conv, build_backbone, build_rpn,
-                       compute_dtype, convert_to_roi_format)
+                       compute_dtype, convert_to_roi_format, rpn_only)
 from .structures import BoxList, to_image_list
 
 
@@ -447,6 +447,8 @@ class GeneralizedRCNNFGFA(nn.Module):
         feats = (_nchw_view(agg.unsqueeze(0)),)
         il = to_image_list(cur)
         proposals, _ = self.rpn(il, feats, None)
+        if rpn_only(self.cfg):                # generalized_rcnn_fgfa.py: `else: result = proposals`
+            return proposals
         _, result, _ = self.roi_heads(feats, proposals, None)
         return result
 
@@ -484,6 +486,8 @@ class GeneralizedRCNN(nn.Module):
         il = type(il)(il.tensors.to(self.device).float(), il.image_sizes)
         features = self.backbone(il.tensors)
         proposals, _ = self.rpn(il, features, None)
+        if rpn_only(self.cfg):                # generalized_rcnn.py:60-61: `else: result = proposals`
+            return proposals
         _, result, _ = self.roi_heads(features, proposals, None)
         return result
 
@@ -533,6 +537,8 @@ class GeneralizedRCNNDFF(nn.Module):
         agg = ops.dff_warp_scale(self.key_feats[0], flow[0].contiguous(), scale[0].contiguous())
         feats = (_nchw_view(agg.unsqueeze(0)),)
         proposals, _ = self.rpn(to_image_list(cur), feats, None)
+        if rpn_only(self.cfg):                # generalized_rcnn_dff.py: `else: result = proposals`
+            return proposals
         _, result, _ = self.roi_heads(feats, proposals, None)
         return result
 
@@ -565,6 +571,7 @@ class _TwoGraphEngine(object):
 
     def __init__(self, model, group, graphs, pipeline, lanes, batch_head):
         self.m = model
+        self.rpn_only = rpn_only(model.cfg)  # MODEL.RPN_ONLY: graph B stops after the proposal selection (_body_b / _body_bb)
         self.group = max(1, int(group))      # frames per graph A
         self.use_graphs = graphs
         self.pipeline = pipeline             # graphs A and B on two streams (see _step); False: one graph on one stream
@@ -605,6 +612,9 @@ class _TwoGraphEngine(object):
         m = self.m
         W, H = size
         feats = (_nchw_view(agg.unsqueeze(0)),)
+        if self.rpn_only:     # the graph ends at the proposals: (boxes [post,4], objectness [post], placeholder, count [1])
+            props, obj, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key")
+            return props[0].contiguous(), obj[0].contiguous(), cnt, cnt
         box = m.roi_heads.box
         fe = box.feature_extractor
         if agg.is_cuda and not ops.profiling() and self.fork_select:
@@ -634,6 +644,9 @@ class _TwoGraphEngine(object):
         W, H = size
         G = aggs.shape[0]
         feats = (_nchw_view(aggs),)
+        if self.rpn_only:     # (boxes [G,post,4], objectness [G,post], placeholder [G], counts [G])
+            props, obj, cnt = m.rpn.propose(_nhwc(feats[0]), W, H, "key")
+            return props, obj, cnt, cnt
         box = m.roi_heads.box
         fe = box.feature_extractor
         if aggs.is_cuda and not ops.profiling():
@@ -752,7 +765,12 @@ class _TwoGraphEngine(object):
             torch.cuda.current_stream().wait_stream(s_)           # (the second halves of the pending frames)
         counts = torch.cat([p[3] for p in pending]).tolist()
         for (ob, os_, ol, _), n in zip(pending, counts):
-            out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), size))
+            if self.rpn_only:
+                bl = BoxList(ob[:int(n)], size, "xyxy")
+                bl.add_field("objectness", os_[:int(n)])
+                out.append(bl)
+            else:
+                out.append(PostProcessor.materialize((ob, os_, ol, None), int(n), size))
         del pending[:]
 
     @torch.no_grad()

@@ -125,6 +125,10 @@ def _bbox_aug_cfg(cfg):
     return cfg if aug is not None and aug.ENABLED else None
 
 
+def _rpn_only(cfg):
+    return bool(getattr(cfg.MODEL, "RPN_ONLY", False))
+
+
 def _video_runner(model, steps_per_batch, seed, engine_kwargs):
     """The engine of compute_on_dataset, built once -> run(src, v): the detections (list of BoxList on the device) of
     video v whose frames come from the feed.FrameSource src.  Every call is a fresh video for the engine, so the views
@@ -132,6 +136,11 @@ def _video_runner(model, steps_per_batch, seed, engine_kwargs):
     method = model.cfg.MODEL.VID.METHOD
     if method == "rdn" and not (engine_kwargs or {}).get("per_frame"):
         method = "mega"
+    if _rpn_only(model.cfg) and method in ("mega", "rdn"):
+        # the key frame's proposals need its own C4 map only (GeneralizedRCNNMEGA.forward_rpn_only): the single-frame engine
+        # has the same backbone and the same "key" selector, and no window to keep
+        method = "base"
+        engine_kwargs = {k: v for k, v in (engine_kwargs or {}).items() if k != "per_frame"}
     if method != "mega":
         ek = dict(engine_kwargs or {})
         per_frame = bool(ek.pop("per_frame", False)) or method not in ("fgfa", "dff", "base")
@@ -181,6 +190,8 @@ def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_bat
                    graphs, pipeline, group / interval, lanes); engine_kwargs={"per_frame": True} runs the reference's call
                    convention instead;
       (per_frame)  the detector frame by frame on the reference's own test feed (frame_feed).
+    With MODEL.RPN_ONLY the BoxLists are the key frames' proposals (field "objectness"); mega / rdn then run through
+    BaseClipEngine, ClipEngine is not used.
     bbox_aug_cfg: a config whose TEST.BBOX_AUG.ENABLED is set (default: the model's own config, if set there): test-time
     box augmentation of every video (bbox_aug.py) with that config's views, each view a pass through the same engine."""
     model.eval()
@@ -304,8 +315,16 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     seq_nms: None (off), True or a dict of seq_nms.seq_nms's link_iou / nms_iou / rescore: Seq-NMS over all videos on
     the main process after the gather.  predictions.pth stays the raw list; the rescored one goes to
     predictions_seq_nms.pth and its evaluation to result_seq_nms.txt (result.txt stays the raw evaluation); the return
-    value is then the rescored list."""
+    value is then the rescored list.
+    cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
+    (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
+    Seq-NMS and TEST.BBOX_AUG work on detections: combined with RPN_ONLY they are a ValueError."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
+    box_only = _rpn_only(cfg)
+    if box_only and seq_nms is not None and seq_nms is not False:
+        raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")
+    if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
+        raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
     device = torch.device(cfg.MODEL.DEVICE if device is None else device)
     dist = torch.distributed
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -341,6 +360,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if isinstance(motion_iou, str):
             motion_iou = vid_eval.load_motion_iou(motion_iou)
         gt = vid_eval.VIDGroundTruth(img_index, anno_path)
+        if box_only:
+            vid_eval.evaluate_proposals(predictions, gt, output_folder=output_folder, device=device, logger=logger)
+            return predictions
         vid_eval.evaluate_detections(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                      logger=logger)
         if rescored is not None:

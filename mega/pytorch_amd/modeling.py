@@ -573,6 +573,14 @@ class RPNWithRefModule(nn.Module):
         return (boxes, {}) if version == "key" else boxes
 
 
+def rpn_only(cfg):
+    """MODEL.RPN_ONLY: the detectors return the key frame's proposals (rpn/rpn.py:186-197; the `else: result = proposals`
+    branch of every generalized_rcnn*.py).  The proposals come back in the RPN's keep order, which is descending
+    objectness already (the reference re-sorts them, rpn.py:193-196).  roi_heads is still built, so state_dict keys and
+    strict checkpoint loading do not change; its weights are packed lazily, so nothing is paid for it."""
+    return bool(getattr(cfg.MODEL, "RPN_ONLY", False))
+
+
 def build_rpn(cfg, in_channels):
     """rpn/rpn.py:246-262: METHOD 'mega' -> RPNWithRefModule."""
     # "mega" -> RPNWithRefModule; "fgfa" / "base" use the plain RPNModule in the reference, which is the "key" path
@@ -1667,16 +1675,33 @@ class GeneralizedRCNNMEGA(nn.Module):
             outs = shard.gather_detections(outs, len(frames), pp.detections_per_img, frames[0]["rois_key"].device)
         return outs
 
+    @torch.no_grad()
+    def forward_rpn_only(self, cur):
+        """MODEL.RPN_ONLY: the key frame's proposals.  The reference computes them from the key frame's own C4 map alone,
+        through the "key" selector (generalized_rcnn_mega.py:210-211: feats = self.feats[key_frame_location]; self.rpn(imgs,
+        (feats,), None); generalized_rcnn_rdn.py does the same), and the key frame is images["cur"]: so this is backbone ->
+        rpn(version="key") on that frame, with no window, global-pool or memory upkeep -- none of it reaches the result
+        (:220-223, `else: result = proposals`)."""
+        H, W = cur.shape[-2:]
+        a = self.frame_stage_a1(self.frame_stage_a0(cur.float()), W, H)
+        n = int(a["cnt"][0].item())
+        bl = BoxList(a["props"][0, :n], (W, H), "xyxy")
+        bl.add_field("objectness", a["scores"][0, :n])
+        return [bl]
+
     def forward(self, images, targets=None):
         """Reference call convention (generalized_rcnn_mega.py:48-78, data/datasets/vid_mega.py:95-142):
         images = {"cur", "ref_l": [frame t+MAX_OFFSET], "ref_g": [...], "frame_category", "seg_len", "pattern",
         "img_dir", "transforms"}.  Extension: "ref_l_init" may hold the preprocessed frames 1..12 needed at
-        frame_category 0, which replaces the PIL read inside forward (:185-191)."""
+        frame_category 0, which replaces the PIL read inside forward (:185-191).
+        With MODEL.RPN_ONLY: [the key frame's proposals] (forward_rpn_only)."""
         if targets is not None:
             raise ValueError("In testing mode, targets should be None")
         if self.training:
             raise NotImplementedError("inference path only (training is out of scope)")
         cur = to_image_list(images["cur"]).tensors.to(self.device)
+        if rpn_only(self.cfg):
+            return self.forward_rpn_only(cur)
         H, W = cur.shape[-2:]
         ref_g = [to_image_list(g).tensors.to(self.device) for g in images.get("ref_g", [])] if self.global_enable else []
         new_local = None

@@ -1415,6 +1415,31 @@ def vid_eval_ap(match, pred_ignore, gorder, seg_off, n_pos):
     return ap
 
 
+def proposal_recall_match(box, off, order, ratio, gt_box, gt_off, limits, max_limit, max_gt):
+    """eval_proposals_vid's greedy matching (vid_eval.py:72-119) for F frames and nL limits in one launch
+    (include/mega_hip.h mega_proposal_recall_match).  box [N,4] f32, off [F+1] i64, order [N] i32 (each frame's run in
+    evaluation order), ratio [F,2] f32, gt_box [G,4] f32, gt_off [F+1] i64, limits [nL] i32 (each <= max_limit <= 1024).
+    -> gt_overlap [nL,G] f32, gt_prop [nL,G] i32 (position in the frame's order, -1: unmatched), on the device."""
+    _gpu(box, off, order, ratio, gt_box, gt_off, limits)
+    lib = _lib.load()
+    N, F, G, nL = box.shape[0], off.shape[0] - 1, gt_box.shape[0], limits.shape[0]
+    for t, dt in ((box, torch.float32), (off, torch.int64), (order, torch.int32), (ratio, torch.float32),
+                  (gt_box, torch.float32), (gt_off, torch.int64), (limits, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert box.shape == (N, 4) and order.shape == (N,) and ratio.shape == (F, 2) and gt_box.shape == (G, 4)
+    assert gt_off.shape == (F + 1,)
+    dev = box.device
+    gt_overlap = torch.empty((nL, G), dtype=torch.float32, device=dev)
+    gt_prop = torch.empty((nL, G), dtype=torch.int32, device=dev)
+    _tok = _pb("proposal_recall_match")
+    rc = lib.mega_proposal_recall_match(_ptr(box), _ptr(off), _ptr(order), _ptr(ratio), _ptr(gt_box), _ptr(gt_off),
+                                        _ptr(limits), F, nL, N, G, int(max_limit), int(max_gt), _ptr(gt_overlap),
+                                        _ptr(gt_prop), _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_proposal_recall_match")
+    return gt_overlap, gt_prop
+
+
 # ------------------------------------------------------------------------------------------------ Seq-NMS
 def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     """Seq-NMS over T (video, class) tasks (include/mega_hip.h mega_seq_nms).  box [N,4] f32, score [N] f32 sorted class-

@@ -18,7 +18,14 @@ What is defined here where the reference leaves it to the platform:
     (vid_eval.py:133-137) fails on numpy >= 1.24.
   - empty_weight (the pred_ignore of a detection whose class has no GT box in its frame) is, as in the reference, the
     fraction of ALL entries of the motion file inside the range, even when fewer frames are evaluated.
-Not provided (a clear error): box_only proposal recall (eval_proposals_vid) and the VOC07 11-point metric.
+  - PROPOSAL ORDER ON TIES (evaluate_proposals).  The reference orders a frame's proposals with torch's
+    sort(descending=True), which is not stable.  Here they are ordered by descending objectness and equal values keep
+    their ASCENDING position in the prediction list (a stable descending sort); the RPN's keep order is already that.
+    In the greedy matching, equal IoUs go to the lower GT index, then to the lower proposal position: what torch's CPU
+    max(dim) -- the first maximum -- gives the reference.
+Proposal recall (do_vid_evaluation(box_only=True), eval_proposals_vid, vid_eval.py:26-37 / :72-119) is
+evaluate_proposals(): a third HIP kernel (csrc/proposal_recall.hip), one wave per (frame, proposal limit).
+Not provided (a clear error): the VOC07 11-point metric; evaluate_detections(box_only=True) points to evaluate_proposals.
 There is no CPU path: the matching and the AP reduction run on a HIP device.
 """
 import logging
@@ -55,6 +62,9 @@ CLASSES_TO_IND = dict(zip(CLASSES_MAP, range(len(CLASSES_MAP))))
 MOTION_RANGES = [[0.0, 1.0], [0.0, 0.7], [0.7, 0.9], [0.9, 1.0]]
 MOTION_NAMES = ["all", "fast", "medium", "slow"]
 MAX_GT_PER_FRAME = 4096     # the matching kernel keeps 64 selected flags per lane
+MAX_PROPOSAL_LIMIT = 1024   # the proposal kernel keeps 16 proposals per lane
+PROPOSAL_LIMITS = (10, 50, 100, 300)
+PROPOSAL_IOU_THRESHOLDS = tuple(round(0.5 + 0.05 * i, 2) for i in range(10))
 
 
 def parse_annotation(root, classes_to_ind=CLASSES_TO_IND):
@@ -224,6 +234,14 @@ def device_views(dbuf, layout):
     return t
 
 
+def _resize_ratios(predictions, groundtruth):
+    """[F,2] f32 (width, height): BoxList.resize (bounding_box.py:95) to the annotation's frame size -- ratios as Python
+    floats, applied in f32."""
+    pw = np.asarray([float(p.size[0]) for p in predictions])
+    ph = np.asarray([float(p.size[1]) for p in predictions])
+    return np.stack([groundtruth.width / pw, groundtruth.height / ph], axis=1).astype(np.float32)
+
+
 def _pack(predictions, groundtruth, motion_iou, motion_ranges):
     """Flat host arrays of the whole evaluation, in one byte buffer (one host-to-device copy)."""
     F = len(predictions)
@@ -249,10 +267,7 @@ def _pack(predictions, groundtruth, motion_iou, motion_ranges):
     max_gt = int(gcount.max()) if F else 0
     if max_gt > MAX_GT_PER_FRAME:
         raise ValueError("evaluate_detections: a frame holds %d GT boxes (at most %d)" % (max_gt, MAX_GT_PER_FRAME))
-    # BoxList.resize (bounding_box.py:95): ratios as Python floats, applied in f32
-    pw = np.asarray([float(p.size[0]) for p in predictions])
-    ph = np.asarray([float(p.size[1]) for p in predictions])
-    ratio = np.stack([groundtruth.width / pw, groundtruth.height / ph], axis=1).astype(np.float32)
+    ratio = _resize_ratios(predictions, groundtruth)
     G = int(groundtruth.off[-1])
     motion = None
     if motion_iou is not None:
@@ -336,7 +351,8 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
     result_name: the file the text goes to in output_folder (result_seq_nms.txt for Seq-NMS-rescored predictions).
     -> {motion_index: {"ap": ndarray [n_fg_class] f64 (NaN: class not seen or without non-ignored GT), "map": nanmean}}."""
     if box_only:
-        raise NotImplementedError("box_only proposal recall (eval_proposals_vid) is not provided")
+        raise NotImplementedError("box_only proposal recall (eval_proposals_vid) is not provided by evaluate_detections: "
+                                  "call vid_eval.evaluate_proposals on predictions with the field \"objectness\"")
     if use_07_metric:
         raise NotImplementedError("the VOC07 11-point metric is not provided (the reference hard-codes use_07_metric=False)")
     if torch.device(device).type != "cuda":
@@ -355,3 +371,134 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
         with open(os.path.join(output_folder, result_name), "w") as fid_:
             fid_.write(text)
     return result
+
+
+# ------------------------------------------------------------------------------------------------ proposal recall
+def proposal_inputs(predictions, groundtruth, limits, device="cuda"):
+    """The checked, flat device arrays of ops.proposal_recall_match, in its argument order (one host-to-device copy, the
+    within-frame objectness order sorted on the device) -> (box, off, order, ratio, gt_box, gt_off, limits, max_limit,
+    max_gt)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    limits = [int(l) for l in limits]
+    if not limits or min(limits) < 0:
+        raise ValueError("evaluate_proposals: limits must be non-negative integers, got %r" % (limits,))
+    if max(limits) > MAX_PROPOSAL_LIMIT:
+        raise ValueError("evaluate_proposals: limit %d (at most %d)" % (max(limits), MAX_PROPOSAL_LIMIT))
+    F = len(predictions)
+    if F == 0:
+        raise ValueError("evaluate_proposals: no predictions")
+    if len(groundtruth) != F:
+        raise ValueError("Length of gt and pred lists need to be same (%d predictions, %d GT frames)" % (F, len(groundtruth)))
+    for p in predictions:
+        if not p.has_field("objectness"):
+            raise ValueError("evaluate_proposals: a prediction has no field \"objectness\" (fields: %r); proposals come "
+                             "from a detector run with MODEL.RPN_ONLY True" % (sorted(p.fields()),))
+    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
+    off = np.zeros(F + 1, np.int64)
+    off[1:] = np.cumsum(counts)
+    N = int(off[-1])
+    if N:
+        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
+        obj = torch.cat([p.get_field("objectness").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
+    else:
+        boxes, obj = np.zeros((0, 4), np.float32), np.zeros(0, np.float32)
+    if not np.isfinite(boxes).all():
+        raise ValueError("evaluate_proposals: a proposal box is not finite")
+    if np.isnan(obj).any():
+        raise ValueError("evaluate_proposals: an objectness value is NaN")
+    if not np.isfinite(groundtruth.boxes).all():
+        raise ValueError("evaluate_proposals: a GT box is not finite")
+    gcount = np.diff(groundtruth.off)
+    max_gt = int(gcount.max())
+    if max_gt > MAX_GT_PER_FRAME:
+        raise ValueError("evaluate_proposals: a frame holds %d GT boxes (at most %d)" % (max_gt, MAX_GT_PER_FRAME))
+    buf, layout = one_buffer([("box", boxes), ("obj", (obj + np.float32(0)).astype(np.float32)),       # -0 -> +0
+                              ("off", off), ("ratio", _resize_ratios(predictions, groundtruth)),
+                              ("gt_box", groundtruth.boxes), ("gt_off", groundtruth.off),
+                              ("limits", np.asarray(limits, np.int32))])
+    t = device_views(torch.from_numpy(buf).to(dev), layout)
+    if N:
+        # within a frame: objectness descending, equal values by ascending position
+        perm = torch.sort(t["obj"], descending=True, stable=True).indices
+        fid = torch.repeat_interleave(torch.arange(F, device=dev), torch.from_numpy(counts).to(dev), output_size=N)
+        order = perm[torch.sort(fid[perm], stable=True).indices].int()
+    else:
+        order = torch.zeros(0, dtype=torch.int32, device=dev)
+    return t["box"], t["off"], order, t["ratio"], t["gt_box"], t["gt_off"], t["limits"], max(limits), max_gt
+
+
+def match_proposals(predictions, groundtruth, limits, device="cuda"):
+    """eval_proposals_vid's greedy matching (vid_eval.py:79-111) of every frame, for all `limits` in one kernel launch
+    -> (gt_overlap [nL,G] f32, gt_prop [nL,G] i32) on the device, indexed like groundtruth.boxes: the IoU each GT box was
+    matched with (0: never matched) and the matched proposal's position in its frame's objectness order (-1: none)."""
+    from . import ops
+    args = proposal_inputs(predictions, groundtruth, limits, device)
+    with torch.cuda.device(args[0].device):
+        return ops.proposal_recall_match(*args)
+
+
+def format_recall_table(limits, iou_thresholds, table, ar, num_pos):
+    """The text of proposal_recall_table.txt: one row per proposal limit, AR (the mean over the IoU thresholds) and the
+    recall at each threshold."""
+    s = "Proposal recall, %d GT boxes\n" % num_pos
+    s += "{:>6s} {:>6s}".format("limit", "AR") + "".join(" {:>6s}".format("@%.2f" % t) for t in iou_thresholds) + "\n"
+    for li, lim in enumerate(limits):
+        s += "{:>6d} {:.4f}".format(lim, ar[li]) + "".join(" {:.4f}".format(v) for v in table[li]) + "\n"
+    return s
+
+
+def evaluate_proposals(predictions, groundtruth, iou_thresh=0.5, limit=300, limits=None, iou_thresholds=None,
+                       output_folder=None, device="cuda", logger=None):
+    """do_vid_evaluation(box_only=True) / eval_proposals_vid (vid_eval.py:26-37, :72-119) for `predictions` (list[BoxList]
+    with the field "objectness", boxes in the size each BoxList carries: what inference() returns under MODEL.RPN_ONLY)
+    against `groundtruth` (VIDGroundTruth, same frames, same order): the recall of the GT boxes at IoU >= iou_thresh by
+    each frame's first `limit` proposals, every proposal matched to at most one GT box.  num_pos counts every GT box,
+    those of frames without proposals too; recall = f32(matched) / f32(num_pos) (NaN without GT boxes).
+    "Recall: {:.4f}" goes to the log and to <output_folder>/proposal_result.txt, as the reference writes it.
+    limits / iou_thresholds: when either is given (the other takes PROPOSAL_LIMITS / PROPOSAL_IOU_THRESHOLDS), also the
+    recall table [limit, threshold] and its mean over thresholds (AR) per limit, written to proposal_recall_table.txt;
+    all limits are matched in the same kernel launch.  Thresholds are compared in f32 and must be > 0 (an unmatched GT
+    box has overlap 0).
+    -> {"recall": f32, "num_pos": int, "gt_overlaps": [G] f32, "gt_prop": [G] i32 (by GT box: the IoU it was matched with
+    and the matched proposal's position in the frame's objectness order, 0 / -1 if none)} and, with a table, "limits",
+    "iou_thresholds", "table" [nL,nT] f32, "ar" [nL] f32."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    want_table = limits is not None or iou_thresholds is not None
+    tl = [int(l) for l in (PROPOSAL_LIMITS if limits is None else limits)] if want_table else []
+    tt = [float(t) for t in (PROPOSAL_IOU_THRESHOLDS if iou_thresholds is None else iou_thresholds)] if want_table else []
+    if want_table and (not tl or not tt):
+        raise ValueError("evaluate_proposals: limits and iou_thresholds must not be empty")
+    for t in [float(iou_thresh)] + tt:
+        if not t > 0:
+            raise ValueError("evaluate_proposals: IoU thresholds must be > 0, got %r" % (t,))
+    launch = [int(limit)] + [l for l in tl if l != int(limit)]
+    launch = sorted(set(launch), key=launch.index)
+    ov, prop = match_proposals(predictions, groundtruth, launch, device)
+    num_pos = int(groundtruth.off[-1])
+    thr = torch.tensor([float(iou_thresh)] + tt, dtype=torch.float32, device=ov.device)
+    hits = (ov[:, :, None] >= thr[None, None, :]).sum(dim=1).cpu().numpy()            # [launch, 1 + nT]
+
+    def rec(n):
+        return np.float32(n) / np.float32(num_pos) if num_pos else np.float32(np.nan)
+    out = {"recall": rec(hits[0, 0]), "num_pos": num_pos, "gt_overlaps": ov[0].cpu().numpy(),
+           "gt_prop": prop[0].cpu().numpy()}
+    text = "Recall: {:.4f}".format(out["recall"])
+    log = logger or logging.getLogger("mega.pytorch_amd.vid_eval")
+    log.info(text)
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+        with open(os.path.join(output_folder, "proposal_result.txt"), "w") as fid_:
+            fid_.write(text)
+    if want_table:
+        table = np.asarray([[rec(hits[launch.index(l), 1 + ti]) for ti in range(len(tt))] for l in tl], np.float32)
+        ar = table.mean(axis=1, dtype=np.float32)
+        out.update({"limits": tl, "iou_thresholds": tt, "table": table, "ar": ar})
+        ttext = format_recall_table(tl, tt, table, ar, num_pos)
+        log.info("\n" + ttext)
+        if output_folder:
+            with open(os.path.join(output_folder, "proposal_recall_table.txt"), "w") as fid_:
+                fid_.write(ttext)
+    return out

@@ -10,6 +10,14 @@ folder of predictions.pth); the text is also printed.
 --seq-nms (with --seq-nms-link-iou / --seq-nms-iou / --seq-nms-rescore) also applies Seq-NMS (mega.pytorch_amd.seq_nms)
 over the videos of --img-index, writes predictions_seq_nms.pth and result_seq_nms.txt to the output folder and prints
 that evaluation too.
+
+--box-only evaluates proposals instead (predictions made with MODEL.RPN_ONLY True, field "objectness"): the recall of the
+GT boxes at IoU 0.5 by each frame's first --limit proposals -> proposal_result.txt ("Recall: x", the reference's
+do_vid_evaluation(box_only=True)); --recall-table adds the recall at limits 10 / 50 / 100 / 300 and IoU 0.50 .. 0.95 with
+its mean (AR) -> proposal_recall_table.txt.
+
+  python tools/eval_vid.py --box-only --predictions OUT/predictions.pth --img-index ImageSets/VID_val_videos.txt \\
+      --anno-path Annotations/VID/val [--limit 300] [--recall-table]
 """
 import argparse
 import os
@@ -32,12 +40,25 @@ def main(argv=None):
                     "frames link")
     ap.add_argument("--seq-nms-iou", type=float, default=0.3, help="Seq-NMS: IoU above which a path box suppresses")
     ap.add_argument("--seq-nms-rescore", choices=("avg", "max"), default="avg")
+    ap.add_argument("--box-only", action="store_true", help="proposal recall of RPN-only predictions (proposal_result.txt)")
+    ap.add_argument("--limit", type=int, default=300, help="--box-only: proposals used per frame (at most 1024)")
+    ap.add_argument("--recall-table", action="store_true", help="--box-only: also the recall per limit and IoU threshold")
     a = ap.parse_args(argv)
+    if a.box_only and (a.seq_nms or a.motion_iou):
+        ap.error("--box-only evaluates proposals: --seq-nms / --motion-iou apply to detections")
     from mega.pytorch_amd import inference, vid_eval
     preds = inference.load_predictions(a.predictions)
     gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
     motion = vid_eval.load_motion_iou(a.motion_iou) if a.motion_iou else None
     out = a.output_folder or os.path.dirname(os.path.abspath(a.predictions))
+    if a.box_only:
+        res = vid_eval.evaluate_proposals(preds, gt, limit=a.limit, output_folder=out, device=a.device,
+                                          limits=vid_eval.PROPOSAL_LIMITS if a.recall_table else None)
+        sys.stdout.write("Recall: {:.4f}\n".format(res["recall"]))
+        if a.recall_table:
+            sys.stdout.write(vid_eval.format_recall_table(res["limits"], res["iou_thresholds"], res["table"], res["ar"],
+                                                          res["num_pos"]))
+        return 0
     res = vid_eval.evaluate_detections(preds, gt, motion_iou=motion, output_folder=out, device=a.device)
     sys.stdout.write(vid_eval.format_result(res))
     if a.seq_nms:
