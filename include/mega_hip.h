@@ -195,6 +195,29 @@ int mega_bbox_aug_merge(const float* cboxes, const float* cscores, int F, int K,
                         int max_det, float* out_boxes, float* out_scores, long long* out_labels, int* out_cnt, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* The same merge with another final filter: soft-NMS (TEST.SOFT_NMS) and / or box voting (TEST.BBOX_VOTE), as
+ * mega/pytorch_amd/soft_nms.py defines them.  Inputs, view mapping, row order, outputs and limits are those of
+ * mega_bbox_aug_merge (K <= 16, K * R <= 8192, else MEGA_ERR_LIMIT; MEGA_ERR_ARG, MEGA_ERR_WS: all before any launch,
+ * the outputs untouched).  Per (frame, class), on the rows with score > score_thresh:
+ *   soft_method 0  the greedy NMS of mega_bbox_aug_merge (nms_thresh, strict_gt);
+ *               1  linear soft-NMS: repeatedly keep the highest score (ties: lowest row) with its current score and
+ *                  multiply every remaining row's score by 1 - iou where iou > nms_thresh (>= with strict_gt = 0);
+ *               2  gaussian: by expf(-(iou * iou) / sigma), every row;
+ *                  a row whose score is no longer > score_thresh leaves unkept.  f32 throughout, +1-area IoU.
+ *   vote 1         every kept box becomes sum(s_j * b_j) / sum(s_j) over the live rows j of its (frame, class) with
+ *                  iou(kept, j) >= vote_thresh -- original boxes and scores, f64 sums, rounded once to f32; the kept
+ *                  row always votes.  vote_scoring 0 ("ID"): the score stays; 1 ("AVG"): the f64 mean of the voters'
+ *                  original scores, rounded to f32.
+ * then the class-major compaction and the max_det k-th value cut on the final scores.  A NaN IoU neither decays nor
+ * votes.  soft_method 0 with vote 0 is mega_bbox_aug_merge, bit for bit.  MEGA_ERR_ARG for soft_method outside 0..2,
+ * sigma <= 0, vote / vote_scoring outside 0..1, vote_thresh outside (0, 1]. */
+size_t mega_soft_merge_workspace_bytes(int F, int K, int R, int NC);
+int mega_soft_merge(const float* cboxes, const float* cscores, int F, int K, int R, int NC, const int* view_w,
+                    const int* view_h, const int* view_flip, float score_thresh, float nms_thresh, int strict_gt,
+                    int soft_method, float sigma, int vote, float vote_thresh, int vote_scoring, int max_det,
+                    float* out_boxes, float* out_scores, long long* out_labels, int* out_cnt, void* ws, size_t ws_bytes,
+                    void* stream);
+
 /* Position-embedding logits of the relation module: log(relu(Wg . pe(q,k) + bg) + 1e-6).
  * Replaces extract_position_matrix + extract_position_embedding + the Wgs 1x1 conv + relu + log
  * (roi_box_feature_extractors.py:147-176,:126-144,:593-597,:630) without materialising the

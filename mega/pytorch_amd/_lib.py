@@ -43,6 +43,10 @@ SIGNATURES = {
     "mega_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 4),
     "mega_bbox_aug_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_float, c_float, c_int, c_int] +
                             [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "mega_soft_merge_workspace_bytes": (c_size_t, [c_int] * 4),
+    "mega_soft_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 +
+                        [c_float, c_float, c_int, c_int, c_float, c_int, c_float, c_int, c_int] + [c_void_p] * 5 +
+                        [c_size_t, c_void_p]),
     "mega_position_logits": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "mega_relation_attention_splits": (c_int, [c_int, c_int, c_int]),
     "mega_relation_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

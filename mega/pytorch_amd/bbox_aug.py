@@ -46,6 +46,12 @@ def views_from_cfg(cfg, in_wh):
     return views
 
 
+def identity_view(cfg, in_wh):
+    """The view a video has without TEST.BBOX_AUG: INPUT.MIN_SIZE_TEST / MAX_SIZE_TEST, not flipped."""
+    h, w = feed.get_size(tuple(in_wh), cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    return View(int(cfg.INPUT.MIN_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST), False, (int(w), int(h)))
+
+
 @contextlib.contextmanager
 def candidate_mode(model, on=True):
     """The model's box head emits candidates (PostProcessor.candidates) inside the block."""
@@ -80,9 +86,11 @@ def stack_candidates(dets, num_classes):
     return cb, cs
 
 
-def merge(per_view, views, post_processor, chunk=16):
+def merge(per_view, views, post_processor, chunk=16, final=None):
     """per_view[k] = (boxes [T,NC-1,R_k,4], scores [T,NC-1,R_k]) of view k (stack_candidates) -> list of T BoxLists
-    in view 0's image.  The merge runs `chunk` frames at a time, so its workspace does not grow with the video."""
+    in view 0's image.  The merge runs `chunk` frames at a time, so its workspace does not grow with the video.
+    final: a config.FinalFilter (TEST.SOFT_NMS / TEST.BBOX_VOTE); when one of its options is on the final filter is
+    ops.soft_merge with its settings instead of ops.bbox_aug_merge."""
     pp = post_processor
     K = len(per_view)
     T = per_view[0][1].shape[0]
@@ -102,8 +110,12 @@ def merge(per_view, views, post_processor, chunk=16):
             for k, (b, s) in enumerate(per_view):
                 cb[k, :, :, :b.shape[2]] = b[f0:f1]
                 cs[k, :, :, :s.shape[2]] = s[f0:f1]
-        ob, os_, ol, oc = ops.bbox_aug_merge(cb, cs, sizes, flips, pp.score_thresh, pp.nms, pp.detections_per_img,
-                                             pp.strict_gt)
+        if final is not None and final.enabled:
+            ob, os_, ol, oc = ops.soft_merge(cb, cs, sizes, flips, pp.score_thresh, pp.nms, pp.detections_per_img,
+                                             pp.strict_gt, **final.kwargs())
+        else:
+            ob, os_, ol, oc = ops.bbox_aug_merge(cb, cs, sizes, flips, pp.score_thresh, pp.nms, pp.detections_per_img,
+                                                 pp.strict_gt)
         for f, n in enumerate(oc.tolist()):
             # copies of the live rows: a view would keep the chunk's whole (NC-1)*K*R-row output buffers alive
             res = BoxList(ob[f, :n].clone(), sizes[0], "xyxy")
@@ -113,9 +125,9 @@ def merge(per_view, views, post_processor, chunk=16):
     return out
 
 
-def detect_video(model, views, run_view, chunk=16):
+def detect_video(model, views, run_view, chunk=16, final=None):
     """The views of one video through run_view(view) -> that pass's per-frame outputs (list of BoxLists, candidate mode on
-    for the call), then the merge -> list of BoxLists (one per frame, in view 0's image)."""
+    for the call), then the merge -> list of BoxLists (one per frame, in view 0's image).  final: merge()'s."""
     nc = model.cfg.MODEL.ROI_BOX_HEAD.NUM_CLASSES
     per_view = []
     with candidate_mode(model) as pp:
@@ -123,4 +135,25 @@ def detect_video(model, views, run_view, chunk=16):
             dets = run_view(v)
             per_view.append(stack_candidates(dets, nc))
             del dets
+    if final is not None and final.enabled:
+        return merge(per_view, views, pp, chunk=chunk, final=final)
     return merge(per_view, views, pp, chunk=chunk)
+
+
+def run_video(model, run, v, src, make_source, aug_cfg=None, final=None, chunk=16):
+    """One video through its views and the merge, for the test loop and the demo.  run(source, v) is the engine's pass
+    over one feed; src the identity view's feed.FrameSource, make_source(min_size, max_size, hflip) the feed of another
+    view (closed here).  aug_cfg: the config whose TEST.BBOX_AUG views are used, or None: the identity view alone (what
+    TEST.SOFT_NMS / TEST.BBOX_VOTE need without box augmentation: candidate mode, one pass)."""
+    in_wh = (src.in_hw[1], src.in_hw[0])
+    views = views_from_cfg(aug_cfg, in_wh) if aug_cfg is not None else [identity_view(model.cfg, in_wh)]
+
+    def run_view(view):
+        if view == views[0]:
+            return run(src, v)
+        s = make_source(view.min_size, view.max_size, view.hflip)
+        try:
+            return run(s, v)
+        finally:
+            s.close()
+    return detect_video(model, views, run_view, chunk=chunk, final=final)

@@ -37,6 +37,46 @@ class CfgNode(dict):
         return self
 
 
+class FinalFilter(object):
+    """TEST.SOFT_NMS + TEST.BBOX_VOTE as the merge takes them (ops.soft_merge): soft_method None | "linear" | "gaussian",
+    sigma, vote, vote_thresh, vote_scoring "ID" | "AVG"."""
+
+    def __init__(self, soft_method=None, sigma=0.5, vote=False, vote_thresh=0.8, vote_scoring="ID"):
+        self.soft_method, self.sigma = soft_method, float(sigma)
+        self.vote, self.vote_thresh, self.vote_scoring = bool(vote), float(vote_thresh), vote_scoring
+
+    @property
+    def enabled(self):
+        return self.soft_method is not None or self.vote
+
+    def kwargs(self):
+        return {"soft_method": self.soft_method, "sigma": self.sigma, "vote": self.vote, "vote_thresh": self.vote_thresh,
+                "vote_scoring": self.vote_scoring}
+
+    def __repr__(self):
+        return "FinalFilter(%s)" % ", ".join("%s=%r" % kv for kv in sorted(self.kwargs().items()))
+
+
+def final_filter(cfg):
+    """cfg.TEST.SOFT_NMS / cfg.TEST.BBOX_VOTE -> FinalFilter.  Every key is read with its default, so a reference yacs cfg
+    (which has neither node) gives the disabled filter.  ValueError for an unknown METHOD / SCORING_METHOD, SIGMA <= 0 or
+    VOTE_TH outside (0, 1] -- enabled or not, so a typo does not wait for the switch to be flipped."""
+    test = getattr(cfg, "TEST", None)
+    soft, vote = getattr(test, "SOFT_NMS", None), getattr(test, "BBOX_VOTE", None)
+    method, sigma = getattr(soft, "METHOD", "linear"), getattr(soft, "SIGMA", 0.5)
+    vote_th, scoring = getattr(vote, "VOTE_TH", 0.8), getattr(vote, "SCORING_METHOD", "ID")
+    if method not in ("linear", "gaussian"):
+        raise ValueError("TEST.SOFT_NMS.METHOD = %r: 'linear' or 'gaussian'" % (method,))
+    if not float(sigma) > 0:
+        raise ValueError("TEST.SOFT_NMS.SIGMA = %r must be > 0" % (sigma,))
+    if not 0 < float(vote_th) <= 1:
+        raise ValueError("TEST.BBOX_VOTE.VOTE_TH = %r must be in (0, 1]" % (vote_th,))
+    if scoring not in ("ID", "AVG"):
+        raise ValueError("TEST.BBOX_VOTE.SCORING_METHOD = %r: 'ID' or 'AVG'" % (scoring,))
+    return FinalFilter(method if bool(getattr(soft, "ENABLED", False)) else None, sigma,
+                       bool(getattr(vote, "ENABLED", False)), vote_th, scoring)
+
+
 def get_cfg(arch="R-101", method="mega"):
     """Test-time defaults.  arch: 'R-101' | 'R-50'; method: 'mega' (configs/MEGA/vid_R_{101,50}_C4_MEGA_1x.yaml)
     or 'fgfa' (configs/FGFA/vid_R_{101,50}_C4_FGFA_1x.yaml: GeneralizedRCNNFGFA +
@@ -99,7 +139,13 @@ def _mega_cfg(r50):
         "RESIDUAL_STREAM": "bfloat16",
         # test-time box augmentation (defaults.py:511-526; bbox_aug.py): views = identity, its flip if H_FLIP, then every
         # SCALES entry at MAX_SIZE and its flip if SCALE_H_FLIP
-        "TEST": {"BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False}},
+        "TEST": {"BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False},
+                 # the final filter of the detections (soft_nms.py; neither is in the reference): soft-NMS decays the
+                 # scores of overlapping boxes instead of deleting them, METHOD "linear" | "gaussian" (SIGMA: gaussian);
+                 # box voting replaces every kept box by the score-weighted mean of the candidates with IoU >= VOTE_TH,
+                 # SCORING_METHOD "ID" (score unchanged) | "AVG" (mean of the voters' scores)
+                 "SOFT_NMS": {"ENABLED": False, "METHOD": "linear", "SIGMA": 0.5},
+                 "BBOX_VOTE": {"ENABLED": False, "VOTE_TH": 0.8, "SCORING_METHOD": "ID"}},
         "INPUT": {"MIN_SIZE_TEST": 600, "MAX_SIZE_TEST": 1000,
                   "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True},
         "MODEL": {

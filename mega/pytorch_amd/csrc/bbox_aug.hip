@@ -11,41 +11,14 @@
 // row asc), greedy NMS, class-major / row-ascending compaction and the detections-per-image k-th value cut.  With K = 1
 // and view 0 this is mega_postprocess's P2-P4 on the same candidates: the same bits.
 // Compiled with -ffp-contract=off: the flip / resize products and differences round like the reference's torch ops.
-#include "common.h"
+#include "aug_views.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kMaxViews = 16;
-constexpr int kMaxRows = 8192;     // K * R per (frame, class): 8192 u64 sort keys = 64 KiB of LDS
-
-struct AugViews {
-  float rw[kMaxViews], rh[kMaxViews];   // view 0 size / view k size (f32), per axis
-  float w[kMaxViews];                   // view k image width (f32), for the flip
-  int flip[kMaxViews];
-};
-
-__device__ __forceinline__ unsigned f32_sortable(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float4 to_view0(float4 b, int k, const AugViews& v) {
-  if (v.flip[k]) {
-    const float x1 = v.w[k] - b.z - 1.f;
-    const float x2 = v.w[k] - b.x - 1.f;
-    b.x = x1;
-    b.z = x2;
-  }
-  if (k > 0) {
-    b.x = b.x * v.rw[k];
-    b.y = b.y * v.rh[k];
-    b.z = b.z * v.rw[k];
-    b.w = b.w * v.rh[k];
-  }
-  return b;
-}
+constexpr int kMaxViews = kAugMaxViews;
+constexpr int kMaxRows = kAugMaxRows;     // K * R per (frame, class): 8192 u64 sort keys = 64 KiB of LDS
 
 // One 1024-thread block per (frame, class) problem p = f * C1 + c.  Writes the merged rows (view-0 boxes, scores with
 // -1 for dropped rows, zeroed kept flags) at [p][K*R], and the score-sorted boxes + order + count for the NMS.
@@ -74,11 +47,11 @@ __global__ __launch_bounds__(1024) void aug_load_sort_kernel(const float4* __res
       const size_t src = (((size_t)k * F + f) * C1 + c) * R + r;
       float sc = cscores[src];
       if (!(sc >= 0.f && sc > score_thresh)) sc = -1.f;
-      mboxes[base + i] = to_view0(cboxes[src], k, views);
+      mboxes[base + i] = aug_to_view0(cboxes[src], k, views);
       mscores[base + i] = sc;
       flags[base + i] = 0;
       if (sc >= 0.f) {
-        key = ((u64)f32_sortable(sc) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
+        key = ((u64)aug_f32_sortable(sc) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
         ++local;
       }
     }
@@ -105,19 +78,31 @@ __global__ __launch_bounds__(1024) void aug_load_sort_kernel(const float4* __res
     const int k = idx / R, r = idx - k * R;
     order[base + i] = idx;
     // (recomputed from the input rather than read back from mboxes: no cross-thread global round trip)
-    sboxes[base + i] = to_view0(cboxes[(((size_t)k * F + f) * C1 + c) * R + r], k, views);
+    sboxes[base + i] = aug_to_view0(cboxes[(((size_t)k * F + f) * C1 + c) * R + r], k, views);
   }
   if (threadIdx.x == 0) counts[p] = n;
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 }  // namespace
 
 extern "C" size_t mega_bbox_aug_merge_workspace_bytes(int F, int K, int R, int NC) {
-  const size_t m = (size_t)F * (NC - 1) * K * R;
-  const size_t P = (size_t)F * (NC - 1);
-  return 2 * align_up(m * 16, 256) + 4 * align_up(m * 4, 256) + align_up(m, 256) + 2 * align_up(P * 4, 256);
+  return aug_ws_bytes((size_t)F * (NC - 1) * K * R, (size_t)F * (NC - 1));
+}
+
+// Library-internal (aug_views.h): load + sort + greedy NMS, shared with the soft-NMS / box-voting merge (soft_nms.hip).
+int mega_bbox_aug_load_nms(const float* cboxes, const float* cscores, int F, int K, int R, int NC, const AugViews& v,
+                           float score_thresh, float nms_thresh, int strict_gt, const AugWs& w, hipStream_t st) {
+  const int C1 = NC - 1, P = F * C1, KR = K * R;
+  int ns = 64;
+  while (ns < KR) ns <<= 1;
+  (void)hipFuncSetAttribute((const void*)aug_load_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kMaxRows * (int)sizeof(u64));
+  hipLaunchKernelGGL(aug_load_sort_kernel, dim3(P), dim3(1024), (size_t)ns * sizeof(u64), st, (const float4*)cboxes,
+                     cscores, K, F, C1, R, score_thresh, v, w.mboxes, w.mscores, w.flags, w.sboxes, w.order, w.counts);
+  int rc = mega_check_launch();
+  if (rc != MEGA_OK) return rc;
+  return mega_boxes_nms_lazy((const float*)w.sboxes, w.counts, w.order, P, KR, nms_thresh, strict_gt, KR, w.keep_pos,
+                             w.keep_cnt, w.flags, st);
 }
 
 // cboxes [K][F][NC-1][R][4], cscores [K][F][NC-1][R]; view_w / view_h [K] (host) the views' image sizes, view_flip [K]
@@ -135,43 +120,13 @@ extern "C" int mega_bbox_aug_merge(const float* cboxes, const float* cscores, in
   if ((long long)F * (NC - 1) > 0x7fffffffLL) return MEGA_ERR_ARG;
   if (ws_bytes < mega_bbox_aug_merge_workspace_bytes(F, K, R, NC)) return MEGA_ERR_WS;
   AugViews v;
-  for (int k = 0; k < kMaxViews; ++k) {
-    v.rw[k] = v.rh[k] = 1.f;
-    v.w[k] = 0.f;
-    v.flip[k] = 0;
-  }
-  for (int k = 0; k < K; ++k) {
-    if (view_w[k] <= 0 || view_h[k] <= 0) return MEGA_ERR_ARG;
-    // BoxList.resize: float(s) / float(s_orig) in double, then the f32 tensor times that Python float (an f32 multiply)
-    v.rw[k] = (float)((double)view_w[0] / (double)view_w[k]);
-    v.rh[k] = (float)((double)view_h[0] / (double)view_h[k]);
-    v.w[k] = (float)view_w[k];
-    v.flip[k] = view_flip[k] ? 1 : 0;
-  }
+  int rc = aug_views_init(v, view_w, view_h, view_flip, K);
+  if (rc != MEGA_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int C1 = NC - 1, P = F * C1, KR = K * R;
-  const size_t m = (size_t)P * KR;
-  unsigned char* w = (unsigned char*)ws;
-  float4* mboxes = (float4*)w; w += align_up(m * 16, 256);
-  float4* sboxes = (float4*)w; w += align_up(m * 16, 256);
-  float* mscores = (float*)w; w += align_up(m * 4, 256);
-  int* order = (int*)w; w += align_up(m * 4, 256);
-  int* keep_pos = (int*)w; w += align_up(m * 4, 256);
-  int* tmp_idx = (int*)w; w += align_up(m * 4, 256);
-  unsigned char* flags = w; w += align_up(m, 256);
-  int* counts = (int*)w; w += align_up((size_t)P * 4, 256);
-  int* keep_cnt = (int*)w;
-  int ns = 64;
-  while (ns < KR) ns <<= 1;
-  (void)hipFuncSetAttribute((const void*)aug_load_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kMaxRows * (int)sizeof(u64));
-  hipLaunchKernelGGL(aug_load_sort_kernel, dim3(P), dim3(1024), (size_t)ns * sizeof(u64), st, (const float4*)cboxes,
-                     cscores, K, F, C1, R, score_thresh, v, mboxes, mscores, flags, sboxes, order, counts);
-  int rc = mega_check_launch();
+  const int C1 = NC - 1, KR = K * R;
+  const AugWs w = aug_ws_carve(ws, (size_t)F * C1 * KR, (size_t)F * C1);
+  rc = mega_bbox_aug_load_nms(cboxes, cscores, F, K, R, NC, v, score_thresh, nms_thresh, strict_gt, w, st);
   if (rc != MEGA_OK) return rc;
-  rc = mega_boxes_nms_lazy((const float*)sboxes, counts, order, P, KR, nms_thresh, strict_gt, KR, keep_pos, keep_cnt,
-                           flags, st);
-  if (rc != MEGA_OK) return rc;
-  return mega_boxes_post_finalize(flags, (const float*)mboxes, mscores, F, C1, KR, max_det, out_boxes, out_scores,
-                                  out_labels, out_cnt, tmp_idx, st);
+  return mega_boxes_post_finalize(w.flags, (const float*)w.mboxes, w.mscores, F, C1, KR, max_det, out_boxes, out_scores,
+                                  out_labels, out_cnt, w.tmp_idx, st);
 }

@@ -132,7 +132,7 @@ static inline int mega_check_launch() {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Library-internal launchers of boxes.hip, shared with bbox_aug.hip (not part of the C ABI):
+// Library-internal launchers of boxes.hip, shared with bbox_aug.hip and soft_nms.hip (not part of the C ABI):
 //   mega_boxes_nms_lazy      greedy NMS over P score-sorted problems, always in the lazy one-block-per-problem form
 //                            (nmax <= 8192; no workspace); flags[p][order[p][pos]] = 1 for the kept boxes
 //   mega_boxes_post_finalize the post-processor's class-major compaction + detections-per-image cut of B images

@@ -120,7 +120,10 @@ def encode_jpeg(path, frame):
 class VIDDemo(object):
     """predictor.py:300-640.  cfg.MODEL.VID.METHOD selects the detector (mega, rdn, fgfa, dff, base), each through the
     engine compute_on_dataset uses.  model: a built detector with its weights loaded (None: build_detection_model(cfg),
-    weights as initialised).  runner / overlay replace the engine and ops.overlay_detections (tests without a device)."""
+    weights as initialised).  runner / overlay replace the engine and ops.overlay_detections (tests without a device).
+    With cfg.TEST.SOFT_NMS or cfg.TEST.BBOX_VOTE on, the folder runs as compute_on_dataset runs a video with them: the
+    box head in candidate mode, the identity view (or the TEST.BBOX_AUG views, if enabled too) through the runner, then
+    soft_nms.py's filter; this needs the model (its post-processor holds the thresholds), also beside a runner."""
 
     CATEGORIES = CATEGORIES
 
@@ -137,6 +140,10 @@ class VIDDemo(object):
         self.output_folder = output_folder
         self.render_chunk = int(render_chunk)
         self.source_kwargs = dict(source_kwargs or {})
+        from .soft_nms import enabled_filter
+        self.final = enabled_filter(cfg)        # (ValueError for a bad value, before any device work)
+        if self.final is not None and model is None and runner is not None:
+            raise ValueError("TEST.SOFT_NMS / TEST.BBOX_VOTE need the model beside a runner (candidate mode)")
         if runner is None:
             from . import inference
             if model is None:
@@ -167,14 +174,25 @@ class VIDDemo(object):
             raise FileNotFoundError('no "*%s" files in "%s"' % (suffix, folder))
         return [os.path.join(folder, f) for f in files]
 
-    def _source(self, files):
+    def _source(self, files, min_size=None, max_size=None, hflip=False):
         from PIL import Image
 
         def opener(i):
             return np.asarray(Image.open(files[i]).convert("RGB"))
         return feed.FrameSource(os.path.join(os.path.dirname(files[0]), "%s"), "%s", len(files), self.device,
-                                min_size=self.cfg.INPUT.MIN_SIZE_TEST, max_size=self.cfg.INPUT.MAX_SIZE_TEST,
-                                opener=opener, **self.source_kwargs)
+                                min_size=self.cfg.INPUT.MIN_SIZE_TEST if min_size is None else min_size,
+                                max_size=self.cfg.INPUT.MAX_SIZE_TEST if max_size is None else max_size,
+                                hflip=hflip, opener=opener, **self.source_kwargs)
+
+    def _detect(self, src, files):
+        v = {"start": 0, "pattern": "%s", "seg_len": len(files)}
+        if self.final is None:
+            return self.runner(src, v)
+        from . import bbox_aug
+        aug = getattr(getattr(self.cfg, "TEST", None), "BBOX_AUG", None)
+        aug_cfg = self.cfg if aug is not None and aug.ENABLED else None
+        return bbox_aug.run_video(self.model, self.runner, v, src, lambda mn, mx, hf: self._source(files, mn, mx, hf),
+                                  aug_cfg=aug_cfg, final=self.final)
 
     # ------------------------------------------------------------------------------------------ render
     def _render_chunk(self, src, dets, ids):
@@ -208,7 +226,7 @@ class VIDDemo(object):
         try:
             t0 = time.perf_counter()
             with torch.no_grad():
-                dets = self.runner(src, {"start": 0, "pattern": "%s", "seg_len": L})
+                dets = self._detect(src, files)
             if len(dets) != L:
                 raise RuntimeError("the detector returned %d frames for a folder of %d" % (len(dets), L))
             self.predictions = dets

@@ -740,8 +740,9 @@ class ClipEngine(object):
                         return
                     shard = None
                     if (self.world > 1 or self.force_sharded) and pp.candidates:
-                        raise RuntimeError("ClipEngine: sharded key frames (KeyFrameShard) do not carry TEST.BBOX_AUG "
-                                           "candidates; run box augmentation with one rank per video (inference())")
+                        raise RuntimeError("ClipEngine: sharded key frames (KeyFrameShard) do not carry the candidates of "
+                                           "TEST.BBOX_AUG / TEST.SOFT_NMS / TEST.BBOX_VOTE; run these with one rank per "
+                                           "video (inference())")
                     if self.world > 1 or self.force_sharded:
                         # (legacy dealing: batch position t -> rank t mod world, whole records are everywhere)
                         shard = KeyFrameShard(self.dist, self.group_agg, self.rank, self.world,

@@ -30,6 +30,7 @@ import torch
 
 from . import engine as _engine
 from . import feed
+from .soft_nms import enabled_filter as _final_filter      # cfg -> its TEST.SOFT_NMS / TEST.BBOX_VOTE filter, or None
 from .structures import BoxList
 
 _REF_MODULE = "mega_core.structures.bounding_box"
@@ -180,7 +181,7 @@ def _video_runner(model, steps_per_batch, seed, engine_kwargs):
 
 
 def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_batch=10, seed=0, timer=None,
-                       source_kwargs=None, engine_kwargs=None, bbox_aug_cfg=None):
+                       source_kwargs=None, engine_kwargs=None, bbox_aug_cfg=None, final_filter=None, runner=None):
     """inference.py:17-47: -> {dataset index: BoxList on the host}, for every MODEL.VID.METHOD of the reference:
       mega / rdn   ClipEngine on the video's FrameSource (RDN is the MEGA detector without memory / global pools: rdn.py).  The
                    engine runs with reuse_records=True unless engine_kwargs says otherwise: every frame of a video goes
@@ -193,38 +194,36 @@ def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_bat
     With MODEL.RPN_ONLY the BoxLists are the key frames' proposals (field "objectness"); mega / rdn then run through
     BaseClipEngine, ClipEngine is not used.
     bbox_aug_cfg: a config whose TEST.BBOX_AUG.ENABLED is set (default: the model's own config, if set there): test-time
-    box augmentation of every video (bbox_aug.py) with that config's views, each view a pass through the same engine."""
+    box augmentation of every video (bbox_aug.py) with that config's views, each view a pass through the same engine.
+    final_filter: a config.FinalFilter (default: the model's own TEST.SOFT_NMS / TEST.BBOX_VOTE).  When one of its options
+    is on, the detections come from soft_nms.py's filter: the views of TEST.BBOX_AUG feed it, and without box augmentation
+    the video runs as the identity view alone (candidate mode, one pass).  With both off nothing changes.
+    runner: replaces the engine, run(src, v) -> the video's per-frame outputs (tests without a device)."""
     model.eval()
     results = {}
     videos = index.videos if videos is None else videos
     aug_cfg = bbox_aug_cfg if bbox_aug_cfg is not None else _bbox_aug_cfg(model.cfg)
-    run = _video_runner(model, steps_per_batch, seed, engine_kwargs)
+    final = final_filter if final_filter is not None else _final_filter(model.cfg)
+    if final is not None and not final.enabled:
+        final = None
+    run = runner if runner is not None else _video_runner(model, steps_per_batch, seed, engine_kwargs)
     pattern = os.path.join(img_dir, "%s.JPEG")
     for v in videos:
         def source(min_size, max_size, hflip=False):
             return feed.FrameSource(pattern, v["pattern"], v["seg_len"], device, min_size=min_size, max_size=max_size,
                                     hflip=hflip, **(source_kwargs or {}))
-        if aug_cfg is None:
+        if aug_cfg is None and final is None:
             src = source(model.cfg.INPUT.MIN_SIZE_TEST, model.cfg.INPUT.MAX_SIZE_TEST)
             t0 = time.perf_counter()
             with torch.no_grad():
                 dets = run(src, v)
         else:
             from . import bbox_aug
-            src = source(aug_cfg.INPUT.MIN_SIZE_TEST, aug_cfg.INPUT.MAX_SIZE_TEST)      # the identity view's feed
-            views = bbox_aug.views_from_cfg(aug_cfg, (src.in_hw[1], src.in_hw[0]))
-
-            def run_view(view):
-                if view == views[0]:
-                    return run(src, v)
-                s = source(view.min_size, view.max_size, view.hflip)
-                try:
-                    return run(s, v)
-                finally:
-                    s.close()
+            size_cfg = aug_cfg if aug_cfg is not None else model.cfg
+            src = source(size_cfg.INPUT.MIN_SIZE_TEST, size_cfg.INPUT.MAX_SIZE_TEST)      # the identity view's feed
             t0 = time.perf_counter()
             with torch.no_grad():
-                dets = bbox_aug.detect_video(model, views, run_view)
+                dets = bbox_aug.run_video(model, run, v, src, source, aug_cfg=aug_cfg, final=final)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         if timer is not None:
@@ -318,13 +317,18 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     value is then the rescored list.
     cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
     (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
-    Seq-NMS and TEST.BBOX_AUG work on detections: combined with RPN_ONLY they are a ValueError."""
+    Seq-NMS, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY they are a
+    ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     box_only = _rpn_only(cfg)
     if box_only and seq_nms is not None and seq_nms is not False:
         raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")
     if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
         raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
+    final = _final_filter(cfg) or _final_filter(model.cfg)      # (raises ValueError for a bad value, before any device work)
+    if box_only and final is not None:
+        raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.SOFT_NMS / TEST.BBOX_VOTE filter detections (disable "
+                         "them or RPN_ONLY)")
     device = torch.device(cfg.MODEL.DEVICE if device is None else device)
     dist = torch.distributed
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -335,7 +339,7 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     t0 = time.perf_counter()
     # TEST.BBOX_AUG.ENABLED is read from cfg, as tools/test_net.py does (engine/inference.py:26)
     preds = compute_on_dataset(model, index, img_dir, device, videos=mine, timer=timer, bbox_aug_cfg=_bbox_aug_cfg(cfg),
-                               **kw)
+                               final_filter=final, **kw)
     if world > 1:
         dist.barrier(group=group)
     total = time.perf_counter() - t0

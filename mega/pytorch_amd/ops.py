@@ -693,6 +693,56 @@ def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_th
     return ob, os_, ol, oc
 
 
+SOFT_NMS_METHODS = {None: 0, "linear": 1, "gaussian": 2}
+BBOX_VOTE_SCORING = {"ID": 0, "AVG": 1}
+
+
+def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh, max_det, strict_gt=True, soft_method=None,
+               sigma=0.5, vote=False, vote_thresh=0.8, vote_scoring="ID"):
+    """bbox_aug_merge with soft-NMS and / or box voting as the final filter (include/mega_hip.h mega_soft_merge; the
+    definition is soft_nms.py's).  soft_method None | "linear" | "gaussian"; vote_scoring "ID" | "AVG".  Inputs, outputs
+    and limits as bbox_aug_merge; with soft_method None and vote False the result is bbox_aug_merge's, bit for bit."""
+    _gpu(cboxes, cscores)
+    lib = _lib.load()
+    K, F, C1, R = cscores.shape
+    if soft_method not in SOFT_NMS_METHODS:
+        raise ValueError("soft_merge: soft_method %r, not None, 'linear' or 'gaussian'" % (soft_method,))
+    if vote_scoring not in BBOX_VOTE_SCORING:
+        raise ValueError("soft_merge: vote_scoring %r, not 'ID' or 'AVG'" % (vote_scoring,))
+    if not float(sigma) > 0:
+        raise ValueError("soft_merge: sigma = %r must be > 0" % (sigma,))
+    if not 0 < float(vote_thresh) <= 1:
+        raise ValueError("soft_merge: vote_thresh = %r must be in (0, 1]" % (vote_thresh,))
+    if K != len(view_sizes) or K != len(view_flips):
+        raise ValueError("soft_merge: %d views of candidates, %d sizes, %d flips" % (K, len(view_sizes), len(view_flips)))
+    if K > BBOX_AUG_MAX_VIEWS or K * R > BBOX_AUG_MAX_ROWS:
+        raise ValueError("soft_merge: %d views x %d rows per class; the merge takes at most %d views and %d rows "
+                         "per (frame, class)" % (K, R, BBOX_AUG_MAX_VIEWS, BBOX_AUG_MAX_ROWS))
+    assert cboxes.shape == (K, F, C1, R, 4) and cboxes.dtype == torch.float32 and cscores.dtype == torch.float32
+    assert cboxes.is_contiguous() and cscores.is_contiguous()
+    dev = cboxes.device
+    cap = C1 * K * R
+    ob = torch.empty((F, cap, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((F, cap), dtype=torch.float32, device=dev)
+    ol = torch.empty((F, cap), dtype=torch.int64, device=dev)
+    oc = torch.zeros((F,), dtype=torch.int32, device=dev)
+    nb = lib.mega_soft_merge_workspace_bytes(F, K, R, C1 + 1)
+    ws = _ws(nb, dev)
+    arr = ctypes.c_int * K
+    vw = arr(*[int(s[0]) for s in view_sizes])
+    vh = arr(*[int(s[1]) for s in view_sizes])
+    vf = arr(*[1 if f else 0 for f in view_flips])
+    _tok = _pb("soft_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
+    rc = lib.mega_soft_merge(_ptr(cboxes), _ptr(cscores), F, K, R, C1 + 1, ctypes.cast(vw, ctypes.c_void_p),
+                             ctypes.cast(vh, ctypes.c_void_p), ctypes.cast(vf, ctypes.c_void_p), float(score_thresh),
+                             float(nms_thresh), int(strict_gt), SOFT_NMS_METHODS[soft_method], float(sigma),
+                             1 if vote else 0, float(vote_thresh), BBOX_VOTE_SCORING[vote_scoring], int(max_det),
+                             _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc), _ptr(ws), nb, _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_soft_merge")
+    return ob, os_, ol, oc
+
+
 # ------------------------------------------------------------------------------------------------ relation module
 def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False):
     """-> [16, Nq, ldp] f32 with ldp = roundup(Nk, 32).  precise=False: fast sin/cos (bf16 mode).
