@@ -4,11 +4,11 @@
  * Boundary rules
  *   - extern "C", plain device pointers + sizes, no torch / ATen types.
  *   - every entry point returns int: 0 = MEGA_OK, 1 = bad argument, 2 = launch failure,
- *     3 = workspace too small, 4 = a kernel's loop bound was exceeded (mega_seq_nms).  Nothing is allocated inside:
- *     the caller owns outputs and workspaces.
+ *     3 = workspace too small, 4 = a kernel's loop bound was exceeded (mega_seq_nms, mega_link_tracks).  Nothing is
+ *     allocated inside: the caller owns outputs and workspaces.
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All work is
- *     enqueued on that stream; no call synchronises the device or copies to the host, except mega_seq_nms, which
- *     reads its status word back.
+ *     enqueued on that stream; no call synchronises the device or copies to the host, except mega_seq_nms and
+ *     mega_link_tracks, which read their status word back.
  *   - dtype codes: MEGA_F32 = 0 (exact-f32 MFMA path, parity mode), MEGA_BF16 = 1, MEGA_F16 = 2 (IEEE half: the same
  *     kernels instantiated for _Float16 operands -- the bf16 MFMA rate and bytes with 11 significant bits instead of 8,
  *     values bounded by 65 504; accumulation is f32 in every mode).  Wherever an entry point takes a dtype code, MEGA_F16
@@ -35,7 +35,7 @@ extern "C" {
 #define MEGA_ERR_ARG 1
 #define MEGA_ERR_LAUNCH 2
 #define MEGA_ERR_WS 3
-#define MEGA_ERR_LIMIT 4   /* a kernel's loop bound was exceeded (reported by mega_seq_nms) */
+#define MEGA_ERR_LIMIT 4   /* a kernel's loop bound was exceeded (mega_seq_nms, mega_link_tracks) */
 
 /* Conv2d (+ FrozenBatchNorm2d scale/bias) (+ residual add) (+ ReLU), implicit GEMM on MFMA.
  * Replaces torch Conv2d->cuDNN + the unfused FrozenBatchNorm2d / relu_ / += of
@@ -539,6 +539,28 @@ size_t mega_seq_nms_workspace_bytes(long long N, long long segs);
 int mega_seq_nms(const float* box, const float* score, const long long* seg_off, const int* tasks, int T, int F, int C,
                  long long N, float link_iou, float nms_iou, int rescore_max, unsigned char* keep, float* new_score,
                  long long* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* Linking detections into tracks (mega/pytorch_amd/tracks.py defines it; the reference has no counterpart).  One
+ * workgroup per (video, class) task; per task, frames t ascending: close every open track whose last frame is
+ * < t - max_gap - 1; then the frame's boxes with score >= score_thresh, in descending score (equal scores: ascending
+ * position), each join the open track with last frame < t of the largest iou(track's last box, box) > link_iou (strict; on
+ * equal IoU the track whose root has the smallest pos), or open a new track with themselves as the root.  A track extended
+ * or born in frame t is not available in frame t; a NaN IoU never links.  IoU: the +1 convention in f32, as mega_seq_nms.
+ * Inputs, sorted class-major then frame, and within each (class, frame) run by descending score, equal scores by
+ * ascending position:
+ *   box [N][4] f32, score [N] f32 (>= 0), pos [N] i32 (the box's position in the frame-by-frame concatenation: the tie
+ *   key), seg_off [C * F + 1] i64 and tasks [T][3] i32 as for mega_seq_nms.
+ * Outputs (same order): root [N] i64 = the index (in this order) of the first box of the box's track, -1 for a box below
+ * score_thresh; and at each root's index cnt i32 = the track's box count, sum f64 = its members' scores added in frame
+ * order, mx f32 = the largest of them (other elements are not written).
+ * max_open: the caller's bound on the open tracks of a task (e.g. the most boxes of one class in max_gap + 2 consecutive
+ * frames); tracks beyond the 1024 kept in LDS live in the workspace, mega_link_tracks_workspace_bytes(T, max_open).
+ * link_iou in [0, 1], score_thresh not NaN, max_gap >= 0; negative sizes: MEGA_ERR_ARG; N = 0 or T = 0 is a no-op.
+ * Synchronises the stream: returns MEGA_ERR_LIMIT if a task would have opened more than max_open tracks. */
+size_t mega_link_tracks_workspace_bytes(int T, int max_open);
+int mega_link_tracks(const float* box, const float* score, const int* pos, const long long* seg_off, const int* tasks,
+                     int T, int F, int C, long long N, float score_thresh, float link_iou, int max_gap, int max_open,
+                     long long* root, int* cnt, double* sum, float* mx, void* ws, size_t ws_bytes, void* stream);
 
 /* Detection overlay of the demo (mega/pytorch_amd/demo.py defines it), in place on F original-size frames, no host round
  * trip.  Per frame: rows i < counts[f] with score > thr (strict), drawn in descending score order (equal scores: ascending

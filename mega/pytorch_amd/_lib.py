@@ -97,6 +97,9 @@ SIGNATURES = {
     "mega_seq_nms_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
     "mega_seq_nms": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int] + [c_void_p] * 4 +
                      [c_size_t, c_void_p]),
+    "mega_link_tracks_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mega_link_tracks": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int, c_int] +
+                         [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mega_overlay_detections_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mega_overlay_detections": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                         c_float, c_float, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,

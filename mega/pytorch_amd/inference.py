@@ -306,7 +306,7 @@ def load_predictions(path):
 
 
 def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, anno_path=None,
-              motion_iou=None, seq_nms=None, **kw):
+              motion_iou=None, seq_nms=None, tracks=None, **kw):
     """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
     evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
     result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
@@ -315,14 +315,25 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     the main process after the gather.  predictions.pth stays the raw list; the rescored one goes to
     predictions_seq_nms.pth and its evaluation to result_seq_nms.txt (result.txt stays the raw evaluation); the return
     value is then the rescored list.
+    tracks: None (off), True or a dict of tracks.link's score_thresh / link_iou / max_gap / min_len / rescore: the
+    detections (what Seq-NMS kept, if both are on) linked into tracks on the main process.  predictions_tracks.pth holds
+    them with the extra field "track_ids" (and the rescored "scores" when rescore is set), tracks.txt one line per track
+    (tracks.format_table), and with rescore and anno_path result_tracks.txt the evaluation of the rescored list;
+    predictions.pth, result.txt and the return value do not change.
     cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
     (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
-    Seq-NMS, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY they are a
-    ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is."""
+    Seq-NMS, track linking, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY
+    they are a ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     box_only = _rpn_only(cfg)
     if box_only and seq_nms is not None and seq_nms is not False:
         raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")
+    if box_only and tracks is not None and tracks is not False:
+        raise ValueError("MODEL.RPN_ONLY returns proposals: track linking (tracks=...) needs detections")
+    if tracks is not None and tracks is not False:
+        from . import tracks as tr
+        track_params = {} if tracks is True else dict(tracks)
+        tr.check_params(**track_params)                          # (a bad value raises before the run, not after it)
     if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
         raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
     final = _final_filter(cfg) or _final_filter(model.cfg)      # (raises ValueError for a bad value, before any device work)
@@ -359,6 +370,15 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         rescored = sn.seq_nms(predictions, [(v["start"], v["seg_len"]) for v in index.videos], device=device, **params)
         if output_folder:
             save_predictions(rescored, os.path.join(output_folder, "predictions_seq_nms.pth"))
+    tracked = None
+    if tracks is not None and tracks is not False:
+        tracked, table = tr.link(predictions if rescored is None else rescored,
+                                 [(v["start"], v["seg_len"]) for v in index.videos], device=device, **track_params)
+        if output_folder:
+            save_predictions(tracked, os.path.join(output_folder, "predictions_tracks.pth"))
+            with open(os.path.join(output_folder, "tracks.txt"), "w") as f:
+                f.write(tr.format_table(table))
+        logger.info("Linked %d tracks", len(table))
     if anno_path is not None:
         from . import vid_eval
         if isinstance(motion_iou, str):
@@ -372,4 +392,7 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if rescored is not None:
             vid_eval.evaluate_detections(rescored, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                          logger=logger, result_name="result_seq_nms.txt")
+        if tracked is not None and track_params.get("rescore") is not None:
+            vid_eval.evaluate_detections(tracked, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
+                                         logger=logger, result_name="result_tracks.txt")
     return predictions if rescored is None else rescored

@@ -1517,6 +1517,37 @@ def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     return keep, new_score, stats
 
 
+# ------------------------------------------------------------------------------------------------ track linking
+def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, max_gap, max_open):
+    """Link detections into tracks over T (video, class) tasks (include/mega_hip.h mega_link_tracks).  box [N,4] f32,
+    score [N] f32, pos [N] i32 sorted class-major, then frame, then descending score (equal scores: ascending position);
+    seg_off [C*F+1] i64, tasks [T,3] i32 (class, first frame, frame count), longest first; max_open: a bound on a task's
+    open tracks.  -> root [N] i64 (index of the track's first box in this order, -1: no track), and valid at the roots
+    cnt [N] i32, sum [N] f64, mx [N] f32, on the device.  Synchronises the stream (the kernel's status word)."""
+    _gpu(box, score, pos, seg_off, tasks)
+    lib = _lib.load()
+    N, T = box.shape[0], tasks.shape[0]
+    for t, dt in ((box, torch.float32), (score, torch.float32), (pos, torch.int32), (seg_off, torch.int64),
+                  (tasks, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert box.shape == (N, 4) and score.shape == (N,) and pos.shape == (N,) and seg_off.shape == (C * F + 1,)
+    assert tasks.shape == (T, 3)
+    dev = box.device
+    root = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+    acc = torch.zeros(N, dtype=torch.float64, device=dev)
+    mx = torch.zeros(N, dtype=torch.float32, device=dev)
+    nb = lib.mega_link_tracks_workspace_bytes(T, int(max_open))
+    ws = _ws(max(nb, 1), dev)
+    _tok = _pb("link_tracks")
+    rc = lib.mega_link_tracks(_ptr(box), _ptr(score), _ptr(pos), _ptr(seg_off), _ptr(tasks), T, int(F), int(C), N,
+                              float(score_thresh), float(link_iou), int(max_gap), int(max_open), _ptr(root), _ptr(cnt),
+                              _ptr(acc), _ptr(mx), _ptr(ws), nb, _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_link_tracks")
+    return root, cnt, acc, mx
+
+
 # ------------------------------------------------------------------------------------------------ demo overlay
 def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, thickness, palette, atlas,
                        select_only=False):

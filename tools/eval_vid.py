@@ -11,6 +11,11 @@ folder of predictions.pth); the text is also printed.
 over the videos of --img-index, writes predictions_seq_nms.pth and result_seq_nms.txt to the output folder and prints
 that evaluation too.
 
+--tracks (with --tracks-score-thresh / --tracks-link-iou / --tracks-max-gap / --tracks-min-len / --tracks-rescore) links
+the detections (what Seq-NMS kept, with --seq-nms) into tracks (mega.pytorch_amd.tracks): predictions_tracks.pth with the
+field "track_ids", tracks.txt with one line per track, and with --tracks-rescore avg|max result_tracks.txt, the evaluation
+of the rescored detections.
+
 --box-only evaluates proposals instead (predictions made with MODEL.RPN_ONLY True, field "objectness"): the recall of the
 GT boxes at IoU 0.5 by each frame's first --limit proposals -> proposal_result.txt ("Recall: x", the reference's
 do_vid_evaluation(box_only=True)); --recall-table adds the recall at limits 10 / 50 / 100 / 300 and IoU 0.50 .. 0.95 with
@@ -40,12 +45,22 @@ def main(argv=None):
                     "frames link")
     ap.add_argument("--seq-nms-iou", type=float, default=0.3, help="Seq-NMS: IoU above which a path box suppresses")
     ap.add_argument("--seq-nms-rescore", choices=("avg", "max"), default="avg")
+    ap.add_argument("--tracks", action="store_true", help="link the detections into tracks (predictions_tracks.pth, "
+                    "tracks.txt)")
+    ap.add_argument("--tracks-score-thresh", type=float, default=0.05, help="tracks: boxes scoring less take no part")
+    ap.add_argument("--tracks-link-iou", type=float, default=0.5, help="tracks: IoU above which a box joins a track")
+    ap.add_argument("--tracks-max-gap", type=int, default=1, help="tracks: frames a track may go without a box")
+    ap.add_argument("--tracks-min-len", type=int, default=1, help="tracks: shorter tracks get no id")
+    ap.add_argument("--tracks-rescore", choices=("none", "avg", "max"), default="none",
+                    help="tracks: replace a linked box's score by its track's mean / max -> result_tracks.txt")
     ap.add_argument("--box-only", action="store_true", help="proposal recall of RPN-only predictions (proposal_result.txt)")
     ap.add_argument("--limit", type=int, default=300, help="--box-only: proposals used per frame (at most 1024)")
     ap.add_argument("--recall-table", action="store_true", help="--box-only: also the recall per limit and IoU threshold")
     a = ap.parse_args(argv)
     if a.box_only and (a.seq_nms or a.motion_iou):
         ap.error("--box-only evaluates proposals: --seq-nms / --motion-iou apply to detections")
+    if a.box_only and a.tracks:
+        ap.error("--box-only evaluates proposals: --tracks applies to detections")
     from mega.pytorch_amd import inference, vid_eval
     preds = inference.load_predictions(a.predictions)
     gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
@@ -71,6 +86,22 @@ def main(argv=None):
         res = vid_eval.evaluate_detections(rescored, gt, motion_iou=motion, output_folder=out, device=a.device,
                                            result_name="result_seq_nms.txt")
         sys.stdout.write("Seq-NMS:\n" + vid_eval.format_result(res))
+        preds = rescored
+    if a.tracks:
+        from mega.pytorch_amd import tracks
+        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
+        rescore = None if a.tracks_rescore == "none" else a.tracks_rescore
+        tracked, table = tracks.link(preds, videos, score_thresh=a.tracks_score_thresh, link_iou=a.tracks_link_iou,
+                                     max_gap=a.tracks_max_gap, min_len=a.tracks_min_len, rescore=rescore, device=a.device)
+        os.makedirs(out, exist_ok=True)
+        inference.save_predictions(tracked, os.path.join(out, "predictions_tracks.pth"))
+        with open(os.path.join(out, "tracks.txt"), "w") as f:
+            f.write(tracks.format_table(table))
+        sys.stdout.write("Tracks: %d\n" % len(table))
+        if rescore is not None:
+            res = vid_eval.evaluate_detections(tracked, gt, motion_iou=motion, output_folder=out, device=a.device,
+                                               result_name="result_tracks.txt")
+            sys.stdout.write("Tracks, rescored:\n" + vid_eval.format_result(res))
     return 0
 
 
