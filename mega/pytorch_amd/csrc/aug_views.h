@@ -1,8 +1,11 @@
 // Shared by bbox_aug.hip and soft_nms.hip: the views of a test-time augmentation merge, the mapping of a view's box into
-// view 0's image, the +1-area IoU, the (score, row) sort key and the workspace both merges carve up the same way.
-// Both files are compiled with -ffp-contract=off: every product and difference below rounds on its own.
+// view 0's image, and the workspace both merges and the post-processor (boxes.hip) carve up the same way.  The +1 IoU and
+// the (score, row) sort key are box_math.h's.
+// Every includer is compiled with -ffp-contract=off: every product and difference below rounds on its own.
 #pragma once
+#include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 constexpr int kAugMaxViews = 16;
 constexpr int kAugMaxRows = 8192;     // K * R per (frame, class)
@@ -13,7 +16,8 @@ struct AugViews {
   int flip[kAugMaxViews];
 };
 
-// The workspace of mega_bbox_aug_merge (m = F * (NC-1) * K * R rows, P = F * (NC-1) problems), in this order.
+// The workspace of mega_bbox_aug_merge (m = F * (NC-1) * K * R rows, P = F * (NC-1) problems) and the head of
+// mega_soft_merge's and mega_postprocess_batched's (m = B * (NC-1) * R, P = B * (NC-1)), in this order.
 struct AugWs {
   float4* mboxes;          // [m] boxes in view 0's image
   float4* sboxes;          // [m] the same, score-sorted per problem
@@ -24,30 +28,12 @@ struct AugWs {
   unsigned char* flags;    // [m] 1 = kept
   int* counts;             // [P] live rows
   int* keep_cnt;           // [P] kept rows
-  unsigned char* end;
 };
 
-static inline size_t aug_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-static inline size_t aug_ws_bytes(size_t m, size_t P) {
-  return 2 * aug_align_up(m * 16, 256) + 4 * aug_align_up(m * 4, 256) + aug_align_up(m, 256) +
-         2 * aug_align_up(P * 4, 256);
-}
-
-static inline AugWs aug_ws_carve(void* ws, size_t m, size_t P) {
-  AugWs a;
-  unsigned char* w = (unsigned char*)ws;
-  a.mboxes = (float4*)w; w += aug_align_up(m * 16, 256);
-  a.sboxes = (float4*)w; w += aug_align_up(m * 16, 256);
-  a.mscores = (float*)w; w += aug_align_up(m * 4, 256);
-  a.order = (int*)w; w += aug_align_up(m * 4, 256);
-  a.keep_pos = (int*)w; w += aug_align_up(m * 4, 256);
-  a.tmp_idx = (int*)w; w += aug_align_up(m * 4, 256);
-  a.flags = w; w += aug_align_up(m, 256);
-  a.counts = (int*)w; w += aug_align_up(P * 4, 256);
-  a.keep_cnt = (int*)w; w += aug_align_up(P * 4, 256);
-  a.end = w;
-  return a;
+// Takes the nine arrays from c; an entry point with more in its workspace goes on taking from the same carver.
+static inline AugWs aug_ws_carve(WsCarver& c, size_t m, size_t P) {
+  return {c.take<float4>(m), c.take<float4>(m), c.take<float>(m), c.take<int>(m), c.take<int>(m), c.take<int>(m),
+          c.take<unsigned char>(m), c.take<int>(P), c.take<int>(P)};     // (evaluated left to right: AugWs's order)
 }
 
 // view_w / view_h / view_flip [K] (host).  MEGA_ERR_ARG for a view without a size.
@@ -68,11 +54,6 @@ static inline int aug_views_init(AugViews& v, const int* view_w, const int* view
   return MEGA_OK;
 }
 
-static __device__ __forceinline__ unsigned aug_f32_sortable(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 static __device__ __forceinline__ float4 aug_to_view0(float4 b, int k, const AugViews& v) {
   if (v.flip[k]) {
     const float x1 = v.w[k] - b.z - 1.f;
@@ -87,17 +68,6 @@ static __device__ __forceinline__ float4 aug_to_view0(float4 b, int k, const Aug
     b.w = b.w * v.rh[k];
   }
   return b;
-}
-
-// nms.cu:13-21 devIoU, term by term (boxes.hip dev_iou)
-static __device__ __forceinline__ float aug_iou(const float4 a, const float4 b) {
-  const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-  const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-  const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
-  const float interS = width * height;
-  const float Sa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
-  const float Sb = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-  return interS / (Sa + Sb - interS);
 }
 
 // Library-internal (bbox_aug.hip): the first two stages of mega_bbox_aug_merge -- load + view mapping + per-class sort,

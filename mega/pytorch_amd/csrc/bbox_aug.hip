@@ -51,7 +51,7 @@ __global__ __launch_bounds__(1024) void aug_load_sort_kernel(const float4* __res
       mscores[base + i] = sc;
       flags[base + i] = 0;
       if (sc >= 0.f) {
-        key = ((u64)aug_f32_sortable(sc) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
+        key = ((u64)f32_sortable(sc) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
         ++local;
       }
     }
@@ -86,7 +86,9 @@ __global__ __launch_bounds__(1024) void aug_load_sort_kernel(const float4* __res
 }  // namespace
 
 extern "C" size_t mega_bbox_aug_merge_workspace_bytes(int F, int K, int R, int NC) {
-  return aug_ws_bytes((size_t)F * (NC - 1) * K * R, (size_t)F * (NC - 1));
+  WsCarver c(nullptr);
+  aug_ws_carve(c, (size_t)F * (NC - 1) * K * R, (size_t)F * (NC - 1));
+  return c.bytes;
 }
 
 // Library-internal (aug_views.h): load + sort + greedy NMS, shared with the soft-NMS / box-voting merge (soft_nms.hip).
@@ -124,7 +126,8 @@ extern "C" int mega_bbox_aug_merge(const float* cboxes, const float* cscores, in
   if (rc != MEGA_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int C1 = NC - 1, KR = K * R;
-  const AugWs w = aug_ws_carve(ws, (size_t)F * C1 * KR, (size_t)F * C1);
+  WsCarver c(ws);
+  const AugWs w = aug_ws_carve(c, (size_t)F * C1 * KR, (size_t)F * C1);
   rc = mega_bbox_aug_load_nms(cboxes, cscores, F, K, R, NC, v, score_thresh, nms_thresh, strict_gt, w, st);
   if (rc != MEGA_OK) return rc;
   return mega_boxes_post_finalize(w.flags, (const float*)w.mboxes, w.mscores, F, C1, KR, max_det, out_boxes, out_scores,

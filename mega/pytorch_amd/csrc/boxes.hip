@@ -14,16 +14,12 @@
 // unspecified tie order (torch.topk / sort, nms.cu:74), these kernels sort by (score desc, index asc).
 #include <stdlib.h>
 
-#include "common.h"
+#include "aug_views.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ unsigned f32_sortable(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __device__ __forceinline__ float sortable_f32(unsigned s) {
   unsigned u = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s;
   return __uint_as_float(u);
@@ -46,28 +42,14 @@ __device__ void bitonic_sort_desc(u64* s, int n) {
   }
 }
 
-// nms.cu:13-21 devIoU, term by term.
-__device__ __forceinline__ float dev_iou(const float4 a, const float4 b) {
-  const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-  const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-  const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
-  const float interS = width * height;
-  const float Sa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
-  const float Sb = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-  return interS / (Sa + Sb - interS);
-}
-
-// The decision `dev_iou(a, b) > thr` (strict_gt) or `>= thr` WITHOUT the division in all but borderline cases:
+// The decision `box_iou1(a, b) > thr` (strict_gt) or `>= thr` WITHOUT the division in all but borderline cases:
 // iou <> thr  <=>  interS <> thr * union; when the two sides differ by more than 1e-5 relative -- 40x the worst
 // rounding error of the quotient (<= 2.5 ulp for the device's f32 division) plus that of the product -- the answer
-// cannot depend on how the quotient rounds, otherwise the quotient is evaluated exactly as dev_iou does.
+// cannot depend on how the quotient rounds, otherwise the quotient is evaluated exactly as box_iou1 does.
 __device__ __forceinline__ bool dev_suppresses_areas(const float4 a, const float Sa, const float4 b, const float Sb,
                                                      float thr, int strict_gt) {
-  const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-  const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-  const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
-  const float interS = width * height;
-  const float uni = Sa + Sb - interS;
+  const float interS = box_inter1(a, b);
+  const float uni = box_union1(Sa, Sb, interS);
   if (thr > 0.f && uni > 0.f) {
     const float rhs = thr * uni;
     if (interS > rhs * 1.00001f) return true;
@@ -77,8 +59,7 @@ __device__ __forceinline__ bool dev_suppresses_areas(const float4 a, const float
   return strict_gt ? (iou > thr) : (iou >= thr);
 }
 __device__ __forceinline__ bool dev_suppresses(const float4 a, const float4 b, float thr, int strict_gt) {
-  return dev_suppresses_areas(a, (a.z - a.x + 1.f) * (a.w - a.y + 1.f), b, (b.z - b.x + 1.f) * (b.w - b.y + 1.f), thr,
-                              strict_gt);
+  return dev_suppresses_areas(a, box_area1(a), b, box_area1(b), thr, strict_gt);
 }
 
 // ---------------------------------------------------------------------------------------------- NMS mask
@@ -251,13 +232,13 @@ __global__ __launch_bounds__(1024) void nms_lazy_kernel(const float4* __restrict
       mine = sb[j];
       alive = !rem[j];
     }
-    const float my_area = (mine.z - mine.x + 1.f) * (mine.w - mine.y + 1.f);
+    const float my_area = box_area1(mine);
     if (ws > 0) {
       const int K = s_total;
       for (int k = 0; k < K; ++k) {
         if (!__ballot(alive)) break;                      // the whole wavefront is dead
         const float4 kbx = sb[klist[k]];
-        const float ka = (kbx.z - kbx.x + 1.f) * (kbx.w - kbx.y + 1.f);
+        const float ka = box_area1(kbx);
         if (alive && dev_suppresses_areas(kbx, ka, mine, my_area, thr, strict_gt)) alive = false;
       }
       if (j < n && !alive) rem[j] = 1;
@@ -298,7 +279,7 @@ __global__ __launch_bounds__(1024) void nms_lazy_kernel(const float4* __restrict
       if (__ballot(alive && j >= b0 + 64)) {
         for (int k = 0; k < nk; ++k) {
           const float4 kbx = kb[k];
-          const float ka = (kbx.z - kbx.x + 1.f) * (kbx.w - kbx.y + 1.f);
+          const float ka = box_area1(kbx);
           if (alive && j >= b0 + 64 && dev_suppresses_areas(kbx, ka, mine, my_area, thr, strict_gt)) {
             alive = false;
             rem[j] = 1;
@@ -758,15 +739,53 @@ __global__ void set_int_kernel(int* p, int v, unsigned char* zero, int nzero) {
   for (int e = i; e < min(i + 4, nzero); ++e) zero[e] = 0;
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// The workspaces, each struct in its layout's order (a braced list is evaluated left to right).
+// The mask-form NMS: the suppression words [P][nmax][cb], then one spare 256-byte slot.
+u64* nms_carve(WsCarver& c, int P, int nmax) {
+  u64* mask = c.take<u64>((size_t)P * nmax * (size_t)cdiv(nmax, 64));
+  c.take<unsigned char>(256);
+  return mask;
+}
+
+struct NmsFullWs {     // mega_nms
+  float4* sboxes; int* order; int* keep_pos; unsigned char* flags; int* counts; u64* mask;
+  size_t bytes;
+};
+NmsFullWs nms_full_carve(void* ws, int n) {
+  WsCarver c(ws);
+  const size_t m = (size_t)n;
+  return {c.take<float4>(m), c.take<int>(m), c.take<int>(m), c.take<unsigned char>(m), c.take<int>(1), nms_carve(c, 1, n),
+          c.bytes};
+}
+
+struct RpnWs {         // mega_rpn_select_idx: B frames of k candidates each
+  float4* sboxes; float* sscores; int* keep_pos; int* aidx; unsigned char* valid; int* counts; u64* mask;
+  size_t bytes;
+};
+RpnWs rpn_carve(void* ws, int B, int k) {
+  WsCarver c(ws);
+  const size_t m = (size_t)B * k;
+  return {c.take<float4>(m), c.take<float>(m), c.take<int>(m), c.take<int>(m), c.take<unsigned char>(m),
+          c.take<int>((size_t)B), nms_carve(c, B, k), c.bytes};
+}
+
+struct PostWs {        // mega_postprocess_batched: the merges' nine arrays (mboxes / mscores: the candidates), the mask
+  AugWs a; u64* mask;
+  size_t bytes;
+};
+PostWs post_carve(void* ws, int B, int R, int NC) {
+  WsCarver c(ws);
+  return {aug_ws_carve(c, (size_t)B * (NC - 1) * R, (size_t)B * (NC - 1)), nms_carve(c, B * (NC - 1), R), c.bytes};
+}
 
 }  // namespace
 
 // ================================================================================================ C ABI
 // Workspace size for mega_nms_sorted / rpn / post paths (bytes).
 extern "C" size_t mega_nms_workspace_bytes(int P, int nmax) {
-  const size_t cb = (size_t)cdiv(nmax, 64);
-  return align_up((size_t)P * nmax * cb * sizeof(u64), 256) + 256;
+  WsCarver c(nullptr);
+  nms_carve(c, P, nmax);
+  return c.bytes;
 }
 
 // Greedy NMS over P independent, already score-sorted problems.
@@ -796,7 +815,8 @@ extern "C" int mega_nms_sorted(const float* boxes, const int* counts, const unsi
                        thr, strict_gt, max_keep, keep_pos, keep_cnt, flags);
     return mega_check_launch();
   }
-  u64* mask = (u64*)ws;
+  WsCarver c(ws);
+  u64* mask = nms_carve(c, P, nmax);
   hipLaunchKernelGGL(nms_mask_kernel, dim3(cb, cb, P), dim3(64), 0, st, (const float4*)boxes, counts, mask, nmax, cb,
                      thr, strict_gt);
   hipLaunchKernelGGL(nms_scan_kernel, dim3(P), dim3(64), 0, st, mask, counts, valid, order, nmax, cb, max_keep,
@@ -806,11 +826,7 @@ extern "C" int mega_nms_sorted(const float* boxes, const int* counts, const unsi
 
 // Drop-in core of mega_core._C.nms (csrc/nms.h:10-28): unsorted dets/scores -> kept ORIGINAL indices,
 // ascending (nms.cu:127-130 / nms_cpu.cpp:64), int64, plus the count (device).
-//   ws layout: sorted boxes | sorted order | keep_pos | flags | counts | mask
-extern "C" size_t mega_nms_full_workspace_bytes(int n) {
-  return align_up((size_t)n * 16, 256) + align_up((size_t)n * 4, 256) * 2 + align_up((size_t)n, 256) + 256 +
-         mega_nms_workspace_bytes(1, n);
-}
+extern "C" size_t mega_nms_full_workspace_bytes(int n) { return nms_full_carve(nullptr, n).bytes; }
 
 extern "C" int mega_nms(const float* dets, const float* scores, int n, float thr, int strict_gt, long long* keep_out,
                         int* keep_cnt, void* ws, size_t ws_bytes, void* stream) {
@@ -820,32 +836,23 @@ extern "C" int mega_nms(const float* dets, const float* scores, int n, float thr
   if (n > SORT_MAX) return MEGA_ERR_ARG;
   if (ws_bytes < mega_nms_full_workspace_bytes(n)) return MEGA_ERR_WS;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)ws;
-  float4* sboxes = (float4*)w; w += align_up((size_t)n * 16, 256);
-  int* order = (int*)w; w += align_up((size_t)n * 4, 256);
-  int* keep_pos = (int*)w; w += align_up((size_t)n * 4, 256);
-  unsigned char* flags = w; w += align_up((size_t)n, 256);
-  int* counts = (int*)w; w += 256;
-  void* mws = w;
+  const NmsFullWs w = nms_full_carve(ws, n);
   int ns = 64;
   while (ns < n) ns <<= 1;
   // (a kernel, not hipMemsetAsync: captured into a hipGraph a memset NODE was seen to run out of order, see NOTES)
-  hipLaunchKernelGGL(set_int_kernel, dim3(cdiv(n, 1024)), dim3(256), 0, st, counts, n, flags, n);
+  hipLaunchKernelGGL(set_int_kernel, dim3(cdiv(n, 1024)), dim3(256), 0, st, w.counts, n, w.flags, n);
   hipLaunchKernelGGL(sort_boxes_kernel, dim3(1), dim3(1024), (size_t)ns * sizeof(u64), st, scores, (const float4*)dets,
-                     (const int*)nullptr, n, sboxes, (float*)nullptr, order);
-  int rc = mega_nms_sorted((const float*)sboxes, counts, nullptr, order, 1, n, thr, strict_gt, n, keep_pos, keep_cnt,
-                           flags, mws, mega_nms_workspace_bytes(1, n), stream);
+                     (const int*)nullptr, n, w.sboxes, (float*)nullptr, w.order);
+  int rc = mega_nms_sorted((const float*)w.sboxes, w.counts, nullptr, w.order, 1, n, thr, strict_gt, n, w.keep_pos,
+                           keep_cnt, w.flags, w.mask, mega_nms_workspace_bytes(1, n), stream);
   if (rc != MEGA_OK) return rc;
-  hipLaunchKernelGGL(compact_flags_kernel, dim3(1), dim3(1024), 0, st, flags, n, keep_out, keep_cnt);
+  hipLaunchKernelGGL(compact_flags_kernel, dim3(1), dim3(1024), 0, st, w.flags, n, keep_out, keep_cnt);
   return mega_check_launch();
 }
 
 // RPN proposal selection for B frames (rpn/inference.py:76-123).
 //   rpn_out [B][Hf*Wf][ldc] f32; cell_anchors [A][4]; outputs proposals [B][post_nms][4], prop_scores, prop_cnt[B]
-extern "C" size_t mega_rpn_select_workspace_bytes(int B, int pre_nms) {
-  return align_up((size_t)B * pre_nms * 16, 256) + align_up((size_t)B * pre_nms * 4, 256) * 3 +
-         align_up((size_t)B * pre_nms, 256) + align_up((size_t)B * 4, 256) + mega_nms_workspace_bytes(B, pre_nms);
-}
+extern "C" size_t mega_rpn_select_workspace_bytes(int B, int pre_nms) { return rpn_carve(nullptr, B, pre_nms).bytes; }
 
 // prop_index [B][post_nms_top_n] (optional): the flat anchor index (y * Wf + x) * A + a of every kept proposal, -1 in
 // the unused rows -- the "proposal indices after NMS" in the reference's (N, H, W, A) flattening (rpn/utils.py:10-14).
@@ -863,18 +870,11 @@ extern "C" int mega_rpn_select_idx(const float* rpn_out, const float* cell_ancho
   if (k > SORT_MAX) return MEGA_ERR_ARG;
   if (ws_bytes < mega_rpn_select_workspace_bytes(B, k)) return MEGA_ERR_WS;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)ws;
-  float4* sboxes = (float4*)w; w += align_up((size_t)B * k * 16, 256);
-  float* sscores = (float*)w; w += align_up((size_t)B * k * 4, 256);
-  int* keep_pos = (int*)w; w += align_up((size_t)B * k * 4, 256);
-  int* aidx = (int*)w; w += align_up((size_t)B * k * 4, 256);
-  unsigned char* valid = w; w += align_up((size_t)B * k, 256);
-  int* counts = (int*)w; w += align_up((size_t)B * 4, 256);
-  void* mws = w;
+  const RpnWs w = rpn_carve(ws, B, k);
   RpnParams p;
-  p.anchor_idx = prop_index ? aidx : nullptr;
-  p.rpn_out = rpn_out; p.cell_anchors = cell_anchors; p.boxes = sboxes; p.scores = sscores; p.valid = valid;
-  p.counts = counts; p.B = B; p.Hf = Hf; p.Wf = Wf; p.A = A; p.ldc = ldc; p.stride = anchor_stride; p.k = k;
+  p.anchor_idx = prop_index ? w.aidx : nullptr;
+  p.rpn_out = rpn_out; p.cell_anchors = cell_anchors; p.boxes = w.sboxes; p.scores = w.sscores; p.valid = w.valid;
+  p.counts = w.counts; p.B = B; p.Hf = Hf; p.Wf = Wf; p.A = A; p.ldc = ldc; p.stride = anchor_stride; p.k = k;
   p.kmax = k; p.im_w = im_w; p.im_h = im_h; p.min_size = min_size; p.clip = logf(1000.f / 16.f);
   int ns = 64;
   while (ns < k) ns <<= 1;
@@ -882,11 +882,11 @@ extern "C" int mega_rpn_select_idx(const float* rpn_out, const float* cell_ancho
   (void)hipFuncSetAttribute((const void*)rpn_topk_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SORT_MAX * (int)sizeof(u64));
   hipLaunchKernelGGL(rpn_topk_decode_kernel, dim3(B), dim3(1024), (size_t)ns * sizeof(u64), st, p);
-  int rc = mega_nms_sorted((const float*)sboxes, counts, valid, nullptr, B, k, nms_thresh, strict_gt, post_nms_top_n,
-                           keep_pos, prop_cnt, nullptr, mws, mega_nms_workspace_bytes(B, k), stream);
+  int rc = mega_nms_sorted((const float*)w.sboxes, w.counts, w.valid, nullptr, B, k, nms_thresh, strict_gt,
+                           post_nms_top_n, w.keep_pos, prop_cnt, nullptr, w.mask, mega_nms_workspace_bytes(B, k), stream);
   if (rc != MEGA_OK) return rc;
   // keep_pos rows are post_nms_top_n wide
-  hipLaunchKernelGGL(gather_kept_kernel, dim3(B), dim3(256), 0, st, sboxes, sscores, keep_pos, prop_cnt, k,
+  hipLaunchKernelGGL(gather_kept_kernel, dim3(B), dim3(256), 0, st, w.sboxes, w.sscores, w.keep_pos, prop_cnt, k,
                      post_nms_top_n, (float4*)proposals, prop_scores, (const int*)p.anchor_idx, prop_index);
   return mega_check_launch();
 }
@@ -895,9 +895,7 @@ extern "C" int mega_rpn_select_idx(const float* rpn_out, const float* cell_ancho
 //   logits [R][NC], deltas [R][NC*4], props [R][4], nprop (device int, may be null -> R)
 //   outputs (capacity (NC-1)*R rows): out_boxes [.][4], out_scores, out_labels (i64), out_cnt (device int)
 extern "C" size_t mega_postprocess_batched_workspace_bytes(int B, int R, int NC) {
-  const size_t m = (size_t)B * (NC - 1) * R;
-  return 2 * align_up(m * 16, 256) + 4 * align_up(m * 4, 256) + align_up(m, 256) +
-         2 * align_up((size_t)B * (NC - 1) * 4, 256) + mega_nms_workspace_bytes(B * (NC - 1), R);
+  return post_carve(nullptr, B, R, NC).bytes;
 }
 
 extern "C" size_t mega_postprocess_workspace_bytes(int R, int NC) {
@@ -918,30 +916,20 @@ extern "C" int mega_postprocess_batched(const float* logits, const float* deltas
   hipStream_t st = (hipStream_t)stream;
   const int C1 = NC - 1;
   const int P = B * C1;                      // (image, class) problems, image-major: the layout of every array below
-  const size_t m = (size_t)P * R;
-  unsigned char* w = (unsigned char*)ws;
-  float4* cboxes = (float4*)w; w += align_up(m * 16, 256);
-  float4* sboxes = (float4*)w; w += align_up(m * 16, 256);
-  float* cscores = (float*)w; w += align_up(m * 4, 256);
-  int* order = (int*)w; w += align_up(m * 4, 256);
-  int* keep_pos = (int*)w; w += align_up(m * 4, 256);
-  int* tmp_idx = (int*)w; w += align_up(m * 4, 256);
-  unsigned char* flags = w; w += align_up(m, 256);
-  int* counts = (int*)w; w += align_up((size_t)P * 4, 256);
-  int* keep_cnt = (int*)w; w += align_up((size_t)P * 4, 256);
-  void* mws = w;
+  const PostWs pw = post_carve(ws, B, R, NC);
+  const AugWs& w = pw.a;             // mboxes / mscores: the candidates
   // (the kept flags are zeroed by post_prepare_kernel, one store per candidate it writes anyway: a hipMemsetAsync here
   // becomes a memset NODE when the call is captured into a hipGraph, and a captured FGFA step whose graph holds that node
   // produced history-dependent kept sets after a restart -- see NOTES, traps)
   hipLaunchKernelGGL(post_prepare_kernel, dim3(cdiv(R, 64), B), dim3(64), 0, st, logits, deltas, (const float4*)props,
-                     nprop, R, NC, wx, wy, ww, wh, logf(1000.f / 16.f), im_w, im_h, score_thresh, cboxes, cscores,
-                     probs_out, flags);
-  hipLaunchKernelGGL(post_sort_kernel, dim3(P), dim3(256), 0, st, cboxes, cscores, R, sboxes, order, counts);
-  int rc = mega_nms_sorted((const float*)sboxes, counts, nullptr, order, P, R, nms_thresh, strict_gt, R, keep_pos,
-                           keep_cnt, flags, mws, mega_nms_workspace_bytes(P, R), stream);
+                     nprop, R, NC, wx, wy, ww, wh, logf(1000.f / 16.f), im_w, im_h, score_thresh, w.mboxes, w.mscores,
+                     probs_out, w.flags);
+  hipLaunchKernelGGL(post_sort_kernel, dim3(P), dim3(256), 0, st, w.mboxes, w.mscores, R, w.sboxes, w.order, w.counts);
+  int rc = mega_nms_sorted((const float*)w.sboxes, w.counts, nullptr, w.order, P, R, nms_thresh, strict_gt, R, w.keep_pos,
+                           w.keep_cnt, w.flags, pw.mask, mega_nms_workspace_bytes(P, R), stream);
   if (rc != MEGA_OK) return rc;
-  hipLaunchKernelGGL(post_finalize_kernel, dim3(B), dim3(1024), 0, st, flags, cboxes, cscores, C1, R, max_det,
-                     (float4*)out_boxes, out_scores, out_labels, out_cnt, tmp_idx);
+  hipLaunchKernelGGL(post_finalize_kernel, dim3(B), dim3(1024), 0, st, w.flags, w.mboxes, w.mscores, C1, R, max_det,
+                     (float4*)out_boxes, out_scores, out_labels, out_cnt, w.tmp_idx);
   return mega_check_launch();
 }
 

@@ -130,6 +130,20 @@ static inline int mega_check_launch() {
   return e == hipSuccess ? MEGA_OK : MEGA_ERR_LAUNCH;
 }
 
+// After the launch of a kernel that reports "a limit was hit" through a device status word (zeroed on the stream before
+// the launch): checks the launch, reads the word back on the stream and waits for it.
+static inline int mega_check_status(const int* status, hipStream_t st) {
+  const int rc = mega_check_launch();
+  if (rc != MEGA_OK) return rc;
+  int h_status = 0;
+  if (hipMemcpyAsync(&h_status, status, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    g_mega_last_hip_error = (int)hipGetLastError();
+    return MEGA_ERR_LAUNCH;
+  }
+  return h_status ? MEGA_ERR_LIMIT : MEGA_OK;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Library-internal launchers of boxes.hip, shared with bbox_aug.hip and soft_nms.hip (not part of the C ABI):

@@ -5,6 +5,7 @@
 //
 // Built with -ffp-contract=off: every f32 operation of the rescale / IoU rounds exactly like the reference's separate
 // torch ops (no FMA contraction).
+#include "box_math.h"
 #include "common.h"
 
 namespace {
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(64 * PR_WAVES) void proposal_recall_match_kernel(
       const float4 b = box[order[d0 + p]];
       // BoxList.resize: x * ratio_w, y * ratio_h in f32; BoxList.area: (x2 - x1 + 1) * (y2 - y1 + 1)
       pb[k] = make_float4(b.x * rw, b.y * rh, b.z * rw, b.w * rh);
-      pa[k] = (pb[k].z - pb[k].x + 1.0f) * (pb[k].w - pb[k].y + 1.0f);
+      pa[k] = box_area1(pb[k]);
     } else {
       pb[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       pa[k] = 0.f;
@@ -84,15 +85,11 @@ __global__ __launch_bounds__(64 * PR_WAVES) void proposal_recall_match_kernel(
         live &= live - 1;
         const int g = c * 64 + t;
         const float4 gb = gt_box[g0 + g];
-        const float ga = (gb.z - gb.x + 1.0f) * (gb.w - gb.y + 1.0f);
+        const float ga = box_area1(gb);
 #pragma unroll
         for (int k = 0; k < PR_SLOTS; ++k) {
           if ((prem >> k) & 1) continue;
-          const float ltx = fmaxf(pb[k].x, gb.x), lty = fmaxf(pb[k].y, gb.y);
-          const float rbx = fminf(pb[k].z, gb.z), rby = fminf(pb[k].w, gb.w);
-          const float w = fmaxf(rbx - ltx + 1.0f, 0.0f), h = fmaxf(rby - lty + 1.0f, 0.0f);
-          const float inter = w * h;
-          const float v = inter / ((pa[k] + ga) - inter);
+          const float v = box_iou1(pb[k], pa[k], gb, ga);
           // g ascends, then k: a strict > keeps the lane's first maximum (a NaN never wins)
           if (v > best.iou) {
             best.iou = v;

@@ -5,7 +5,7 @@
 //   2. the alive box with the largest S, on equal S the earliest frame, then the smallest position; backtrack through P;
 //   3. rescore the path: avg -> f32(S* / path length) (f64 division), max -> the largest original score on the path;
 //   4. in every path frame remove the path box and every alive box k with iou(k, path box) > nms_iou (suppressed).
-// IoU: the legacy +1 convention in f32, this operation order (built with -ffp-contract=off: no FMA contraction):
+// IoU: box_math.h's box_iou1 -- the legacy +1 convention in f32 (built with -ffp-contract=off: no FMA contraction):
 //   area(b) = (x2 - x1 + 1) * (y2 - y1 + 1);  w = max(min(x2) - max(x1) + 1, 0), h likewise;  inter / ((aa + ab) - inter)
 // A NaN IoU neither links nor suppresses.
 //
@@ -18,7 +18,9 @@
 // per-frame best (S, position) is kept for step 2; its reduction over frames takes the earliest frame on equal S.
 #include <climits>
 
+#include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -26,17 +28,6 @@ constexpr int SN_THREADS = 256;
 constexpr int SN_WAVES = SN_THREADS / 64;
 constexpr unsigned char SN_ALIVE = 1;
 constexpr unsigned char SN_PATH = 2;
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-__device__ __forceinline__ float sn_iou(float4 a, float4 b) {
-  const float aa = (a.z - a.x + 1.0f) * (a.w - a.y + 1.0f);
-  const float ab = (b.z - b.x + 1.0f) * (b.w - b.y + 1.0f);
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x) + 1.0f, 0.0f);
-  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y) + 1.0f, 0.0f);
-  const float inter = w * h;
-  return inter / ((aa + ab) - inter);
-}
 
 // (s, p) beats (bs, bp): larger S, on equal S the smaller index.  The "none" value is (-inf, INT_MAX).
 __device__ __forceinline__ bool sn_better(double s, int p, double bs, int bp) { return s > bs || (s == bs && p < bp); }
@@ -85,7 +76,7 @@ __device__ bool sn_frame_step(const float4* __restrict__ box, const float* __res
       const float4 bi = box[a0 + i];
       for (int j = r; j < np; j += g) {
         if (!(state[p0 + j] & SN_ALIVE)) continue;
-        if (sn_iou(box[p0 + j], bi) > link) {
+        if (box_iou1(box[p0 + j], bi) > link) {
           const double sj = S[p0 + j];
           if (sj > bs) { bs = sj; bj = j; }
         }
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(SN_THREADS) void seq_nms_kernel(
         const int p = path_pos[seg0 + t];
         const float4 pb = box[a + p];
         for (int k = 0; k < nb; ++k)
-          if (k != p && (state[a + k] & SN_ALIVE) && sn_iou(box[a + k], pb) > nms) state[a + k] = 0;
+          if (k != p && (state[a + k] & SN_ALIVE) && box_iou1(box[a + k], pb) > nms) state[a + k] = 0;
         state[a + p] = SN_PATH;
         new_score[a + p] = val;
       }
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(SN_THREADS) void seq_nms_kernel(
           if (k == p) {
             state[a + p] = SN_PATH;
             new_score[a + p] = val;
-          } else if ((state[a + k] & SN_ALIVE) && sn_iou(box[a + k], pb) > nms) {
+          } else if ((state[a + k] & SN_ALIVE) && box_iou1(box[a + k], pb) > nms) {
             state[a + k] = 0;
           }
         }
@@ -223,12 +214,22 @@ __global__ __launch_bounds__(SN_THREADS) void seq_nms_kernel(
   }
 }
 
+struct SnWorkspace {     // in this order (a braced list is evaluated left to right)
+  double* S; int* P; double* fbS; int* fbP; int* path_pos; int* status;
+  size_t bytes;
+};
+
+SnWorkspace sn_carve(void* ws, size_t N, size_t segs) {
+  WsCarver c(ws);
+  return {c.take<double>(N), c.take<int>(N), c.take<double>(segs), c.take<int>(segs), c.take<int>(segs), c.take<int>(1),
+          c.bytes};
+}
+
 }  // namespace
 
 extern "C" size_t mega_seq_nms_workspace_bytes(long long N, long long segs) {
   if (N <= 0 || segs <= 0) return 0;
-  return align_up((size_t)N * sizeof(double), 256) + align_up((size_t)N * sizeof(int), 256) +
-         align_up((size_t)segs * sizeof(double), 256) + 2 * align_up((size_t)segs * sizeof(int), 256) + 256;
+  return sn_carve(nullptr, N, segs).bytes;
 }
 
 extern "C" int mega_seq_nms(const float* box, const float* score, const long long* seg_off, const int* tasks, int T,
@@ -242,29 +243,10 @@ extern "C" int mega_seq_nms(const float* box, const float* score, const long lon
   if (N > 0x7fffffffLL || T > 0x7fffffff / 3) return MEGA_ERR_ARG;
   const long long segs = (long long)C * F;
   if (ws_bytes < mega_seq_nms_workspace_bytes(N, segs)) return MEGA_ERR_WS;
-  unsigned char* w = (unsigned char*)ws;
-  double* S = (double*)w;
-  w += align_up((size_t)N * sizeof(double), 256);
-  int* P = (int*)w;
-  w += align_up((size_t)N * sizeof(int), 256);
-  double* fbS = (double*)w;
-  w += align_up((size_t)segs * sizeof(double), 256);
-  int* fbP = (int*)w;
-  w += align_up((size_t)segs * sizeof(int), 256);
-  int* path_pos = (int*)w;
-  w += align_up((size_t)segs * sizeof(int), 256);
-  int* status = (int*)w;
+  const SnWorkspace w = sn_carve(ws, N, segs);
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) return MEGA_ERR_LAUNCH;
+  if (hipMemsetAsync(w.status, 0, sizeof(int), st) != hipSuccess) return MEGA_ERR_LAUNCH;
   hipLaunchKernelGGL(seq_nms_kernel, dim3(T), dim3(SN_THREADS), 0, st, (const float4*)box, score, seg_off, tasks, F,
-                     link_iou, nms_iou, rescore_max, keep, new_score, stats, S, P, fbS, fbP, path_pos, status);
-  int rc = mega_check_launch();
-  if (rc != MEGA_OK) return rc;
-  int h_status = 0;
-  if (hipMemcpyAsync(&h_status, status, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_mega_last_hip_error = (int)hipGetLastError();
-    return MEGA_ERR_LAUNCH;
-  }
-  return h_status ? MEGA_ERR_LIMIT : MEGA_OK;
+                     link_iou, nms_iou, rescore_max, keep, new_score, stats, w.S, w.P, w.fbS, w.fbP, w.path_pos, w.status);
+  return mega_check_status(w.status, st);
 }

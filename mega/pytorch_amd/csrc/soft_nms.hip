@@ -60,7 +60,7 @@ __global__ __launch_bounds__(1024) void soft_nms_kernel(const float4* __restrict
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       if ((alive >> j) & 1u) {
-        const u64 key = ((u64)aug_f32_sortable(sc[j]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)(j * T + tid));
+        const u64 key = ((u64)f32_sortable(sc[j]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)(j * T + tid));
         if (key > best) { best = key; bb = box[j]; }
       }
     }
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(1024) void soft_nms_kernel(const float4* __restrict
         keep_idx[base + nk] = widx;
         continue;
       }
-      const float o = aug_iou(mb, box[j]);
+      const float o = box_iou1(mb, box[j]);
       float w = 1.f;
       if (o == o) {                            // a NaN IoU does not decay
         if (method == 2) w = expf(-(o * o) / sigma);
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void box_vote_kernel(const float4* __restrict_
     const float s = mscores[base + j];
     if (!(s >= 0.f)) continue;
     const float4 b = mboxes[base + j];
-    if (j == k || aug_iou(kb, b) >= vote_thresh) {      // (NaN >= thr is false: a NaN IoU does not vote)
+    if (j == k || box_iou1(kb, b) >= vote_thresh) {      // (NaN >= thr is false: a NaN IoU does not vote)
       const double sd = (double)s;
       sx1 += sd * (double)b.x;
       sy1 += sd * (double)b.y;
@@ -169,12 +169,21 @@ __global__ __launch_bounds__(256) void box_vote_kernel(const float4* __restrict_
   }
 }
 
+// The bbox_aug workspace, then the voted boxes [m][4] and the final scores [m].
+struct SoftWs {
+  AugWs aug; float4* vboxes; float* fscores;
+  size_t bytes;
+};
+
+SoftWs soft_ws_carve(void* ws, size_t m, size_t P) {
+  WsCarver c(ws);
+  return {aug_ws_carve(c, m, P), c.take<float4>(m), c.take<float>(m), c.bytes};
+}
+
 }  // namespace
 
-// The bbox_aug workspace, then the voted boxes [m][4] and the final scores [m].
 extern "C" size_t mega_soft_merge_workspace_bytes(int F, int K, int R, int NC) {
-  const size_t m = (size_t)F * (NC - 1) * K * R;
-  return aug_ws_bytes(m, (size_t)F * (NC - 1)) + aug_align_up(m * 16, 256) + aug_align_up(m * 4, 256);
+  return soft_ws_carve(nullptr, (size_t)F * (NC - 1) * K * R, (size_t)F * (NC - 1)).bytes;
 }
 
 extern "C" int mega_bbox_aug_merge(const float* cboxes, const float* cscores, int F, int K, int R, int NC,
@@ -205,10 +214,10 @@ extern "C" int mega_soft_merge(const float* cboxes, const float* cscores, int F,
   if (rc != MEGA_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int C1 = NC - 1, P = F * C1, KR = K * R;
-  const size_t m = (size_t)P * KR;
-  const AugWs w = aug_ws_carve(ws, m, (size_t)P);
-  float4* vboxes = (float4*)w.end;
-  float* fscores = (float*)(w.end + aug_align_up(m * 16, 256));
+  const SoftWs sw = soft_ws_carve(ws, (size_t)P * KR, (size_t)P);
+  const AugWs& w = sw.aug;
+  float4* vboxes = sw.vboxes;
+  float* fscores = sw.fscores;
   if (soft_method) {
     int T = (KR + 63) / 64 * 64;
     if (T > 1024) T = 1024;

@@ -6,8 +6,7 @@
 //   3. each candidate joins the open track with last frame < t of the largest iou(track's last box, candidate) > link_iou
 //      (strict; equal IoU: the track whose root has the smallest position in the frame-by-frame concatenation), or opens
 //      a new track with itself as the root.  A track extended or born in frame t is not available in frame t.
-// IoU: Seq-NMS's (the legacy +1 convention in f32, this operation order, built with -ffp-contract=off):
-//   area(b) = (x2 - x1 + 1) * (y2 - y1 + 1);  w = max(min(x2) - max(x1) + 1, 0), h likewise;  inter / ((aa + ab) - inter)
+// IoU: Seq-NMS's, box_math.h's box_iou1 (the legacy +1 convention in f32, built with -ffp-contract=off).
 // A NaN IoU never links.
 //
 // Task mapping: one 256-thread workgroup (4 waves of 64) per task, tasks in descending box count (the host orders them),
@@ -23,24 +22,15 @@
 // more than max_open tracks sets the status word instead (MEGA_ERR_LIMIT).
 #include <climits>
 
+#include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
 constexpr int LT_THREADS = 256;
 constexpr int LT_WAVES = LT_THREADS / 64;
 constexpr int LT_LDS_TRACKS = 1024;      // 44 bytes per entry: 44 KiB of LDS
-
-inline size_t lt_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-__device__ __forceinline__ float lt_iou(float4 a, float4 b) {
-  const float aa = (a.z - a.x + 1.0f) * (a.w - a.y + 1.0f);
-  const float ab = (b.z - b.x + 1.0f) * (b.w - b.y + 1.0f);
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x) + 1.0f, 0.0f);
-  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y) + 1.0f, 0.0f);
-  const float inter = w * h;
-  return inter / ((aa + ab) - inter);
-}
 
 struct LtEntry {
   float4 box;      // the track's last box
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(LT_THREADS) void link_tracks_kernel(
       int bpos = INT_MAX, bidx = -1;
       const auto consider = [&](int j, int last, float4 tb, int p) {
         if (last >= t) return;                            // extended in this frame
-        const float iou = lt_iou(tb, cb);
+        const float iou = box_iou1(tb, cb);
         if (iou > link && lt_better(iou, p, biou, bpos)) { biou = iou; bpos = p; bidx = j; }
       };
       // (two loops, so that each half of the table is read with its own kind of load)
@@ -222,18 +212,9 @@ struct LtWorkspace {
 LtWorkspace lt_carve(void* ws, int T, int max_open) {
   const size_t over = max_open > LT_LDS_TRACKS ? (size_t)(max_open - LT_LDS_TRACKS) : 0;
   const size_t n = (size_t)(T > 0 ? T : 0) * over;
-  unsigned char* w = (unsigned char*)ws;
-  LtWorkspace o;
-  o.box = (float4*)w;   w += lt_align_up(n * sizeof(float4), 256);
-  o.sum = (double*)w;   w += lt_align_up(n * sizeof(double), 256);
-  o.last = (int*)w;     w += lt_align_up(n * sizeof(int), 256);
-  o.root = (int*)w;     w += lt_align_up(n * sizeof(int), 256);
-  o.pos = (int*)w;      w += lt_align_up(n * sizeof(int), 256);
-  o.cnt = (int*)w;      w += lt_align_up(n * sizeof(int), 256);
-  o.mx = (float*)w;     w += lt_align_up(n * sizeof(float), 256);
-  o.status = (int*)w;   w += 256;
-  o.bytes = (size_t)(w - (unsigned char*)ws);
-  return o;
+  WsCarver c(ws);      // (a braced list is evaluated left to right: the struct's order)
+  return {c.take<float4>(n), c.take<double>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n),
+          c.take<float>(n), c.take<int>(1), c.bytes};
 }
 
 }  // namespace
@@ -262,13 +243,5 @@ extern "C" int mega_link_tracks(const float* box, const float* score, const int*
   hipLaunchKernelGGL(link_tracks_kernel, dim3(T), dim3(LT_THREADS), 0, st, (const float4*)box, score, pos, seg_off, tasks,
                      F, score_thresh, link_iou, max_gap, max_open, root, cnt, sum, mx, w.box, w.last, w.root, w.pos,
                      w.cnt, w.sum, w.mx, w.status);
-  int rc = mega_check_launch();
-  if (rc != MEGA_OK) return rc;
-  int h_status = 0;
-  if (hipMemcpyAsync(&h_status, w.status, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_mega_last_hip_error = (int)hipGetLastError();
-    return MEGA_ERR_LAUNCH;
-  }
-  return h_status ? MEGA_ERR_LIMIT : MEGA_OK;
+  return mega_check_status(w.status, st);
 }

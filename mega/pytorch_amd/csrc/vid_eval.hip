@@ -7,7 +7,9 @@
 //
 // Built with -ffp-contract=off: every f32 operation of the rescale / IoU rounds exactly like the reference's separate
 // torch ops (no FMA contraction).
+#include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -19,22 +21,17 @@ constexpr int AP_THREADS = 256;
 constexpr int AP_PER_THREAD = 4;
 constexpr int AP_CHUNK = AP_THREADS * AP_PER_THREAD;
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 __device__ __forceinline__ float wave_max_f(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 
-// One GT slot's IoU with the (rescaled, +1) detection box, boxlist_iou's operation order, f32.
-__device__ __forceinline__ float vid_iou(float px1, float py1, float px2, float py2, float pa, float4 g) {
-  const float gx2 = g.z + 1.0f, gy2 = g.w + 1.0f;
-  const float ga = (gx2 - g.x + 1.0f) * (gy2 - g.y + 1.0f);
-  const float ltx = fmaxf(px1, g.x), lty = fmaxf(py1, g.y);
-  const float rbx = fminf(px2, gx2), rby = fminf(py2, gy2);
-  const float w = fmaxf(rbx - ltx + 1.0f, 0.0f), h = fmaxf(rby - lty + 1.0f, 0.0f);
-  const float inter = w * h;
-  return inter / ((pa + ga) - inter);
+// One GT slot's IoU with the (rescaled, +1) detection box p of area pa: the GT box gets vid_eval.py:209-214's +1 on
+// x2 / y2 first, then boxlist_iou's operation order in f32 (box_math.h).
+__device__ __forceinline__ float vid_iou(float4 p, float pa, float4 g) {
+  g.z += 1.0f;
+  g.w += 1.0f;
+  return box_iou1(p, pa, g, box_area1(g));
 }
 
 // torch.max / torch.min / clamp(min=0) propagate NaN; fmaxf / fminf do not.  The reference's elementwise ops are
@@ -95,9 +92,8 @@ __global__ __launch_bounds__(64 * VE_WAVES) void vid_match_kernel(
     const float4 b = det_box[idx];
     const int L = det_label[idx];
     // BoxList.resize: x * ratio_w, y * ratio_h in f32; then vid_eval.py:209-214: x2 + 1, y2 + 1
-    const float px1 = b.x * rw, py1 = b.y * rh;
-    const float px2 = b.z * rw + 1.0f, py2 = b.w * rh + 1.0f;
-    const float pa = (px2 - px1 + 1.0f) * (py2 - py1 + 1.0f);
+    const float4 pb = make_float4(b.x * rw, b.y * rh, b.z * rw + 1.0f, b.w * rh + 1.0f);
+    const float pa = box_area1(pb);
 
     // pass 1: per-class maxima over ignored / non-ignored GT (selected ones included), the best candidate, NaN candidates
     float mx_ig = -1.0f, mx_nig = -1.0f, mx_cand = -INFINITY;
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(64 * VE_WAVES) void vid_match_kernel(
     for (int c = 0; c < nch; ++c) {
       const GtSlot s = c == 0 ? s0 : load_gt(gt_box, gt_label, gt_motion, g0, G, c, lo, hi);
       const bool same = s.valid && s.label == L;
-      const float v = same ? vid_iou(px1, py1, px2, py2, pa, s.box) : -1.0f;
+      const float v = same ? vid_iou(pb, pa, s.box) : -1.0f;
       const bool nn = same && !__builtin_isnan(v);
       mx_ig = fmaxf(mx_ig, wave_max_f(nn && s.ign ? v : -1.0f));
       mx_nig = fmaxf(mx_nig, wave_max_f(nn && !s.ign ? v : -1.0f));
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(64 * VE_WAVES) void vid_match_kernel(
       for (int c = 0; c < nch; ++c) {
         const GtSlot s = c == 0 ? s0 : load_gt(gt_box, gt_label, gt_motion, g0, G, c, lo, hi);
         const bool same = s.valid && s.label == L;
-        const float v = same ? vid_iou(px1, py1, px2, py2, pa, s.box) : 0.0f;
+        const float v = same ? vid_iou(pb, pa, s.box) : 0.0f;
         const u64 elig = __ballot(same && !((selected >> c) & 1));
         const u64 ign = __ballot(s.ign);
         for (int t = 0; t < 64; ++t) {
@@ -149,7 +145,7 @@ __global__ __launch_bounds__(64 * VE_WAVES) void vid_match_kernel(
       for (int c = 0; c < nch && chosen < 0; ++c) {
         const GtSlot s = c == 0 ? s0 : load_gt(gt_box, gt_label, gt_motion, g0, G, c, lo, hi);
         const bool same = s.valid && s.label == L;
-        const float v = same ? vid_iou(px1, py1, px2, py2, pa, s.box) : -1.0f;
+        const float v = same ? vid_iou(pb, pa, s.box) : -1.0f;
         const u64 tie = __ballot(same && !((selected >> c) & 1) && v == mx_cand);
         const u64 tie_nig = tie & __ballot(!s.ign);
         if (tie_nig) chosen = c * 64 + __builtin_ctzll(tie_nig);
@@ -343,12 +339,24 @@ __global__ __launch_bounds__(AP_THREADS) void vid_ap_kernel(const unsigned char*
   if (threadIdx.x == 0) ap[r * C + l] = ap_sum;
 }
 
+// The running tp / fp sums before every chunk: `slots` entries per motion range.
+struct ApWorkspace {
+  long long slots;
+  int* tp_carry; double* fp_carry;
+  size_t bytes;
+};
+
+ApWorkspace ap_carve(void* ws, long long N, int C, int R) {
+  WsCarver c(ws);
+  const long long slots = N / AP_CHUNK + C + 1;
+  return {slots, c.take<int>((size_t)R * slots), c.take<double>((size_t)R * slots), c.bytes};
+}
+
 }  // namespace
 
 extern "C" size_t mega_vid_eval_workspace_bytes(long long N, int C, int R) {
   if (N < 0 || C <= 0 || R <= 0) return 0;
-  const size_t slots = (size_t)(N / AP_CHUNK) + (size_t)C + 1;
-  return align_up((size_t)R * slots * sizeof(int), 256) + align_up((size_t)R * slots * sizeof(double), 256);
+  return ap_carve(nullptr, N, C, R).bytes;
 }
 
 extern "C" int mega_vid_eval_match(const float* det_box, const int* det_label, const long long* det_off, const int* order,
@@ -377,10 +385,8 @@ extern "C" int mega_vid_eval_ap(const unsigned char* match, const double* pred_i
   if (N > 0 && (!match || !pred_ignore || !gorder)) return MEGA_ERR_ARG;
   if (C > 65535 * 1024 || R > 65535) return MEGA_ERR_ARG;
   if (ws_bytes < mega_vid_eval_workspace_bytes(N, C, R)) return MEGA_ERR_WS;
-  const long long slots = N / AP_CHUNK + C + 1;
-  int* tpc = (int*)ws;
-  double* fpc = (double*)((unsigned char*)ws + align_up((size_t)R * slots * sizeof(int), 256));
+  const ApWorkspace w = ap_carve(ws, N, C, R);
   hipLaunchKernelGGL(vid_ap_kernel, dim3(C, R), dim3(AP_THREADS), 0, (hipStream_t)stream, match, pred_ignore, gorder,
-                     seg_off, n_pos, C, N, slots, tpc, fpc, ap);
+                     seg_off, n_pos, C, N, w.slots, w.tp_carry, w.fp_carry, ap);
   return mega_check_launch();
 }

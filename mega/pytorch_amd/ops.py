@@ -655,6 +655,29 @@ BBOX_AUG_MAX_VIEWS = 16
 BBOX_AUG_MAX_ROWS = 8192
 
 
+def _merge_setup(name, ws_bytes, cboxes, cscores, view_sizes, view_flips):
+    """What bbox_aug_merge and soft_merge share: shape and limit checks (ValueError texts start with `name`), outputs,
+    workspace (ws_bytes: the entry point's *_workspace_bytes) and the views as ctypes int arrays (they pass as the void
+    pointers) -> F, K, R, NC, (boxes, scores, labels, counts), [view_w, view_h, view_flip], ws, its bytes."""
+    K, F, C1, R = cscores.shape
+    if K != len(view_sizes) or K != len(view_flips):
+        raise ValueError("%s: %d views of candidates, %d sizes, %d flips" % (name, K, len(view_sizes), len(view_flips)))
+    if K > BBOX_AUG_MAX_VIEWS or K * R > BBOX_AUG_MAX_ROWS:
+        raise ValueError("%s: %d views x %d rows per class; the merge takes at most %d views and %d rows "
+                         "per (frame, class)" % (name, K, R, BBOX_AUG_MAX_VIEWS, BBOX_AUG_MAX_ROWS))
+    assert cboxes.shape == (K, F, C1, R, 4) and cboxes.dtype == torch.float32 and cscores.dtype == torch.float32
+    assert cboxes.is_contiguous() and cscores.is_contiguous()
+    dev = cboxes.device
+    cap = C1 * K * R
+    outs = (torch.empty((F, cap, 4), dtype=torch.float32, device=dev), torch.empty((F, cap), dtype=torch.float32, device=dev),
+            torch.empty((F, cap), dtype=torch.int64, device=dev), torch.zeros((F,), dtype=torch.int32, device=dev))
+    nb = ws_bytes(F, K, R, C1 + 1)
+    arr = ctypes.c_int * K
+    views = [arr(*[int(s[0]) for s in view_sizes]), arr(*[int(s[1]) for s in view_sizes]),
+             arr(*[1 if f else 0 for f in view_flips])]
+    return F, K, R, C1 + 1, outs, views, _ws(nb, dev), nb
+
+
 def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh, max_det, strict_gt=True):
     """Test-time box augmentation merge of F frames x K views (include/mega_hip.h mega_bbox_aug_merge).
     cboxes [K,F,NC-1,R,4] / cscores [K,F,NC-1,R] f32 (the candidates of every view, each in its own image), view_sizes
@@ -663,29 +686,10 @@ def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_th
     detections are the first counts[f] rows.  Raises ValueError beyond K = 16 views or K * R = 8192 rows per class."""
     _gpu(cboxes, cscores)
     lib = _lib.load()
-    K, F, C1, R = cscores.shape
-    if K != len(view_sizes) or K != len(view_flips):
-        raise ValueError("bbox_aug_merge: %d views of candidates, %d sizes, %d flips" % (K, len(view_sizes), len(view_flips)))
-    if K > BBOX_AUG_MAX_VIEWS or K * R > BBOX_AUG_MAX_ROWS:
-        raise ValueError("bbox_aug_merge: %d views x %d rows per class; the merge takes at most %d views and %d rows "
-                         "per (frame, class)" % (K, R, BBOX_AUG_MAX_VIEWS, BBOX_AUG_MAX_ROWS))
-    assert cboxes.shape == (K, F, C1, R, 4) and cboxes.dtype == torch.float32 and cscores.dtype == torch.float32
-    assert cboxes.is_contiguous() and cscores.is_contiguous()
-    dev = cboxes.device
-    cap = C1 * K * R
-    ob = torch.empty((F, cap, 4), dtype=torch.float32, device=dev)
-    os_ = torch.empty((F, cap), dtype=torch.float32, device=dev)
-    ol = torch.empty((F, cap), dtype=torch.int64, device=dev)
-    oc = torch.zeros((F,), dtype=torch.int32, device=dev)
-    nb = lib.mega_bbox_aug_merge_workspace_bytes(F, K, R, C1 + 1)
-    ws = _ws(nb, dev)
-    arr = ctypes.c_int * K
-    vw = arr(*[int(s[0]) for s in view_sizes])
-    vh = arr(*[int(s[1]) for s in view_sizes])
-    vf = arr(*[1 if f else 0 for f in view_flips])
+    F, K, R, NC, (ob, os_, ol, oc), (vw, vh, vf), ws, nb = _merge_setup(
+        "bbox_aug_merge", lib.mega_bbox_aug_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
     _tok = _pb("bbox_aug_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
-    rc = lib.mega_bbox_aug_merge(_ptr(cboxes), _ptr(cscores), F, K, R, C1 + 1, ctypes.cast(vw, ctypes.c_void_p),
-                                 ctypes.cast(vh, ctypes.c_void_p), ctypes.cast(vf, ctypes.c_void_p), float(score_thresh),
+    rc = lib.mega_bbox_aug_merge(_ptr(cboxes), _ptr(cscores), F, K, R, NC, vw, vh, vf, float(score_thresh),
                                  float(nms_thresh), int(strict_gt), int(max_det), _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc),
                                  _ptr(ws), nb, _stream())
     _pe(_tok)
@@ -704,7 +708,6 @@ def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh
     and limits as bbox_aug_merge; with soft_method None and vote False the result is bbox_aug_merge's, bit for bit."""
     _gpu(cboxes, cscores)
     lib = _lib.load()
-    K, F, C1, R = cscores.shape
     if soft_method not in SOFT_NMS_METHODS:
         raise ValueError("soft_merge: soft_method %r, not None, 'linear' or 'gaussian'" % (soft_method,))
     if vote_scoring not in BBOX_VOTE_SCORING:
@@ -713,28 +716,10 @@ def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh
         raise ValueError("soft_merge: sigma = %r must be > 0" % (sigma,))
     if not 0 < float(vote_thresh) <= 1:
         raise ValueError("soft_merge: vote_thresh = %r must be in (0, 1]" % (vote_thresh,))
-    if K != len(view_sizes) or K != len(view_flips):
-        raise ValueError("soft_merge: %d views of candidates, %d sizes, %d flips" % (K, len(view_sizes), len(view_flips)))
-    if K > BBOX_AUG_MAX_VIEWS or K * R > BBOX_AUG_MAX_ROWS:
-        raise ValueError("soft_merge: %d views x %d rows per class; the merge takes at most %d views and %d rows "
-                         "per (frame, class)" % (K, R, BBOX_AUG_MAX_VIEWS, BBOX_AUG_MAX_ROWS))
-    assert cboxes.shape == (K, F, C1, R, 4) and cboxes.dtype == torch.float32 and cscores.dtype == torch.float32
-    assert cboxes.is_contiguous() and cscores.is_contiguous()
-    dev = cboxes.device
-    cap = C1 * K * R
-    ob = torch.empty((F, cap, 4), dtype=torch.float32, device=dev)
-    os_ = torch.empty((F, cap), dtype=torch.float32, device=dev)
-    ol = torch.empty((F, cap), dtype=torch.int64, device=dev)
-    oc = torch.zeros((F,), dtype=torch.int32, device=dev)
-    nb = lib.mega_soft_merge_workspace_bytes(F, K, R, C1 + 1)
-    ws = _ws(nb, dev)
-    arr = ctypes.c_int * K
-    vw = arr(*[int(s[0]) for s in view_sizes])
-    vh = arr(*[int(s[1]) for s in view_sizes])
-    vf = arr(*[1 if f else 0 for f in view_flips])
+    F, K, R, NC, (ob, os_, ol, oc), (vw, vh, vf), ws, nb = _merge_setup(
+        "soft_merge", lib.mega_soft_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
     _tok = _pb("soft_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
-    rc = lib.mega_soft_merge(_ptr(cboxes), _ptr(cscores), F, K, R, C1 + 1, ctypes.cast(vw, ctypes.c_void_p),
-                             ctypes.cast(vh, ctypes.c_void_p), ctypes.cast(vf, ctypes.c_void_p), float(score_thresh),
+    rc = lib.mega_soft_merge(_ptr(cboxes), _ptr(cscores), F, K, R, NC, vw, vh, vf, float(score_thresh),
                              float(nms_thresh), int(strict_gt), SOFT_NMS_METHODS[soft_method], float(sigma),
                              1 if vote else 0, float(vote_thresh), BBOX_VOTE_SCORING[vote_scoring], int(max_det),
                              _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc), _ptr(ws), nb, _stream())
@@ -1491,6 +1476,17 @@ def proposal_recall_match(box, off, order, ratio, gt_box, gt_off, limits, max_li
 
 
 # ------------------------------------------------------------------------------------------------ Seq-NMS
+def _check_video_tensors(box, score, seg_off, tasks, F, C, pos=None):
+    """The tensor checks seq_nms and link_tracks share -> (N, T)."""
+    N, T = box.shape[0], tasks.shape[0]
+    for t, dt in ((box, torch.float32), (score, torch.float32), (seg_off, torch.int64), (tasks, torch.int32)) + \
+            (((pos, torch.int32),) if pos is not None else ()):
+        assert t.dtype == dt and t.is_contiguous()
+    assert box.shape == (N, 4) and score.shape == (N,) and seg_off.shape == (C * F + 1,) and tasks.shape == (T, 3)
+    assert pos is None or pos.shape == (N,)
+    return N, T
+
+
 def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     """Seq-NMS over T (video, class) tasks (include/mega_hip.h mega_seq_nms).  box [N,4] f32, score [N] f32 sorted class-
     major then frame, seg_off [C*F+1] i64, tasks [T,3] i32 (class, first frame, frame count), longest first.
@@ -1498,10 +1494,7 @@ def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     Synchronises the stream (the kernel's status word)."""
     _gpu(box, score, seg_off, tasks)
     lib = _lib.load()
-    N, T = box.shape[0], tasks.shape[0]
-    for t, dt in ((box, torch.float32), (score, torch.float32), (seg_off, torch.int64), (tasks, torch.int32)):
-        assert t.dtype == dt and t.is_contiguous()
-    assert box.shape == (N, 4) and score.shape == (N,) and seg_off.shape == (C * F + 1,) and tasks.shape == (T, 3)
+    N, T = _check_video_tensors(box, score, seg_off, tasks, F, C)
     dev = box.device
     keep = torch.empty(N, dtype=torch.uint8, device=dev)
     new_score = torch.zeros(N, dtype=torch.float32, device=dev)
@@ -1526,12 +1519,7 @@ def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, m
     cnt [N] i32, sum [N] f64, mx [N] f32, on the device.  Synchronises the stream (the kernel's status word)."""
     _gpu(box, score, pos, seg_off, tasks)
     lib = _lib.load()
-    N, T = box.shape[0], tasks.shape[0]
-    for t, dt in ((box, torch.float32), (score, torch.float32), (pos, torch.int32), (seg_off, torch.int64),
-                  (tasks, torch.int32)):
-        assert t.dtype == dt and t.is_contiguous()
-    assert box.shape == (N, 4) and score.shape == (N,) and pos.shape == (N,) and seg_off.shape == (C * F + 1,)
-    assert tasks.shape == (T, 3)
+    N, T = _check_video_tensors(box, score, seg_off, tasks, F, C, pos)
     dev = box.device
     root = torch.full((N,), -1, dtype=torch.int64, device=dev)
     cnt = torch.zeros(N, dtype=torch.int32, device=dev)

@@ -36,33 +36,10 @@ device, one workgroup per (video, class) task with an incremental DP (csrc/seq_n
 import numpy as np
 import torch
 
-from . import vid_eval
+from . import flat
 from .structures import BoxList
 
 RESCORE_MODES = ("avg", "max")
-
-
-def _video_ranges(videos, F):
-    """(start, length) int64 arrays from (start, length) pairs or {"start", "seg_len"} records; ValueError unless they
-    partition [0, F) into contiguous ranges, in order."""
-    vs, vl = [], []
-    for v in videos:
-        if isinstance(v, dict):
-            s, n = v["start"], v["seg_len"]
-        else:
-            s, n = v
-        vs.append(int(s))
-        vl.append(int(n))
-    vs, vl = np.asarray(vs, np.int64), np.asarray(vl, np.int64)
-    pos = 0
-    for s, n in zip(vs, vl):
-        if s != pos or n < 0:
-            raise ValueError("seq_nms: the videos must partition the %d frames into contiguous ranges in order "
-                             "(a video starts at %d, expected %d, length %d)" % (F, s, pos, n))
-        pos += n
-    if pos != F:
-        raise ValueError("seq_nms: the videos cover %d frames, the predictions hold %d" % (pos, F))
-    return vs, vl
 
 
 def check_params(link_iou, nms_iou, rescore):
@@ -75,23 +52,8 @@ def check_params(link_iou, nms_iou, rescore):
 
 
 def pack(predictions, videos):
-    """Host checks and flat arrays: dict of counts [F], off [F+1], boxes [N,4] f32, scores [N] f32 (-0 -> +0), labels [N]
-    i64, video start / length [V] i64, C (classes: max label + 1)."""
-    F = len(predictions)
-    counts, off, boxes, scores, labels = vid_eval.concat_predictions(predictions)
-    vs, vl = _video_ranges(videos, F)
-    N = int(off[-1])
-    if not np.isfinite(boxes).all():
-        raise ValueError("seq_nms: a prediction box is not finite")
-    if np.isnan(scores).any() or (scores < 0).any():
-        raise ValueError("seq_nms: a prediction score is negative or NaN")
-    if N and labels.min() < 0:
-        raise ValueError("seq_nms: negative class label")
-    C = int(labels.max()) + 1 if N else 0
-    if N > 0x7fffffff or C * F >= 0x7fffffff:
-        raise ValueError("seq_nms: %d boxes, %d classes x %d frames: too many" % (N, C, F))
-    return {"F": F, "N": N, "C": C, "counts": counts, "off": off, "boxes": boxes, "scores": scores + np.float32(0),
-            "labels": labels, "video_start": vs, "video_len": vl}
+    """flat.pack with this module's error prefix (tracks reuses it, prefix included)."""
+    return flat.pack(predictions, videos, "seq_nms")
 
 
 def run(predictions, videos, link_iou=0.5, nms_iou=0.3, rescore="avg", device="cuda", with_stats=False):
@@ -100,8 +62,7 @@ def run(predictions, videos, link_iou=0.5, nms_iou=0.3, rescore="avg", device="c
     and "stats" [T,2] (iterations, DP frame steps) per task, longest task first."""
     link, nms = check_params(link_iou, nms_iou, rescore)
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("seq_nms runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(dev, "seq_nms", device)
     pk = pack(predictions, videos)
     F, N, C = pk["F"], pk["N"], pk["C"]
     out = {"packed": pk, "keep": np.zeros(N, bool), "scores": np.zeros(N, np.float32)}
@@ -110,26 +71,11 @@ def run(predictions, videos, link_iou=0.5, nms_iou=0.3, rescore="avg", device="c
     if N == 0:
         return out
     from . import ops
-    buf, layout = vid_eval.one_buffer([("box", pk["boxes"]), ("score", pk["scores"]), ("label", pk["labels"]),
-                                       ("count", pk["counts"]), ("vs", pk["video_start"]), ("vl", pk["video_len"])])
-    t = vid_eval.device_views(torch.from_numpy(buf).to(dev), layout)
     with torch.cuda.device(dev):
-        # (class, frame) segments: a stable sort by class * F + frame keeps each frame's boxes in position order
-        fid = torch.repeat_interleave(torch.arange(F, device=dev), t["count"], output_size=N)
-        key = t["label"] * F + fid
-        order = torch.sort(key, stable=True).indices
-        seg_off = torch.zeros(C * F + 1, dtype=torch.int64, device=dev)
-        seg_off[1:] = torch.cumsum(torch.bincount(key, minlength=C * F), 0)
-        box_s = t["box"][order].contiguous()
-        score_s = t["score"][order].contiguous()
-        # tasks: every (class, video) with a box, the most boxes first (ties: class, then video)
-        cls = torch.arange(C, device=dev)[:, None] * F
-        first = seg_off[cls + t["vs"][None, :]]
-        cnt = (seg_off[cls + (t["vs"] + t["vl"])[None, :]] - first).reshape(-1)
-        ids = torch.nonzero(cnt > 0).reshape(-1)
-        ids = ids[torch.sort(cnt[ids], descending=True, stable=True).indices]
-        V = t["vs"].shape[0]
-        tasks = torch.stack([ids // V, t["vs"][ids % V], t["vl"][ids % V]], 1).to(torch.int32).contiguous()
+        v = flat.video_tasks(pk, dev, by_score=False)      # each (class, frame) segment in position order
+        order, seg_off, tasks = v["order"], v["seg_off"], v["tasks"]
+        box_s = v["t"]["box"][order].contiguous()
+        score_s = v["t"]["score"][order].contiguous()
         keep_s, ns_s, stats = ops.seq_nms(box_s, score_s, seg_off, tasks, F, C, link, nms, rescore == "max")
         res = torch.empty(N * 5, dtype=torch.uint8, device=dev)      # [new scores f32 | keep u8]: one copy back
         res[:4 * N].view(torch.float32)[order] = ns_s

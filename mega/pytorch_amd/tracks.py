@@ -53,7 +53,7 @@ count / sum / max, then one copy back.
 import numpy as np
 import torch
 
-from . import seq_nms, vid_eval
+from . import flat, seq_nms, vid_eval
 from .structures import BoxList
 
 RESCORE_MODES = (None, "avg", "max")
@@ -85,36 +85,20 @@ def run(predictions, videos, score_thresh=0.05, link_iou=0.5, max_gap=1, min_len
     structured array, TABLE_DTYPE, rows by video then id), "packed": the packed input (seq_nms.pack)}."""
     thr, link, max_gap, min_len = check_params(score_thresh, link_iou, max_gap, min_len, rescore)
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("tracks runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(dev, "tracks", device)
     pk = seq_nms.pack(predictions, videos)
     F, N, C = pk["F"], pk["N"], pk["C"]
     out = {"packed": pk, "track_ids": np.full(N, -1, np.int64), "scores": pk["scores"].copy(), "table": _empty_table()}
     if N == 0:
         return out
     from . import ops
-    buf, layout = vid_eval.one_buffer([("box", pk["boxes"]), ("score", pk["scores"]), ("label", pk["labels"]),
-                                       ("count", pk["counts"]), ("vs", pk["video_start"]), ("vl", pk["video_len"])])
-    t = vid_eval.device_views(torch.from_numpy(buf).to(dev), layout)
     with torch.cuda.device(dev):
-        # (class, frame) segments, each in descending score, equal scores in position order: two stable sorts
-        fid = torch.repeat_interleave(torch.arange(F, device=dev), t["count"], output_size=N)
-        key = t["label"] * F + fid
-        by_score = torch.sort(t["score"], descending=True, stable=True).indices
-        order = by_score[torch.sort(key[by_score], stable=True).indices]
-        seg_off = torch.zeros(C * F + 1, dtype=torch.int64, device=dev)
-        seg_off[1:] = torch.cumsum(torch.bincount(key, minlength=C * F), 0)
+        # each (class, frame) segment in descending score, equal scores in position order
+        v = flat.video_tasks(pk, dev, by_score=True)
+        t, fid, order, seg_off, tasks, V = v["t"], v["fid"], v["order"], v["seg_off"], v["tasks"], v["V"]
         box_s = t["box"][order].contiguous()
         score_s = t["score"][order].contiguous()
         pos_s = order.to(torch.int32)
-        # tasks: every (class, video) with a box, the most boxes first (ties: class, then video)
-        cls = torch.arange(C, device=dev)[:, None] * F
-        first = seg_off[cls + t["vs"][None, :]]
-        cnt = (seg_off[cls + (t["vs"] + t["vl"])[None, :]] - first).reshape(-1)
-        tid = torch.nonzero(cnt > 0).reshape(-1)
-        tid = tid[torch.sort(cnt[tid], descending=True, stable=True).indices]
-        V = t["vs"].shape[0]
-        tasks = torch.stack([tid // V, t["vs"][tid % V], t["vl"][tid % V]], 1).to(torch.int32).contiguous()
         # open tracks of a task <= its boxes in max_gap + 2 consecutive frames (each open track's last box is one of them);
         # a window that runs over a video or class boundary only over-counts
         w = min(max_gap + 2, C * F)
@@ -137,7 +121,7 @@ def run(predictions, videos, score_thresh=0.05, link_iou=0.5, max_gap=1, min_len
         before = torch.cumsum(mark, 0) - mark                       # numbered roots with a smaller flat index
         off = torch.zeros(F + 1, dtype=torch.int64, device=dev)
         off[1:] = torch.cumsum(t["count"], 0)
-        vid_of_frame = torch.repeat_interleave(torch.arange(V, device=dev), t["vl"], output_size=F)
+        vid_of_frame = flat.frame_ids(t["vl"], dev, F)             # the same op over videos: each frame's video
         box_vid = vid_of_frame[fid]
         vid_base = before[off[t["vs"]].clamp(max=N - 1)]            # (a video without boxes is never looked up)
         ids = torch.where(numbered, before[rf] - vid_base[box_vid], torch.full_like(root, -1))

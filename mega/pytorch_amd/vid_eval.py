@@ -36,6 +36,7 @@ import xml.etree.ElementTree as ET
 import numpy as np
 import torch
 
+from . import flat
 from .structures import BoxList
 
 CLASSES = ['__background__',  # always index 0
@@ -196,44 +197,6 @@ def format_result(result, classes=CLASSES, motion_names=None):
     return s
 
 
-def concat_predictions(predictions):
-    """A list[BoxList] as flat host arrays: counts [F] i64, off [F+1] i64 (frame f's boxes are off[f] .. off[f+1]),
-    boxes [N,4] f32, scores [N] f32, labels [N] i64 (the fields "scores" / "labels")."""
-    F = len(predictions)
-    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
-    off = np.zeros(F + 1, np.int64)
-    off[1:] = np.cumsum(counts)
-    if off[-1]:
-        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
-        scores = torch.cat([p.get_field("scores").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
-        labels = torch.cat([p.get_field("labels").reshape(-1).to("cpu", torch.int64) for p in predictions]).numpy()
-    else:
-        boxes, scores, labels = np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64)
-    return counts, off, boxes, scores, labels
-
-
-def one_buffer(parts):
-    """[(name, ndarray)] -> (one u8 host buffer, 16-byte aligned, [(name, dtype, shape, byte offset)]) for a single
-    host-to-device copy; device_views() cuts the copied buffer back into tensors."""
-    layout, off = [], 0
-    for name, a in parts:
-        a = np.ascontiguousarray(a)
-        layout.append((name, a, off))
-        off += (a.nbytes + 15) // 16 * 16
-    buf = np.empty(max(off, 16), np.uint8)
-    for name, a, o in layout:
-        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
-    return buf, [(name, a.dtype, a.shape, o) for name, a, o in layout]
-
-
-def device_views(dbuf, layout):
-    t = {}
-    for name, dt, shape, o in layout:
-        n = int(np.prod(shape))
-        t[name] = dbuf[o:o + n * np.dtype(dt).itemsize].view(_torch_dtype(dt)).reshape(shape)
-    return t
-
-
 def _resize_ratios(predictions, groundtruth):
     """[F,2] f32 (width, height): BoxList.resize (bounding_box.py:95) to the annotation's frame size -- ratios as Python
     floats, applied in f32."""
@@ -243,13 +206,13 @@ def _resize_ratios(predictions, groundtruth):
 
 
 def _pack(predictions, groundtruth, motion_iou, motion_ranges):
-    """Flat host arrays of the whole evaluation, in one byte buffer (one host-to-device copy)."""
+    """The checked flat host arrays of the whole evaluation, [(name, ndarray)] for flat.upload, and the sizes."""
     F = len(predictions)
     if F == 0:
         raise ValueError("evaluate_detections: no predictions")
     if len(groundtruth) != F:
         raise ValueError("Length of gt and pred lists need to be same (%d predictions, %d GT frames)" % (F, len(groundtruth)))
-    counts, det_off, boxes, scores, labels = concat_predictions(predictions)
+    counts, det_off, boxes, scores, labels = flat.concat_predictions(predictions)
     N = int(det_off[-1])
     if not np.isfinite(boxes).all():
         raise ValueError("evaluate_detections: a prediction box is not finite")
@@ -289,14 +252,7 @@ def _pack(predictions, groundtruth, motion_iou, motion_ranges):
              ("ranges", ranges)]
     if motion is not None:
         parts.append(("gt_motion", motion))
-    buf, layout = one_buffer(parts)
-    meta = {"F": F, "N": N, "C": C, "max_gt": max_gt, "counts": counts}
-    return buf, layout, meta
-
-
-def _torch_dtype(dt):
-    return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
-            np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8}[np.dtype(dt)]
+    return parts, {"F": F, "N": N, "C": C, "max_gt": max_gt, "counts": counts}
 
 
 def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_only=False):
@@ -305,26 +261,19 @@ def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_on
     ap_only: copy back only ap (the per-detection arrays stay on the device and are freed)."""
     from . import ops
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(dev, "evaluate_detections", device)
     motion_ranges = MOTION_RANGES if motion_iou is not None else MOTION_RANGES[:1]
-    buf, layout, meta = _pack(predictions, groundtruth, motion_iou, motion_ranges)
+    parts, meta = _pack(predictions, groundtruth, motion_iou, motion_ranges)
     F, N, C = meta["F"], meta["N"], meta["C"]
-    t = device_views(torch.from_numpy(buf).to(dev), layout)
+    t = flat.upload(parts, dev)
     labels = t["det_label"]
     scores = t["score"]
     if N:
         # within-frame order: frame, label, score descending, position descending
-        rev = torch.arange(N - 1, -1, -1, device=dev)
-        perm = rev[torch.sort(scores[rev], descending=True, stable=True).indices]
-        fid = torch.repeat_interleave(torch.arange(F, device=dev), torch.from_numpy(meta["counts"]).to(dev),
-                                      output_size=N)
-        key = fid * C + labels.long()
-        order = perm[torch.sort(key[perm], stable=True).indices]
+        key = flat.frame_ids(meta["counts"], dev) * C + labels.long()
+        order = flat.segment_order(scores, key, start=torch.arange(N - 1, -1, -1, device=dev))
         # per class over the dataset: score descending, then descending position in that frame-by-frame concatenation
-        rev2 = order.flip(0)
-        perm2 = rev2[torch.sort(scores[rev2], descending=True, stable=True).indices]
-        gorder = perm2[torch.sort(labels[perm2], stable=True).indices]
+        gorder = flat.segment_order(scores, labels, start=order.flip(0))
         order, gorder = order.int(), gorder.int()
         seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
         seg_off[1:] = torch.cumsum(torch.bincount(labels.long(), minlength=C), 0)
@@ -355,8 +304,7 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
                                   "call vid_eval.evaluate_proposals on predictions with the field \"objectness\"")
     if use_07_metric:
         raise NotImplementedError("the VOC07 11-point metric is not provided (the reference hard-codes use_07_metric=False)")
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(torch.device(device), "evaluate_detections", device)
     ap = match_and_ap(predictions, groundtruth, motion_iou, device, ap_only=True)["ap"]
     motion_ranges = MOTION_RANGES if motion_iou is not None else MOTION_RANGES[:1]
     result = {}
@@ -379,8 +327,7 @@ def proposal_inputs(predictions, groundtruth, limits, device="cuda"):
     within-frame objectness order sorted on the device) -> (box, off, order, ratio, gt_box, gt_off, limits, max_limit,
     max_gt)."""
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(dev, "evaluate_detections", device)
     limits = [int(l) for l in limits]
     if not limits or min(limits) < 0:
         raise ValueError("evaluate_proposals: limits must be non-negative integers, got %r" % (limits,))
@@ -395,15 +342,8 @@ def proposal_inputs(predictions, groundtruth, limits, device="cuda"):
         if not p.has_field("objectness"):
             raise ValueError("evaluate_proposals: a prediction has no field \"objectness\" (fields: %r); proposals come "
                              "from a detector run with MODEL.RPN_ONLY True" % (sorted(p.fields()),))
-    counts = np.fromiter((len(p) for p in predictions), dtype=np.int64, count=F)
-    off = np.zeros(F + 1, np.int64)
-    off[1:] = np.cumsum(counts)
+    counts, off, boxes, obj = flat.concat_predictions(predictions, ("objectness",))
     N = int(off[-1])
-    if N:
-        boxes = torch.cat([p.bbox.reshape(-1, 4).to("cpu", torch.float32) for p in predictions]).numpy()
-        obj = torch.cat([p.get_field("objectness").reshape(-1).to("cpu", torch.float32) for p in predictions]).numpy()
-    else:
-        boxes, obj = np.zeros((0, 4), np.float32), np.zeros(0, np.float32)
     if not np.isfinite(boxes).all():
         raise ValueError("evaluate_proposals: a proposal box is not finite")
     if np.isnan(obj).any():
@@ -414,16 +354,13 @@ def proposal_inputs(predictions, groundtruth, limits, device="cuda"):
     max_gt = int(gcount.max())
     if max_gt > MAX_GT_PER_FRAME:
         raise ValueError("evaluate_proposals: a frame holds %d GT boxes (at most %d)" % (max_gt, MAX_GT_PER_FRAME))
-    buf, layout = one_buffer([("box", boxes), ("obj", (obj + np.float32(0)).astype(np.float32)),       # -0 -> +0
-                              ("off", off), ("ratio", _resize_ratios(predictions, groundtruth)),
-                              ("gt_box", groundtruth.boxes), ("gt_off", groundtruth.off),
-                              ("limits", np.asarray(limits, np.int32))])
-    t = device_views(torch.from_numpy(buf).to(dev), layout)
+    t = flat.upload([("box", boxes), ("obj", (obj + np.float32(0)).astype(np.float32)),       # -0 -> +0
+                     ("off", off), ("ratio", _resize_ratios(predictions, groundtruth)),
+                     ("gt_box", groundtruth.boxes), ("gt_off", groundtruth.off),
+                     ("limits", np.asarray(limits, np.int32))], dev)
     if N:
         # within a frame: objectness descending, equal values by ascending position
-        perm = torch.sort(t["obj"], descending=True, stable=True).indices
-        fid = torch.repeat_interleave(torch.arange(F, device=dev), torch.from_numpy(counts).to(dev), output_size=N)
-        order = perm[torch.sort(fid[perm], stable=True).indices].int()
+        order = flat.segment_order(t["obj"], flat.frame_ids(counts, dev)).int()
     else:
         order = torch.zeros(0, dtype=torch.int32, device=dev)
     return t["box"], t["off"], order, t["ratio"], t["gt_box"], t["gt_off"], t["limits"], max(limits), max_gt
@@ -464,8 +401,7 @@ def evaluate_proposals(predictions, groundtruth, iou_thresh=0.5, limit=300, limi
     -> {"recall": f32, "num_pos": int, "gt_overlaps": [G] f32, "gt_prop": [G] i32 (by GT box: the IoU it was matched with
     and the matched proposal's position in the frame's objectness order, 0 / -1 if none)} and, with a table, "limits",
     "iou_thresholds", "table" [nL,nT] f32, "ar" [nL] f32."""
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("evaluate_detections runs on a HIP device (no CPU path); got device %r" % (device,))
+    flat.require_hip(torch.device(device), "evaluate_detections", device)
     want_table = limits is not None or iou_thresholds is not None
     tl = [int(l) for l in (PROPOSAL_LIMITS if limits is None else limits)] if want_table else []
     tt = [float(t) for t in (PROPOSAL_IOU_THRESHOLDS if iou_thresholds is None else iou_thresholds)] if want_table else []
