@@ -405,6 +405,14 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const int split) 
   const int h2 = lane >> 5, l31 = lane & 31;
   const int head = blockIdx.y;
   const int qw0 = blockIdx.x * 128 + wave * 32;  // first query row of this wave
+  // A wave whose 32 query rows all lie past Nq (the last block of a problem: waves 2 and 3 of the sixth block at Nq = 675,
+  // of the third at Nq = 300) is dead: it still takes part in the cooperative tile loads, the LDS stores and every
+  // barrier, but skips the tile arithmetic, the position-logit loads and the epilogue (wave-uniform: a scalar branch).
+  // It used to run all of it on clamped rows and store nothing.  Only the 16-bit builds with the tiled position term
+  // take the branch: they gained 13 - 24 % per launch, the builds without it lost 2 % (the branch also changes the
+  // compiler's schedule of the loop) and keep the old code, like f32.  The two position-logit loads ahead of the loop
+  // stay unconditional: guarding them as well made the f16 two-segment build spill 12 bytes.
+  const bool live = !POS_TILED || __builtin_amdgcn_readfirstlane(qw0) < p.Nq;
   const T* __restrict__ Qp = (const T*)p.Q;
   // Keys 0 .. N1-1 live in (K, Vt), keys N1 .. Nk-1 in (K2, Vt2): the [local window ; memory snapshot] key set of a MEGA
   // stage is read where its two parts already are (the projections' output, the memory tape) instead of being copied into
@@ -667,16 +675,21 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const int split) 
   __syncthreads();
   for (int i = 0; i + 1 < n; i += 2) {   // invariant: LDS buffer 0 holds tile t0+i, ka/va hold tile t0+i+1
     load_tiles((t0 + i + 2) * 32, kb2, vb2);
-    compute(0, (t0 + i) * 32, pA);
-    load_pos(t0 + i + 2, pA);
+    if (live) {
+      compute(0, (t0 + i) * 32, pA);
+      load_pos(t0 + i + 2, pA);
+    }
     store_tiles(1, ka, va);
     __syncthreads();
     load_tiles((t0 + i + 3) * 32, ka, va);
-    compute(1, (t0 + i + 1) * 32, pB);
-    load_pos(t0 + i + 3, pB);
+    if (live) {
+      compute(1, (t0 + i + 1) * 32, pB);
+      load_pos(t0 + i + 3, pB);
+    }
     store_tiles(0, kb2, vb2);
     __syncthreads();
   }
+  if (!live) return;       // (no block-wide barrier below; a dead wave has no row to write, whole or partial)
   if (n & 1) compute(0, (t0 + n - 1) * 32, pA);
 
   const float l_tot = l_run + __shfl_xor(l_run, 32);
@@ -964,7 +977,8 @@ extern "C" int mega_relation_attention_batched(const void* descs, int n, int gro
   // Builds: SEG = some problem of the launch has a second key segment (the seam code costs the one-segment launches 5 %:
   // they keep their own build).  The two-segment tiled-position build is compiled for three blocks per CU, every other one
   // for two (attn_batched_kernel's launch bounds): it needs 170 VGPRs under a 2-block bound, two over the 168 that still
-  // fit three waves per SIMD, and exactly 168, without spills, under a 3-block bound (886 against 1020 us at stage 0);
+  // fit three waves per SIMD, and at most 168, without spills, under a 3-block bound (886 against 1020 us at stage 0
+  // before dead waves skipped the tile arithmetic, about 700 us since: 166 VGPRs in bf16, 168 in f16);
   // every other variant fits 166 under the 2-block bound and is 4 % faster that way.
 #define MEGA_ATTN_LAUNCH(T, TILED)                                                                              \
   do {                                                                                                          \
