@@ -29,8 +29,11 @@ __device__ __forceinline__ float box_iou1(const float4 a, const float4 b) {
   return box_iou1(a, box_area1(a), b, box_area1(b));
 }
 
-// f32 -> u32 whose unsigned order is the floats' order (the sort keys' high word)
+// f32 -> u32 whose unsigned order is the floats' order (the sort keys' high word).  Floats that compare equal get equal
+// keys, so that the index in the low word breaks the tie: -0.0 takes +0.0's key (on the bits, not by `f + 0.f`, which
+// holds only as long as no flag lets the compiler drop the addition).  NaNs are not ordered by any caller's contract.
 __device__ __forceinline__ unsigned f32_sortable(float f) {
   unsigned u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }

@@ -43,9 +43,13 @@ __device__ void bitonic_sort_desc(u64* s, int n) {
 }
 
 // The decision `box_iou1(a, b) > thr` (strict_gt) or `>= thr` WITHOUT the division in all but borderline cases:
-// iou <> thr  <=>  interS <> thr * union; when the two sides differ by more than 1e-5 relative -- 40x the worst
-// rounding error of the quotient (<= 2.5 ulp for the device's f32 division) plus that of the product -- the answer
-// cannot depend on how the quotient rounds, otherwise the quotient is evaluated exactly as box_iou1 does.
+// iou <> thr  <=>  interS <> thr * union; when the two sides differ by more than 1e-5 relative -- 80x the rounding
+// errors of the quotient and of the product together (half an ulp each) -- the answer cannot depend on how the
+// quotient rounds, otherwise the quotient is evaluated exactly as box_iou1 does.  The device's f32 division is
+// correctly rounded, like the host's: that is hipcc's default (-fhip-fp32-correctly-rounded-divide-sqrt, the
+// v_div_scale / v_div_fmas / v_div_fixup sequence), and inside the band the decision equals the reference's only as long
+// as no flag trades it for the 2.5-ulp reciprocal form (-fno-hip-fp32-correctly-rounded-divide-sqrt, -ffast-math, -Ofast):
+// tests/test_box_shared.py holds build.py to that, tests/test_box_boundary_gpu.py runs pairs inside the band.
 __device__ __forceinline__ bool dev_suppresses_areas(const float4 a, const float Sa, const float4 b, const float Sb,
                                                      float thr, int strict_gt) {
   const float interS = box_inter1(a, b);

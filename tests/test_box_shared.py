@@ -58,12 +58,29 @@ def _includes(path, seen):
     return seen
 
 
-def test_every_unit_that_sees_box_math_is_built_without_fma_contraction():
+def _box_math_users():
     users = [src for src in build.SOURCES if "box_math.h" in _includes(os.path.join(CSRC, src), set())]
     assert set(users) >= {"boxes.hip", "bbox_aug.hip", "soft_nms.hip", "seq_nms.hip", "tracks.hip", "vid_eval.hip",
                           "proposal_recall.hip"}
-    for src in users:
+    return users
+
+
+def test_every_unit_that_sees_box_math_is_built_without_fma_contraction():
+    for src in _box_math_users():
         assert "-ffp-contract=off" in build.SOURCES[src], src
+
+
+def test_every_unit_that_sees_box_math_keeps_the_correctly_rounded_division():
+    """box_iou1's quotient, and the one dev_suppresses_areas falls back to inside its 1e-5 band, must round like the host's
+    (tests/test_box_boundary_gpu.py runs pairs whose decision hangs on that last bit).  hipcc's default is the correctly
+    rounded expansion (-fhip-fp32-correctly-rounded-divide-sqrt); these flags trade it, or the signed zeros and separate
+    roundings the kernels rely on, for speed -- none may reach such a unit, neither per file nor through BASE_FLAGS."""
+    loose = {"-fno-hip-fp32-correctly-rounded-divide-sqrt", "-ffast-math", "-Ofast", "-funsafe-math-optimizations",
+             "-freciprocal-math", "-fno-signed-zeros", "-fapprox-func", "-ffp-model=fast", "-ffp-model=aggressive",
+             "-fgpu-approx-transcendentals"}
+    for src in _box_math_users():
+        flags = build.BASE_FLAGS + build.SOURCES[src]
+        assert not loose & set(flags), (src, sorted(loose & set(flags)))
 
 
 def _boxlist(rows):
