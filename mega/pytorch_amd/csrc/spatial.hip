@@ -288,9 +288,14 @@ __global__ __launch_bounds__(256) void roi_align_nhwc_vec_kernel(const T* __rest
         const T* e3 = reinterpret_cast<const T*>(&r3);
         const T* e4 = reinterpret_cast<const T*>(&r4);
 #pragma unroll
-        for (int e = 0; e < VE; ++e)
+        for (int e = 0; e < VE; ++e) {
+          // each product and each sum of the blend rounds on its own, as roi_align_kernel's do (and the reference's CPU kernel's):
+          // contracted into fused multiply-adds, 1 % of the f32 results were an ulp or two off those bits wherever a weight is
+          // not a short binary fraction
+#pragma clang fp contract(off)
           acc[e] += (w1 * Elem<T>::ld(e1 + e) + w2 * Elem<T>::ld(e2 + e) + w3 * Elem<T>::ld(e3 + e) +
                      w4 * Elem<T>::ld(e4 + e));
+        }
       }
     }
     if constexpr (PLANES) {
@@ -368,7 +373,8 @@ __device__ __forceinline__ void roi_patch_accumulate(const T* __restrict__ base,
 
 // PLANES (T = float, round 6): the pooled values leave as split-precision planes [hi | lo] of PT (bf16 / f16), as in
 // roi_align_nhwc_vec_kernel<float, ., true>: the split-precision mode's ROIAlign in the separable form (the exact-term-order
-// kernel it replaces there was 3.5x the bf16 kernel's time; the separable sums differ from it at f32 round-off, ~1e-7 relative).
+// kernel it replaces there was 3.5x the bf16 kernel's time; the separable sums differ from it at f32 round-off, ~1e-7 relative;
+// the mean is the correctly rounded sum / count, as in that kernel, so wherever the sums are exact the planes are its planes).
 template <typename T, int NSLICE, bool PLANES = false, typename PT = bf16_t>
 __global__ __launch_bounds__(256, 4) void roi_align_nhwc_sep_kernel(const T* __restrict__ feat,
                                                                  const float* __restrict__ rois, T* __restrict__ out,
@@ -377,11 +383,13 @@ __global__ __launch_bounds__(256, 4) void roi_align_nhwc_sep_kernel(const T* __r
   static_assert(!PLANES || sizeof(T) == 4, "planes output: f32 features");
   constexpr int VE = Elem<T>::VE;
   // one pooled 16-byte vector -> out (plain rows, or the hi / lo planes of ROI k's row)
-  auto store = [&](int k_, int bin, int cv, const float (&acc)[Elem<T>::VE], float inv_count) {
+  auto store = [&](int k_, int bin, int cv, const float (&acc)[Elem<T>::VE], float inv_count, float count_) {
     if constexpr (PLANES) {
+      // the division itself, not the product with the rounded reciprocal: that product is up to 1 ulp of the f32 value away,
+      // which the hi plane absorbs and the lo plane does not (lo = v - hi carries v's last bits: several ulp of an f16 lo)
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = acc[e] * inv_count;
+      for (int e = 0; e < 4; ++e) v[e] = acc[e] / count_;
       const unsigned h0 = Half16<PT>::pack2(v[0], v[1]), h1 = Half16<PT>::pack2(v[2], v[3]);
       const unsigned l0 = Half16<PT>::pack2(v[0] - Half16<PT>::lo(h0), v[1] - Half16<PT>::hi(h0));
       const unsigned l1 = Half16<PT>::pack2(v[2] - Half16<PT>::lo(h1), v[3] - Half16<PT>::hi(h1));
@@ -501,7 +509,7 @@ __global__ __launch_bounds__(256, 4) void roi_align_nhwc_sep_kernel(const T* __r
             }
         }
       }
-      store(k, bin, cv, acc, inv_count);
+      store(k, bin, cv, acc, inv_count, count);
     }
     return;
   }
@@ -517,7 +525,7 @@ __global__ __launch_bounds__(256, 4) void roi_align_nhwc_sep_kernel(const T* __r
     else if (NCm <= 4) roi_patch_accumulate<T, 4, 2>(base, W, H, C, y0, x0, NR, s_wy[ph], s_wx[pw], acc);
     else if (NCm <= 6) roi_patch_accumulate<T, 6, 2>(base, W, H, C, y0, x0, NR, s_wy[ph], s_wx[pw], acc);
     else roi_patch_accumulate<T, RS_MAXP, 1>(base, W, H, C, y0, x0, NR, s_wy[ph], s_wx[pw], acc);
-    store(k, bin, cv, acc, inv_count);
+    store(k, bin, cv, acc, inv_count, count);
   }
 }
 
