@@ -383,9 +383,10 @@ int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int dtype, void
 const char* mega_last_error_string(void);
 
 /* Several independent relation-attention problems (the key frames of one engine step-batch at the same stage) in ONE
- * launch (+ one combine launch).  Every problem runs exactly the code and the key-range split of its own
- * mega_relation_attention / mega_relation_attention_tiled_pos_dt call: identical bits.  n <= 16; all problems share groups,
- * scale, dtype and the kind of position term (none / f32 rows `pos` with ldp / tile-ordered bf16 `pos_tiled`). */
+ * launch (+ one combine launch).  A problem's key-range split is a function of the problem alone, so its bits do not depend
+ * on what it is batched with; mega_relation_attention / mega_relation_attention_tiled_pos_dt launch a batch of one.  n <= 20;
+ * all problems share groups, scale, dtype and the kind of position term (none / f32 rows `pos` with ldp / tile-ordered 16-bit
+ * `pos_tiled`). */
 typedef struct {
   const void* q; const void* k; const void* vt; const float* pos; const void* pos_tiled; const void* resid;
   const float* bias_v; void* out; void* ws; size_t ws_bytes;
@@ -403,7 +404,8 @@ typedef struct {
 int mega_relation_attention_batched(const void* descs /* mega_attn_desc[n], host memory */, int n, int groups,
                                     float scale, int dtype, void* stream);
 
-/* mega_position_logits_tiled_dt for n <= 16 (query boxes, key boxes) problems in one launch (mega_position_logits_tiled_batched_dt). */
+/* mega_position_logits_tiled_dt for n <= 20 (query boxes, key boxes) problems in one launch (mega_position_logits_tiled_batched_dt);
+ * the single entry point launches a batch of one. */
 typedef struct { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; } mega_pos_desc;
 
 /* Round 6: the head on IEEE-half operands (cfg.HEAD_DTYPE "float16": Q K^T, P V and the position term on

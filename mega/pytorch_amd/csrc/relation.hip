@@ -14,13 +14,14 @@
 // Kernels:
 //   pos_logits_kernel : boxes -> w[h][q][k] (f32), one thread per (q,k) pair, 64-d sin/cos embedding and the
 //                       16x64 Wg contraction in registers (Wg staged in LDS, broadcast reads).
-//   attn_kernel<T>    : flash-style streaming softmax.  One wave owns 32 query rows of one head; per 32-key tile
+//   attn_batched_kernel<T> : flash-style streaming softmax.  One wave owns 32 query rows of one head; per 32-key tile
 //                       S^T = K Q^T on MFMA (so a lane holds 16 keys of ONE query: row max / sum are register
 //                       reductions + one cross-half shuffle), P feeds the PV MFMA straight from registers,
 //                       V is consumed from a key-contiguous (transposed) LDS image.  bf16 -> mfma_32x32x16_bf16,
 //                       f32 -> mfma_32x32x2_f32 (exact f32, parity mode).  The key range can be split over
 //                       blockIdx.z (a call has only Nq/128 * 16 blocks for 256 CUs); partial (m, l, O) are then
-//                       merged by attn_combine_kernel.
+//                       merged by attn_combine_batched_kernel.  Every kernel has ONE launch form, over an array of
+//                       problems: a single-problem entry point launches a batch of one.
 #include <type_traits>
 
 #include "common.h"
@@ -288,17 +289,7 @@ __device__ __forceinline__ void pos_logits_tiled_body(const float4* __restrict__
   }
 }
 
-template <typename HT>
-__global__ __launch_bounds__(256) void pos_logits_tiled_kernel(const float4* __restrict__ rois_q,
-                                                               const float4* __restrict__ rois_k,
-                                                               const float* __restrict__ wgt,
-                                                               const float* __restrict__ bg,
-                                                               const float* __restrict__ dim_mat,
-                                                               unsigned short* __restrict__ out_t, int Nq, int Nk) {
-  pos_logits_tiled_body<HT>(rois_q, rois_k, wgt, bg, dim_mat, out_t, Nq, Nk);
-}
-
-// the same for several (query boxes, key boxes) problems in one launch: blockIdx.z = problem
+// one launch for several (query boxes, key boxes) problems: blockIdx.z = problem (a single call is a batch of one)
 constexpr int POS_MAXB = 20;          // problems per launch: the key frames of the bench's 20-key-frame step-batch in ONE launch
 struct PosBatch {
   struct { const float4* rq; const float4* rk; unsigned short* out; int Nq, Nk; } p[POS_MAXB];
@@ -694,7 +685,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const int split) 
 
   const float l_tot = l_run + __shfl_xor(l_run, 32);
   if (p.nsplit > 1) {
-    // ---- partial result: un-normalised O, running max and sum (merged by attn_combine_kernel)
+    // ---- partial result: un-normalised O, running max and sum (merged by attn_combine_batched_kernel)
     if (h2 == 0 && qw0 + l31 < p.Nq) {
       float* ml = p.part_ml + (size_t)split * 2 * p.G * p.Nq;
       ml[(size_t)head * p.Nq + qw0 + l31] = m_run;
@@ -739,15 +730,10 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const int split) 
   }
 }
 
-template <typename T, bool POS_TILED>
-__global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
-  attn_body<T, POS_TILED, false>(p, (int)blockIdx.z);
-}
-
 // Several independent attention problems (the key frames of one engine step-batch at the same stage) in ONE launch:
 // blockIdx.z enumerates (problem, key-range split) pairs through a small table, so the chip is filled by all
-// problems together and the host pays one launch per stage instead of one per key frame.  Every problem runs exactly
-// the code (and the split count) of its single-problem launch: same bits.
+// problems together and the host pays one launch per stage instead of one per key frame.  A problem's split count is a
+// function of the problem alone, so its bits do not depend on what it is batched with.
 constexpr int ATTN_MAXB = 20;         // (kernel arguments are limited to 4 KiB: see the static_assert below)
 constexpr int ATTN_MAXZ = 256;
 struct AttnBatch {
@@ -758,7 +744,7 @@ struct AttnBatch {
 static_assert(sizeof(AttnBatch) <= 4096, "AttnBatch travels as the kernel argument");
 
 // Blocks per CU the register allocation aims at: 3 (<= 168 VGPRs: three waves per SIMD) for the two-segment build with
-// the tiled position term, 2 for every other one; see mega_relation_attention_batched for the VGPR figures.
+// the tiled position term, 2 for every other one; see attn_launch for the VGPR figures.
 template <typename T, bool POS_TILED, bool SEG>
 __global__ __launch_bounds__(256, (POS_TILED && SEG) ? 3 : 2) void attn_batched_kernel(AttnBatch b) {
   const int z = blockIdx.z;
@@ -796,11 +782,6 @@ __device__ __forceinline__ void attn_combine_body(const AttnParams& p) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void attn_combine_kernel(AttnParams p) {
-  attn_combine_body<T>(p);
-}
-
-template <typename T>
 __global__ __launch_bounds__(256) void attn_combine_batched_kernel(AttnBatch b) {
   const AttnParams& p = b.p[blockIdx.y];
   if (p.nsplit > 1) attn_combine_body<T>(p);
@@ -831,22 +812,45 @@ extern "C" int mega_position_logits(const float* rois_q, const float* rois_k, co
   return mega_check_launch();
 }
 
+struct MegaPosDescC { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; };
+
+// the one launcher of pos_logits_tiled_batched_kernel: n <= POS_MAXB problems
+static int pos_tiled_launch(const MegaPosDescC* d, int n, const float* wg_t, const float* bg, const float* dim_mat,
+                            int dtype, void* stream) {
+  if (!d || n < 0 || n > POS_MAXB || !wg_t || !bg || !dim_mat) return MEGA_ERR_ARG;
+  PosBatch b;
+  int max_q = 0, max_k = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!d[i].rois_q || !d[i].rois_k || !d[i].out_bf16 || d[i].Nq <= 0 || d[i].Nk <= 0 ||
+        (reinterpret_cast<size_t>(d[i].out_bf16) & 15))
+      return MEGA_ERR_ARG;
+    b.p[i].rq = (const float4*)d[i].rois_q; b.p[i].rk = (const float4*)d[i].rois_k; b.p[i].out = (unsigned short*)d[i].out_bf16;
+    b.p[i].Nq = d[i].Nq; b.p[i].Nk = d[i].Nk;
+    max_q = d[i].Nq > max_q ? d[i].Nq : max_q;
+    max_k = d[i].Nk > max_k ? d[i].Nk : max_k;
+  }
+  dim3 grid(cdiv(max_k, 64), cdiv(max_q, 8), n);
+  if (dtype == MEGA_F16) hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
+  else hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
+  return mega_check_launch();
+}
+
 // round 6: the tile-ordered logits in the head's 16-bit operand type (dtype = MEGA_BF16 / MEGA_F16)
 extern "C" int mega_position_logits_tiled_dt(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
                                              const float* dim_mat, void* out16, int Nq, int Nk, int dtype, void* stream) {
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (Nq == 0 || Nk == 0) return MEGA_OK;
-  if (!rois_q || !rois_k || !wg_t || !bg || !dim_mat || !out16 || Nq < 0 || Nk < 0 || (reinterpret_cast<size_t>(out16) & 15))
-    return MEGA_ERR_ARG;
-  dim3 grid(cdiv(Nk, 64), cdiv(Nq, 8));
-  if (dtype == MEGA_F16)
-    hipLaunchKernelGGL(pos_logits_tiled_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out16, Nq, Nk);
-  else
-    hipLaunchKernelGGL(pos_logits_tiled_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)rois_q,
-                       (const float4*)rois_k, wg_t, bg, dim_mat, (unsigned short*)out16, Nq, Nk);
-  return mega_check_launch();
+  const MegaPosDescC d = {rois_q, rois_k, out16, Nq, Nk};
+  return pos_tiled_launch(&d, 1, wg_t, bg, dim_mat, dtype, stream);
+}
+
+extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
+                                                     const float* dim_mat, int dtype, void* stream) {
+  mega_clear_error();
+  if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
+  if (n == 0) return MEGA_OK;
+  return pos_tiled_launch((const MegaPosDescC*)descs, n, wg_t, bg, dim_mat, dtype, stream);
 }
 
 // Number of key-range splits the attention core uses for (Nq, Nk) -- a function of the problem alone, so a problem
@@ -906,37 +910,8 @@ static int attn_fill(AttnParams& p, const void* q, int ldq, const void* k, int l
   return MEGA_OK;
 }
 
-static int relation_attention_impl(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,
-                                   const float* pos, int ldp, const void* pos_tiled, const void* resid, int ldr,
-                                   const float* bias_v, void* out, int ldo, int Nq, int Nk, int groups, float scale,
-                                   int dtype, void* ws, size_t ws_bytes, void* stream) {
-  mega_clear_error();
-  if (Nq == 0) return MEGA_OK;
-  AttnParams p;
-  const int rc = attn_fill(p, q, ldq, k, ldk, vt, ldv, pos, ldp, pos_tiled, resid, ldr, bias_v, out, ldo, Nq, Nk, groups,
-                           scale, dtype, ws, ws_bytes);
-  if (rc != MEGA_OK) return rc;
-  const int nsplit = p.nsplit;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(cdiv(Nq, 128), groups, nsplit);
-  if (dtype == MEGA_BF16 && pos_tiled) hipLaunchKernelGGL((attn_kernel<bf16_t, true>), grid, dim3(256), 0, st, p);
-  else if (dtype == MEGA_BF16) hipLaunchKernelGGL((attn_kernel<bf16_t, false>), grid, dim3(256), 0, st, p);
-  else if (dtype == MEGA_F16 && pos_tiled) hipLaunchKernelGGL((attn_kernel<f16_t, true>), grid, dim3(256), 0, st, p);
-  else if (dtype == MEGA_F16) hipLaunchKernelGGL((attn_kernel<f16_t, false>), grid, dim3(256), 0, st, p);
-  else if (dtype == MEGA_F32) hipLaunchKernelGGL((attn_kernel<float, false>), grid, dim3(256), 0, st, p);
-  else return MEGA_ERR_ARG;
-  if (nsplit > 1) {
-    const size_t total = (size_t)Nq * groups * 64;
-    const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    if (dtype == MEGA_BF16) hipLaunchKernelGGL((attn_combine_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, p);
-    else if (dtype == MEGA_F16) hipLaunchKernelGGL((attn_combine_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((attn_combine_kernel<float>), dim3(blocks), dim3(256), 0, st, p);
-  }
-  return mega_check_launch();
-}
-
-// n <= 16 independent problems in one launch (+ one combine launch when any of them splits its key range).  All
-// problems share groups / scale / dtype and the kind of position term (none, f32 rows, or tile-ordered bf16).
+// n <= ATTN_MAXB independent problems in one launch (+ one combine launch when any of them splits its key range).  All
+// problems share groups / scale / dtype and the kind of position term (none, f32 rows, or tile-ordered 16-bit).
 struct MegaAttnDescC {
   const void* q; const void* k; const void* vt; const float* pos; const void* pos_tiled; const void* resid;
   const float* bias_v; void* out; void* ws; size_t ws_bytes;
@@ -945,12 +920,9 @@ struct MegaAttnDescC {
   const void* k2; const void* vt2; int ldv2, reserved;
 };
 
-extern "C" int mega_relation_attention_batched(const void* descs, int n, int groups, float scale, int dtype,
-                                               void* stream) {
-  mega_clear_error();
-  if (n == 0) return MEGA_OK;
-  if (!descs || n < 0 || n > ATTN_MAXB) return MEGA_ERR_ARG;
-  const MegaAttnDescC* d = (const MegaAttnDescC*)descs;
+// the one launcher of attn_batched_kernel / attn_combine_batched_kernel: fill, z table, SEG choice, dtype dispatch, combine
+static int attn_launch(const MegaAttnDescC* d, int n, int groups, float scale, int dtype, void* stream) {
+  if (!d || n < 0 || n > ATTN_MAXB) return MEGA_ERR_ARG;
   AttnBatch b;                 // by-value kernel argument (~2.5 KB)
   b.n = n;
   int nz = 0, max_q = 0, any_split = 0, any_seg = 0;
@@ -1001,30 +973,25 @@ extern "C" int mega_relation_attention_batched(const void* descs, int n, int gro
   return mega_check_launch();
 }
 
-struct MegaPosDescC { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; };
-
-extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
-                                                     const float* dim_mat, int dtype, void* stream) {
+extern "C" int mega_relation_attention_batched(const void* descs, int n, int groups, float scale, int dtype,
+                                               void* stream) {
   mega_clear_error();
-  if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (n == 0) return MEGA_OK;
-  if (!descs || n < 0 || n > POS_MAXB || !wg_t || !bg || !dim_mat) return MEGA_ERR_ARG;
-  const MegaPosDescC* d = (const MegaPosDescC*)descs;
-  PosBatch b;
-  int max_q = 0, max_k = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!d[i].rois_q || !d[i].rois_k || !d[i].out_bf16 || d[i].Nq <= 0 || d[i].Nk <= 0 ||
-        (reinterpret_cast<size_t>(d[i].out_bf16) & 15))
-      return MEGA_ERR_ARG;
-    b.p[i].rq = (const float4*)d[i].rois_q; b.p[i].rk = (const float4*)d[i].rois_k; b.p[i].out = (unsigned short*)d[i].out_bf16;
-    b.p[i].Nq = d[i].Nq; b.p[i].Nk = d[i].Nk;
-    max_q = d[i].Nq > max_q ? d[i].Nq : max_q;
-    max_k = d[i].Nk > max_k ? d[i].Nk : max_k;
-  }
-  dim3 grid(cdiv(max_k, 64), cdiv(max_q, 8), n);
-  if (dtype == MEGA_F16) hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
-  else hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
-  return mega_check_launch();
+  return attn_launch((const MegaAttnDescC*)descs, n, groups, scale, dtype, stream);
+}
+
+// the single-problem entry points: a batch of one (one key segment, resid / out in the operand type)
+static int relation_attention_impl(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,
+                                   const float* pos, int ldp, const void* pos_tiled, const void* resid, int ldr,
+                                   const float* bias_v, void* out, int ldo, int Nq, int Nk, int groups, float scale,
+                                   int dtype, void* ws, size_t ws_bytes, void* stream) {
+  mega_clear_error();
+  if (Nq == 0) return MEGA_OK;
+  MegaAttnDescC d = {};
+  d.q = q; d.k = k; d.vt = vt; d.pos = pos; d.pos_tiled = pos_tiled; d.resid = resid; d.bias_v = bias_v; d.out = out;
+  d.ws = ws; d.ws_bytes = ws_bytes;
+  d.ldq = ldq; d.ldk = ldk; d.ldv = ldv; d.ldp = ldp; d.ldr = ldr; d.ldo = ldo; d.Nq = Nq; d.Nk = Nk;
+  return attn_launch(&d, 1, groups, scale, dtype, stream);
 }
 
 extern "C" int mega_relation_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,

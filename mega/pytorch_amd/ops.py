@@ -736,17 +736,11 @@ def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False
     _gpu(rois_q, rois_k, wg_t, bg, dim_mat)
     lib = _lib.load()
     Nq, Nk = rois_q.shape[0], rois_k.shape[0]
-    if tiled:
-        tdt = torch.bfloat16 if tiled is True else tiled      # the head's 16-bit operand type (bf16, or f16: round 6)
-        assert not precise and tdt in _HALF, "the tile-ordered position logits are bf16 / f16"
-        kt = (Nk + 31) // 32
-        out = torch.empty((16, kt, Nq, 32), dtype=tdt, device=rois_q.device)
-        _tok = _pb("pos_logits", 2.0 * Nq * Nk * 1024, out.numel() * 2.0)
-        rc = lib.mega_position_logits_tiled_dt(_ptr(rois_q.contiguous()), _ptr(rois_k.contiguous()), _ptr(wg_t), _ptr(bg),
-                                               _ptr(dim_mat), _ptr(out), Nq, Nk, _DT[tdt], _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_position_logits_tiled_dt")
-        return out
+    if tiled:        # one problem of the batched launch (the tile-ordered kernel has no other launch form)
+        assert not precise, "the tile-ordered position logits are bf16 / f16"
+        if Nq == 0 or Nk == 0:      # nothing to compute (the C entry returns before any launch; a batch has no empty problems)
+            return torch.empty((16, (Nk + 31) // 32, Nq, 32), dtype=torch.bfloat16 if tiled is True else tiled, device=rois_q.device)
+        return position_logits_batched([rois_q], [rois_k], wg_t, bg, dim_mat, precise=False, tiled=tiled)[0]
     ldp = (Nk + 31) // 32 * 32
     out = torch.empty((16, Nq, ldp), dtype=torch.float32, device=rois_q.device)
     _tok = _pb("pos_logits", 2.0 * Nq * Nk * 1024, 16.0 * Nq * ldp * 4)
@@ -758,34 +752,12 @@ def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False
 
 
 def relation_attention(q, k, vt, Nk, pos=None, resid=None, bias_v=None, groups=16):
-    """q [Nq,G*64] (u folded in), k [Nk,G*64], vt [G*64, ldv] key-contiguous projected V -> [Nq, G*64]."""
-    _gpu(q, k, vt, pos, resid, bias_v)
-    if resid is not None and resid.dtype != q.dtype:     # f32 activation stream over bf16 operands: same kernel, same bits
-        return relation_attention_batched([{"q": q, "k": k, "vt": vt, "Nk": Nk, "pos": pos, "resid": resid,
-                                            "bias_v": bias_v}], groups)[0]
-    lib = _lib.load()
-    Nq = q.shape[0]
-    assert q.dtype == k.dtype == vt.dtype and q.is_contiguous() and k.is_contiguous() and vt.is_contiguous()
-    out = torch.empty((Nq, groups * 64), dtype=q.dtype, device=q.device)
-    nb = lib.mega_relation_attention_workspace_bytes(Nq, Nk, groups)
-    ws = _ws(nb, q.device) if nb else None
-    _tok = _pb("attention_" + _ATT_NAME.get(q.dtype, "f32"), 4.0 * Nq * Nk * 64 * groups, (q.numel() + k.numel() + vt.numel() + out.numel()) * q.element_size() + (0 if pos is None else pos.numel() * pos.element_size()))
-    if pos is not None and pos.dtype in _HALF:       # tile-ordered 16-bit logits (position_logits(tiled=dtype))
-        assert q.dtype == pos.dtype and pos.is_contiguous() and tuple(pos.shape) == (groups, (Nk + 31) // 32, Nq, 32)
-        rc = lib.mega_relation_attention_tiled_pos_dt(_ptr(q), q.shape[1], _ptr(k), k.shape[1], _ptr(vt), vt.shape[1],
-                                                      _ptr(pos), _ptr(resid), 0 if resid is None else resid.shape[1],
-                                                      _ptr(bias_v), _ptr(out), groups * 64, Nq, Nk, groups,
-                                                      1.0 / math.sqrt(64.0), _DT[q.dtype], _ptr(ws), nb, _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_relation_attention_tiled_pos_dt")
-        return out
-    rc = lib.mega_relation_attention(_ptr(q), q.shape[1], _ptr(k), k.shape[1], _ptr(vt), vt.shape[1], _ptr(pos),
-                                     0 if pos is None else pos.shape[2], _ptr(resid),
-                                     0 if resid is None else resid.shape[1], _ptr(bias_v), _ptr(out), groups * 64,
-                                     Nq, Nk, groups, 1.0 / math.sqrt(64.0), _dt(q), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_relation_attention")
-    return out
+    """q [Nq,G*64] (u folded in), k [Nk,G*64], vt [G*64, ldv] key-contiguous projected V -> [Nq, G*64].
+    One problem of relation_attention_batched: every attention kernel has one launch form, a batch."""
+    if q.shape[0] == 0:             # no query rows: nothing to launch (a batch has no empty problems)
+        return torch.empty((0, groups * 64), dtype=q.dtype if resid is None else resid.dtype, device=q.device)
+    return relation_attention_batched([{"q": q, "k": k, "vt": vt, "Nk": Nk, "pos": pos, "resid": resid,
+                                        "bias_v": bias_v}], groups)[0]
 
 
 _ATT_NAME = {torch.bfloat16: "bf16", torch.float16: "f16"}      # attention kernel family names (bench.py's per-family roofline)
@@ -843,7 +815,7 @@ def position_logits_batched(rois_qs, rois_ks, wg_t, bg, dim_mat, precise=True, t
 
 def relation_attention_batched(items, groups=16):
     """relation_attention for a list of independent problems, each a dict(q, k, vt, Nk, pos, resid, bias_v), in ONE launch
-    per 20 problems (+ one combine launch).  Every problem gets the bits of its own relation_attention call."""
+    per 20 problems (+ one combine launch).  A problem's bits do not depend on what it is batched with."""
     if not items:
         return []
     lib = _lib.load()

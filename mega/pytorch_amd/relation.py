@@ -82,16 +82,7 @@ def relation_attention_forward(w, x, ref, rois_q=None, rois_k=None, residual=Tru
     k = ops.linear(ref, w.wk, w.bk)
     ldr = (Nr + 31) // 32 * 32
     vt = project_v(w, ref, ldr)
-    k_all, vt_all, Nk = k, vt, Nr
-    if mem_kv is not None:
-        k_mem, vt_mem = mem_kv
-        Nk = Nr + k_mem.shape[0]
-        ldv = (Nk + 31) // 32 * 32
-        k_all = torch.cat([k, k_mem], dim=0)
-        parts = [vt[:, :Nr], vt_mem]
-        if ldv > Nk:
-            parts.append(vt.new_zeros((vt.shape[0], ldv - Nk)))
-        vt_all = torch.cat(parts, dim=1)
+    k_all, vt_all, Nk = (k, vt, Nr) if mem_kv is None else cat_key_set(k, vt[:, :Nr], mem_kv)
     q = ops.linear(op_dtype(w, x), w.wq, w.bq)
     pos = None
     if w.with_pos:
@@ -99,6 +90,23 @@ def relation_attention_forward(w, x, ref, rois_q=None, rois_k=None, residual=Tru
         pos = ops.position_logits(rois_q, rois_k, w.wg_t, w.bg, w.dim_mat, precise=not fast, tiled=w.wq.dtype if fast else False)
     out = ops.relation_attention(q, k_all, vt_all, Nk, pos=pos, resid=x if residual else None, bias_v=w.bv)
     return (out, k, vt) if return_kv else out
+
+
+def cat_key_set(k, vt, mem_kv=None):
+    """The [local ; memory] key set of one problem in one K / V^T buffer each: k [Nr,1024], vt [1024,Nr] (may be a strided
+    view), mem_kv = (k_mem [Nm,1024], vt_mem [1024,Nm]) or None -> (k_all [Nk,1024], vt_all [1024,ceil32(Nk)] with zero
+    pad columns, Nk)."""
+    Nk = k.shape[0]
+    vparts = [vt]
+    if mem_kv is not None:
+        k_mem, vt_mem = mem_kv
+        Nk += k_mem.shape[0]
+        k = torch.cat([k, k_mem], dim=0)
+        vparts.append(vt_mem)
+    ldv = (Nk + 31) // 32 * 32
+    if ldv > Nk:
+        vparts.append(vt.new_zeros((vt.shape[0], ldv - Nk)))
+    return k, (torch.cat(vparts, dim=1) if len(vparts) > 1 else vt.contiguous()), Nk
 
 
 def cat_rows(ts):
@@ -217,39 +225,19 @@ def relation_project_batched(w, xs, refs, want_x=False, also_cat=(), pad_refs=Fa
     return res + (cats[2:],) if also_cat else res
 
 
-def relation_attend(w, x, q, k, vt, rois_q=None, rois_k=None, mem_kv=None, residual=True):
-    """The attention core of one problem on already-projected operands (relation_project_batched): q [Nq,1024],
-    k [Nr,1024], vt [1024,Nr] (may be a strided view), mem_kv as in relation_attention_forward.  -> x + attention."""
-    Nk = k.shape[0]
-    vparts = [vt]
-    if mem_kv is not None:
-        k_mem, vt_mem = mem_kv
-        Nk += k_mem.shape[0]
-        k = torch.cat([k, k_mem], dim=0)
-        vparts.append(vt_mem)
-    ldv = (Nk + 31) // 32 * 32
-    if ldv > Nk:
-        vparts.append(vt.new_zeros((vt.shape[0], ldv - Nk)))
-    vv = torch.cat(vparts, dim=1) if len(vparts) > 1 else vt.contiguous()
-    pos = None
-    if w.with_pos:
-        fast = w.wq.dtype != torch.float32
-        pos = ops.position_logits(rois_q, rois_k, w.wg_t, w.bg, w.dim_mat, precise=not fast, tiled=w.wq.dtype if fast else False)
-    return ops.relation_attention(q, k, vv, Nk, pos=pos, resid=x if residual else None, bias_v=w.bv)
-
-
-def relation_attend_batched(w, jobs, residual=True, pos=None):
-    """relation_attend for several problems of the SAME weights (the key frames of a step-batch at one stage) with the
-    position logits and the attention core each as ONE launch: jobs = list of dict(x, q, k, vt, rois_q, rois_k, mem_kv),
+def relation_attend_batched(w, jobs, residual=True):
+    """The attention core of several problems of the SAME weights (the key frames of a step-batch at one stage) on
+    already-projected operands (relation_project_batched), with the position logits and the attention core each as ONE
+    launch: jobs = list of dict(x, q, k [Nr,1024], vt [1024,Nr] (may be a strided view), rois_q, rois_k, mem_kv) with
+    mem_kv as in relation_attention_forward,
     or, with the key sets already assembled by the caller, dict(x, q, k_all [Nk,1024], vt_all [1024,>=ceil32(Nk)]
     (unit column stride, any row stride), Nk, rois_q, rois_k), or in two segments that are read where they lie:
     dict(x, q, k [N1,1024], vt [1024,>=N1], k2 [Nk-N1,1024], vt2 [1024,>=Nk-N1], N1, Nk, rois_q, rois_k).
-    Same bits per problem as relation_attend.
-    The outputs are consecutive row blocks of one buffer (cat_rows() of them in order is free).
-    pos: the problems' position logits if the caller already has them (position_logits_for)."""
+    -> x + attention per problem; a problem's bits do not depend on what it is batched with.
+    The outputs are consecutive row blocks of one buffer (cat_rows() of them in order is free)."""
     if not jobs:
         return []
-    items, rq, rk = [], [], []
+    items = []
     for j in jobs:
         seg = None
         if "k2" in j:          # two key segments read in place: (k, vt) keys 0 .. N1-1, (k2, vt2) keys N1 .. Nk-1
@@ -258,35 +246,14 @@ def relation_attend_batched(w, jobs, residual=True, pos=None):
         elif "k_all" in j:
             k, vv, Nk = j["k_all"], j["vt_all"], j["Nk"]
         else:
-            k, vt = j["k"], j["vt"]
-            Nk = k.shape[0]
-            vparts = [vt]
-            if j.get("mem_kv") is not None:
-                k_mem, vt_mem = j["mem_kv"]
-                Nk += k_mem.shape[0]
-                k = torch.cat([k, k_mem], dim=0)
-                vparts.append(vt_mem)
-            ldv = (Nk + 31) // 32 * 32
-            if ldv > Nk:
-                vparts.append(vt.new_zeros((vt.shape[0], ldv - Nk)))
-            vv = torch.cat(vparts, dim=1) if len(vparts) > 1 else vt.contiguous()
+            k, vv, Nk = cat_key_set(j["k"], j["vt"], j.get("mem_kv"))
         items.append({"q": j["q"], "k": k, "vt": vv, "Nk": Nk, "resid": j["x"] if residual else None, "bias_v": w.bv})
         if seg is not None:
             items[-1].update(seg)
-        rq.append(j.get("rois_q"))
-        rk.append(j.get("rois_k"))
-    if w.with_pos:
-        if pos is None:      # (else: computed ahead of time by position_logits_for, same call, same bits)
-            pos = position_logits_for(w, rq, rk)
+    if w.with_pos:       # one launch per 20 problems in bf16 mode
+        fast = w.wq.dtype != torch.float32
+        pos = ops.position_logits_batched([j.get("rois_q") for j in jobs], [j.get("rois_k") for j in jobs], w.wg_t, w.bg,
+                                          w.dim_mat, precise=not fast, tiled=w.wq.dtype if fast else False)
         for it, p in zip(items, pos):
             it["pos"] = p
     return ops.relation_attention_batched(items)
-
-
-def position_logits_for(w, rois_qs, rois_ks):
-    """The position logits relation_attend_batched(w, jobs) computes for jobs with these query / key boxes (one launch per
-    20 problems in bf16 mode).  They depend on boxes only, so a caller that knows the key sets' boxes of a stage before its
-    features can compute them early, beside other work (MEGAFeatureExtractor.aggregate_batch does, on a side stream)."""
-    fast = w.wq.dtype != torch.float32
-    return ops.position_logits_batched(rois_qs, rois_ks, w.wg_t, w.bg, w.dim_mat, precise=not fast,
-                                       tiled=w.wq.dtype if fast else False)

@@ -793,9 +793,6 @@ def test_static_batch_aggregation_equals_eager(monkeypatch):
         m._reset(200)
         models.append(m)
     a, b = models
-    # b also takes the opt-in early form of the position logits (all stages' logits from boxes tapes laid out before the
-    # stages, MEGAFeatureExtractor._early_position_logits): same values, same state
-    b.roi_heads.box.feature_extractor.early_pos = True
     kn, bn = a.key_num, a.base_num
     recs = [record(kn) for _ in range(60)]
     globs = [[record(bn)] for _ in range(60)]

@@ -176,6 +176,121 @@ def test_position_logits_batched_guard_band(dev, dtype):
     assert (host[end:] == SENT16).all() and host.numel() - end == gap
 
 
+# ------------------------------------------------------------------------------------------------ 2b. single C entry points
+def _single_attention(lib, ptrs, ldv, Nq, Nk, dtype, pos, ldp, out, ws, ws_bytes, tiled=False):
+    """mega_relation_attention (no position term, or f32 rows `pos` with ldp) or, tiled, mega_relation_attention_tiled_pos_dt on
+    ptrs = the addresses of (q, k, vt, resid, bias_v) -> the return code"""
+    ops = _ops()
+    q, k, vt, resid, bias_v = ptrs
+    head = (q, 1024, k, 1024, vt, ldv)
+    tail = (resid, 1024, bias_v, out, 1024, Nq, Nk, 16, 0.125, ops._DT[dtype], ws, ws_bytes, ops._stream())
+    if tiled:
+        return lib.mega_relation_attention_tiled_pos_dt(*head, pos, *tail)
+    return lib.mega_relation_attention(*head, pos, ldp, *tail)
+
+
+def test_single_entry_points_are_batches_of_one(dev):
+    """mega_position_logits_tiled_dt, mega_relation_attention_tiled_pos_dt and mega_relation_attention, which no Python wrapper
+    calls any more (ops.relation_attention and the tiled ops.position_logits are one-problem calls of the batched wrappers):
+    each fills one descriptor and goes through the batched launcher, so its output has the bits of the one-problem
+    ops.*_batched call on the same operands and is within the batched tests' bounds of the float64 formula.
+      bf16 35 x 97: the tile-ordered logits, then the attention on them with a bf16 residual.  The boxes are
+        mc.pos_problem's: the exact f32 formula is itself 2.8e-4 (max) / 4.3e-7 (mean) from float64 on exp() there, well
+        inside the 6e-3 / 1e-3 the fast kernel is allowed;
+      f32 3 x 33: f32 `pos` rows with ldp = 64 from mega_position_logits(precise=1);
+      bf16 40 x 1500, no position term: with its workspace (3 key-range splits: the combine launch) and with ws = NULL
+        (unsplit: another summation order, so measured against the float64 formula only).
+    Nq = 0 returns MEGA_OK before any pointer check; a NULL q with Nq > 0 is MEGA_ERR_ARG."""
+    ops = _ops()
+    lib = _lib().load()
+
+    def item(shape, dtype, seed):
+        it = mc.attn_item(shape, dtype, seed=seed)
+        it["dev"] = tuple(it[n].to(dev) for n in ("q", "k", "vt", "resid", "bias_v"))
+        it["ptrs"] = tuple(t.data_ptr() for t in it["dev"])
+        return it
+
+    def single(it, pos, ldp, out, ws=None, ws_bytes=0, tiled=False):
+        return _single_attention(lib, it["ptrs"], it["vt"].shape[1], it["Nq"], it["Nk"], it["q"].dtype, pos, ldp,
+                                 out.data_ptr(), ws, ws_bytes, tiled)
+
+    def batched_of_one(it, pos):
+        q, k, vt, resid, bias_v = it["dev"]
+        return ops.relation_attention_batched([{"q": q, "k": k, "vt": vt, "Nk": it["Nk"], "pos": pos, "resid": resid,
+                                                "bias_v": bias_v}])[0]
+
+    def check(what, out, it, pos_ref, want=None):
+        dtype = it["q"].dtype
+        ref = mc.relation_attention_f64(it["q"], it["k"], it["vt"], it["Nk"], pos=pos_ref, resid=it["resid"], bias_v=it["bias_v"])
+        err = _relerr(out.cpu(), ref)
+        print("single entry %s: relerr %.3g" % (what, err))
+        assert torch.isfinite(out.float()).all() and err < mc.ATTN_BOUND[dtype], (what, err)
+        if want is not None:
+            assert torch.equal(out, want), (what, (out.float() - want.float()).abs().max().item())
+
+    # ---- bf16 35 x 97: tile-ordered logits, then the attention that reads them
+    dt = torch.bfloat16
+    Nq, Nk = 35, 97
+    it = item((Nq, Nk), dt, 1)
+    wg_t, bg, dim_mat = mc.pos_weights()
+    bq, bk = mc.pos_problem(Nq, Nk)
+    dargs = (wg_t.to(dev), bg.to(dev), dim_mat.to(dev))
+    bq_d, bk_d = bq.to(dev).contiguous(), bk.to(dev).contiguous()
+    pos = torch.full((16, (Nk + 31) // 32, Nq, 32), SENT16, dtype=torch.int16, device=dev).view(dt)
+    rc = lib.mega_position_logits_tiled_dt(bq_d.data_ptr(), bk_d.data_ptr(), *(t.data_ptr() for t in dargs), pos.data_ptr(),
+                                           Nq, Nk, ops._DT[dt], ops._stream())
+    assert rc == 0
+    pos_b = ops.position_logits_batched([bq_d], [bk_d], *dargs, precise=False, tiled=dt)[0]
+    got = _untile_pos(pos.cpu(), Nk)
+    assert torch.isfinite(got).all() and torch.equal(got, _untile_pos(pos_b.cpu(), Nk))
+    err = (got.double().exp() - mc.position_logits_f64(bq, bk, wg_t, bg).exp()).abs()
+    print("single entry position logits (%d, %d) vs float64: max %.3g mean %.3g" % (Nq, Nk, err.max(), err.mean()))
+    assert err.max() < 6e-3 and err.mean() < 1e-3, (err.max(), err.mean())
+    out = torch.empty((Nq, 1024), dtype=dt, device=dev)
+    assert lib.mega_relation_attention_splits(Nq, Nk, 16) == 1
+    assert single(it, pos.data_ptr(), 0, out, tiled=True) == 0
+    check("tiled_pos_dt bf16 (35, 97)", out, it, got, want=batched_of_one(it, pos_b))
+
+    # ---- f32 3 x 33: f32 position rows with a leading dimension
+    Nq, Nk = 3, 33
+    it = item((Nq, Nk), torch.float32, 2)
+    wg, bg2, dm2 = (t.to(dev) for t in mc.attn_pos_weights())
+    rows = torch.empty((16, Nq, 64), dtype=torch.float32, device=dev)
+    rc = lib.mega_position_logits(it["rq"].to(dev).data_ptr(), it["rk"].to(dev).data_ptr(), wg.data_ptr(), bg2.data_ptr(),
+                                  dm2.data_ptr(), rows.data_ptr(), Nq, Nk, 64, 1, ops._stream())
+    assert rc == 0
+    out = torch.empty((Nq, 1024), dtype=torch.float32, device=dev)
+    assert single(it, rows.data_ptr(), 64, out) == 0
+    check("f32 (3, 33) pos rows", out, it, rows.cpu()[:, :, :Nk], want=batched_of_one(it, rows))
+
+    # ---- bf16 40 x 1500, no position term: split 3 ways with the workspace, unsplit without
+    Nq, Nk = 40, 1500
+    it = item((Nq, Nk), dt, 3)
+    assert lib.mega_relation_attention_splits(Nq, Nk, 16) == 3
+    nb = lib.mega_relation_attention_workspace_bytes(Nq, Nk, 16)
+    assert nb > 0
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    want = batched_of_one(it, None)
+    out = torch.empty((Nq, 1024), dtype=dt, device=dev)
+    assert single(it, None, 0, out, ws.data_ptr(), nb) == 0
+    check("bf16 (40, 1500) three splits", out, it, None, want=want)
+    out1 = torch.empty((Nq, 1024), dtype=dt, device=dev)
+    assert single(it, None, 0, out1) == 0
+    check("bf16 (40, 1500) ws = NULL", out1, it, None)
+
+    # ---- the contract's early returns
+    nulls = (None,) * 5                            # every pointer NULL: Nq = 0 returns before looking at any
+    for tiled in (False, True):
+        assert _single_attention(lib, nulls, 0, 0, Nk, dt, None, 0, None, None, 0, tiled) == 0
+        assert _single_attention(lib, (None,) + it["ptrs"][1:], it["vt"].shape[1], Nq, Nk, dt, None, 0, out.data_ptr(), None, 0,
+                                 tiled) == 1       # q = NULL with Nq = 40
+    assert lib.mega_position_logits_tiled_dt(None, None, None, None, None, None, 0, 97, ops._DT[dt], ops._stream()) == 0
+    assert lib.mega_position_logits_tiled_dt(None, bk_d.data_ptr(), *(t.data_ptr() for t in dargs), pos.data_ptr(), 35, 97,
+                                             ops._DT[dt], ops._stream()) == 1
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)                  # (the refused calls launched nothing)
+
+
 # ------------------------------------------------------------------------------------------------ 3. FGFA ring / window / group
 FGFA_W_BOUND = {torch.float32: 2e-5, torch.bfloat16: 2e-3}        # test_fgfa_warp_aggregate's bounds
 FGFA_O_BOUND = {torch.float32: 1e-5, torch.bfloat16: 1e-2}
