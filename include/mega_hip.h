@@ -564,6 +564,41 @@ int mega_link_tracks(const float* box, const float* score, const int* pos, const
                      int T, int F, int C, long long N, float score_thresh, float link_iou, int max_gap, int max_open,
                      long long* root, int* cnt, double* sum, float* mx, void* ws, size_t ws_bytes, void* stream);
 
+/* Tubelet AP: matching linked tracks (tubelets) against ground-truth tracks by temporal IoU
+ * (mega/pytorch_amd/track_eval.py defines it; the reference has no counterpart).  One workgroup per (video, label) task
+ * with P tubelets and G GT tracks (G <= 4096).  Phase 1 counts, per pair, both = frames where both have a box and hits =
+ * those where the box IoU (mega_vid_eval_match's: prediction rescaled by ratio in f32, +1 on x2 / y2, boxlist_iou) is
+ * >= 0.5f; the two i32 tables live in LDS when P * G <= 4096, else in the workspace.  Phase 2, per threshold num / den: the
+ * tubelets in rank order each take the untaken GT track with hits > 0 and hits * den >= num * union (union = tubelet
+ * length + GT length - both) of the largest hits / union, compared cross-multiplied in 64-bit integers; on an equal value
+ * the lowest GT track.  Inputs (device unless noted):
+ *   box [M][4] f32, frame [M] i32 (dataset frame), rank [M] i32 (the box's tubelet: its rank within its task): the tubelet
+ *   boxes sorted class-major then frame, seg_off [C * F + 1] i64 as for mega_seq_nms; ratio [F][2] f32;
+ *   gt_box [Gb][4] f32, gt_track [Gb] i32 (the box's GT track: its index within its task), sorted the same way,
+ *   gt_seg_off [C * F + 1] i64;
+ *   tasks [T][8] i32 = (class, first frame, frames, p0, P, g0, G, 0), the most boxes first; offs [T][2] i64 = (offset of the
+ *   task's P x G table in hits / both, offset of its table in the workspace or -1);
+ *   tubelet [slots] i32: the tubelet index u of task slot p0 + rank; tub_len [U] i32; gt_len [J] i32 by GT slot g0 + index;
+ *   thresholds: HOST int [R][2] = (num, den), 0 < num <= den <= 1024, R <= 8.
+ * Outputs: match [R][U] u8 and matched_gt [R][U] i32 (GT slot g0 + index, -1: none), written for the tubelets of the T
+ * tasks only (the caller presets 0 / -1); hits / both [n_pairs] i32 or both NULL: the pair tables, task by task.
+ * Negative sizes, a threshold outside the range, R outside 1..8: MEGA_ERR_ARG; workspace below
+ * mega_tubelet_match_workspace_bytes(ws_pairs) (ws_pairs = the pairs of the tasks with P * G > 4096): MEGA_ERR_WS; both
+ * before any launch.  T = 0 is a no-op.  A task whose table entries do not fit the sizes is skipped.  Does not
+ * synchronise. */
+size_t mega_tubelet_match_workspace_bytes(long long ws_pairs);
+int mega_tubelet_match(const float* box, const int* frame, const int* rank, const long long* seg_off, const float* ratio,
+                       const float* gt_box, const int* gt_track, const long long* gt_seg_off, const int* tasks,
+                       const long long* offs, const int* tubelet, const int* tub_len, const int* gt_len,
+                       const int* thresholds, int T, int F, int C, int R, long long M, long long Gb, long long U,
+                       long long J, long long slots, long long n_pairs, long long ws_pairs, unsigned char* match,
+                       int* matched_gt, int* hits, int* both, void* ws, size_t ws_bytes, void* stream);
+/* The tubelet score of track_eval.py: out[u] f64 = the f32 scores score[off[u] .. off[u+1]) (a tubelet's members in frame
+ * order) added in f64 in that order, divided by their count; with use_max = 1 the largest of them.  One thread per
+ * tubelet.  U = 0 is a no-op. */
+int mega_tubelet_scores(const float* score, const long long* off, long long U, long long M, int use_max, double* out,
+                        void* stream);
+
 /* Detection overlay of the demo (mega/pytorch_amd/demo.py defines it), in place on F original-size frames, no host round
  * trip.  Per frame: rows i < counts[f] with score > thr (strict), drawn in descending score order (equal scores: ascending
  * row); box -> original frame by ONE f32 multiply per coordinate (x * sx, y * sy; sx = f32(W / resized width) computed by

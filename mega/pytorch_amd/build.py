@@ -33,6 +33,7 @@ SOURCES = {
     "soft_nms.hip": ["-ffp-contract=off"],    # IoU, view mapping and score decay round as soft_nms.py's separate f32 ops
     "overlay.hip": ["-ffp-contract=off"],     # box rescale is one f32 multiply, the score digits one f64 multiply
     "proposal_recall.hip": ["-ffp-contract=off"],   # rescale + IoU round like the reference's separate f32 torch ops
+    "track_eval.hip": ["-ffp-contract=off"],  # the detection AP's rescale + IoU (box_math.h's vid_iou), bit for bit
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -29,6 +29,15 @@ __device__ __forceinline__ float box_iou1(const float4 a, const float4 b) {
   return box_iou1(a, box_area1(a), b, box_area1(b));
 }
 
+// The VID evaluations' IoU (vid_eval.hip's detection AP, track_eval.hip's frame hits) of a detection box p that is already
+// rescaled and carries vid_eval.py:209-214's +1 on x2 / y2 (pa = box_area1(p)) with a raw GT box g: g gets the same +1,
+// then boxlist_iou's operation order in f32.
+__device__ __forceinline__ float vid_iou(float4 p, float pa, float4 g) {
+  g.z += 1.0f;
+  g.w += 1.0f;
+  return box_iou1(p, pa, g, box_area1(g));
+}
+
 // f32 -> u32 whose unsigned order is the floats' order (the sort keys' high word).  Floats that compare equal get equal
 // keys, so that the index in the low word breaks the tie: -0.0 takes +0.0's key (on the bits, not by `f + 0.f`, which
 // holds only as long as no flag lets the compiler drop the addition).  NaNs are not ordered by any caller's contract.

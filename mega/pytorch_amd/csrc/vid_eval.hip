@@ -26,13 +26,7 @@ __device__ __forceinline__ float wave_max_f(float v) {
   return v;
 }
 
-// One GT slot's IoU with the (rescaled, +1) detection box p of area pa: the GT box gets vid_eval.py:209-214's +1 on
-// x2 / y2 first, then boxlist_iou's operation order in f32 (box_math.h).
-__device__ __forceinline__ float vid_iou(float4 p, float pa, float4 g) {
-  g.z += 1.0f;
-  g.w += 1.0f;
-  return box_iou1(p, pa, g, box_area1(g));
-}
+// One GT slot's IoU with the (rescaled, +1) detection box: box_math.h's vid_iou, shared with track_eval.hip.
 
 // torch.max / torch.min / clamp(min=0) propagate NaN; fmaxf / fminf do not.  The reference's elementwise ops are
 // reproduced for NaN-free inputs by fmaxf / fminf; a NaN coordinate gives a NaN IoU either way through the

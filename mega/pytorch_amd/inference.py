@@ -319,7 +319,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     detections (what Seq-NMS kept, if both are on) linked into tracks on the main process.  predictions_tracks.pth holds
     them with the extra field "track_ids" (and the rescored "scores" when rescore is set), tracks.txt one line per track
     (tracks.format_table), and with rescore and anno_path result_tracks.txt the evaluation of the rescored list;
-    predictions.pth, result.txt and the return value do not change.
+    predictions.pth, result.txt and the return value do not change.  With "tubelet_ap": True in the dict (and optionally
+    "tubelet_score": "mean" | "max") and anno_path, the linked tracks are also scored against the annotations' <trackid>
+    tracks (track_eval.evaluate_tracks): result_tubelets.txt.
     cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
     (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
     Seq-NMS, track linking, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY
@@ -333,6 +335,11 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     if tracks is not None and tracks is not False:
         from . import tracks as tr
         track_params = {} if tracks is True else dict(tracks)
+        tubelet_ap = bool(track_params.pop("tubelet_ap", False))
+        tubelet_score = track_params.pop("tubelet_score", "mean")
+        if tubelet_ap:
+            from . import track_eval
+            track_eval.check_params(tubelet_score=tubelet_score)
         tr.check_params(**track_params)                          # (a bad value raises before the run, not after it)
     if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
         raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
@@ -395,4 +402,8 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if tracked is not None and track_params.get("rescore") is not None:
             vid_eval.evaluate_detections(tracked, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                          logger=logger, result_name="result_tracks.txt")
+        if tracked is not None and tubelet_ap:
+            track_eval.evaluate_tracks(tracked, vid_eval.VIDTrackGroundTruth(img_index, anno_path),
+                                       [(v["start"], v["seg_len"]) for v in index.videos], tubelet_score=tubelet_score,
+                                       output_folder=output_folder, device=device, logger=logger)
     return predictions if rescored is None else rescored

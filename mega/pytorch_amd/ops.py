@@ -1508,6 +1508,72 @@ def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, m
     return root, cnt, acc, mx
 
 
+# ------------------------------------------------------------------------------------------------ tubelet AP
+def tubelet_scores(score, off, use_max=False):
+    """A tubelet's score as track_eval.py defines it (include/mega_hip.h mega_tubelet_scores).  score [M] f32: the members
+    sorted by tubelet, then frame; off [U+1] i64.  -> [U] f64 on the device: the f64 sum in that order / the count, or the
+    largest member with use_max."""
+    _gpu(score, off)
+    lib = _lib.load()
+    M, U = score.shape[0], off.shape[0] - 1
+    assert score.dtype == torch.float32 and off.dtype == torch.int64 and score.is_contiguous() and off.is_contiguous()
+    assert score.shape == (M,) and off.shape == (U + 1,)
+    out = torch.zeros(U, dtype=torch.float64, device=score.device)
+    _tok = _pb("tubelet_scores")
+    rc = lib.mega_tubelet_scores(_ptr(score), _ptr(off), U, M, int(bool(use_max)), _ptr(out), _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_tubelet_scores")
+    return out
+
+
+def tubelet_match(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off, tasks, offs, tubelet, tub_len, gt_len,
+                  thresholds, F, C, n_pairs, ws_pairs, want_pairs=True, return_workspace=False):
+    """Tubelets against GT tracks over T (video, label) tasks (include/mega_hip.h mega_tubelet_match).  box [M,4] f32,
+    frame / rank [M] i32 sorted class-major then frame, seg_off [C*F+1] i64; ratio [F,2] f32; gt_box [Gb,4] f32, gt_track
+    [Gb] i32 sorted the same way, gt_seg_off [C*F+1] i64; tasks [T,8] i32 (class, first frame, frames, p0, P, g0, G, 0),
+    the most boxes first; offs [T,2] i64 (pair-table offset, workspace offset or -1); tubelet [slots] i32; tub_len [U]
+    i32; gt_len [J] i32; thresholds: (num, den) pairs (host).  n_pairs: the sum of P * G; ws_pairs: that of the tasks whose
+    table does not fit LDS.  -> match [R,U] u8 (0 outside the tasks), matched_gt [R,U] i32 (GT slot, -1: none), hits /
+    both [n_pairs] i32 (None without want_pairs), on the device; with return_workspace also the workspace's two tables
+    [ws_pairs] i32, preset to -1.  Does not synchronise."""
+    _gpu(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off, tasks, offs, tubelet, tub_len, gt_len)
+    lib = _lib.load()
+    M, Gb, T, U, J, slots = box.shape[0], gt_box.shape[0], tasks.shape[0], tub_len.shape[0], gt_len.shape[0], tubelet.shape[0]
+    for t, dt in ((box, torch.float32), (frame, torch.int32), (rank, torch.int32), (seg_off, torch.int64),
+                  (ratio, torch.float32), (gt_box, torch.float32), (gt_track, torch.int32), (gt_seg_off, torch.int64),
+                  (tasks, torch.int32), (offs, torch.int64), (tubelet, torch.int32), (tub_len, torch.int32),
+                  (gt_len, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert box.shape == (M, 4) and frame.shape == (M,) and rank.shape == (M,) and seg_off.shape == (C * F + 1,)
+    assert ratio.shape == (F, 2) and gt_box.shape == (Gb, 4) and gt_track.shape == (Gb,)
+    assert gt_seg_off.shape == (C * F + 1,) and tasks.shape == (T, 8) and offs.shape == (T, 2)
+    thr = [(int(n), int(d)) for n, d in thresholds]
+    R = len(thr)
+    thr_c = (ctypes.c_int * (2 * R))(*[v for nd in thr for v in nd])
+    dev = box.device
+    match = torch.zeros((R, U), dtype=torch.uint8, device=dev)
+    matched_gt = torch.full((R, U), -1, dtype=torch.int32, device=dev)
+    hits = torch.zeros(int(n_pairs), dtype=torch.int32, device=dev) if want_pairs else None
+    both = torch.zeros(int(n_pairs), dtype=torch.int32, device=dev) if want_pairs else None
+    nb = lib.mega_tubelet_match_workspace_bytes(int(ws_pairs))
+    ws = _ws(max(nb, 1), dev)
+    if return_workspace:
+        ws.fill_(0xFF)
+    _tok = _pb("tubelet_match")
+    rc = lib.mega_tubelet_match(_ptr(box), _ptr(frame), _ptr(rank), _ptr(seg_off), _ptr(ratio), _ptr(gt_box), _ptr(gt_track),
+                                _ptr(gt_seg_off), _ptr(tasks), _ptr(offs), _ptr(tubelet), _ptr(tub_len), _ptr(gt_len),
+                                ctypes.cast(thr_c, ctypes.c_void_p), T, int(F), int(C), R, M, Gb, U, J, slots, int(n_pairs),
+                                int(ws_pairs), _ptr(match), _ptr(matched_gt), _ptr(hits), _ptr(both), _ptr(ws), nb,
+                                _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_tubelet_match")
+    if return_workspace:
+        n, half = int(ws_pairs), nb // 2             # two arrays of n i32, each rounded up to 256 bytes
+        tabs = (ws[:4 * n].view(torch.int32), ws[half:half + 4 * n].view(torch.int32))
+        return match, matched_gt, hits, both, tabs
+    return match, matched_gt, hits, both
+
+
 # ------------------------------------------------------------------------------------------------ demo overlay
 def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, thickness, palette, atlas,
                        select_only=False):

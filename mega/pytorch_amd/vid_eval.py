@@ -154,6 +154,65 @@ class VIDGroundTruth(object):
         return self.classes[class_id]
 
 
+def parse_track_ids(root, name="<annotation>", classes_to_ind=CLASSES_TO_IND):
+    """The <trackid> of every object parse_annotation keeps, in its order -> [n] i64.  ValueError (naming the file) for a
+    kept object without one."""
+    ids = []
+    for obj in root.findall("object"):
+        if obj.find("name").text not in classes_to_ind:
+            continue
+        t = obj.find("trackid")
+        if t is None or t.text is None or not t.text.strip():
+            raise ValueError("%s: an object has no <trackid>" % name)
+        ids.append(int(t.text))
+    return np.asarray(ids, dtype=np.int64)
+
+
+class VIDTrackGroundTruth(VIDGroundTruth):
+    """VIDGroundTruth plus track_ids [G] i64: the <trackid> of every kept object, what track_eval.evaluate_tracks judges
+    linked tracks against.  Its .npz cache holds the same arrays and "track_ids" (a VIDGroundTruth cache, which has none,
+    is re-read from the XML files and overwritten)."""
+
+    def __init__(self, img_index, anno_path, cache=None):
+        from .inference import VIDTestIndex
+        self.image_set_index = list(VIDTestIndex(img_index).image_set_index)
+        if cache and os.path.exists(cache):
+            z = np.load(cache, allow_pickle=False)
+            if "track_ids" in z.files and list(z["image_set_index"]) == self.image_set_index:
+                self._set(z["boxes"], z["labels"], z["off"], z["height"], z["width"])
+                self.track_ids = np.ascontiguousarray(z["track_ids"], dtype=np.int64)
+                return
+            logging.getLogger("mega.pytorch_amd.vid_eval").warning("%s lists other frames or no track ids: re-reading the "
+                                                                   "XML files", cache)
+        annos = []
+        for name in self.image_set_index:
+            path = os.path.join(anno_path, name + ".xml")
+            root = ET.parse(path).getroot()
+            annos.append(dict(parse_annotation(root), track_ids=parse_track_ids(root, path)))
+        self._set_annos(annos)
+        if cache:
+            d = os.path.dirname(os.path.abspath(cache))
+            os.makedirs(d, exist_ok=True)
+            np.savez(cache, image_set_index=np.asarray(self.image_set_index), boxes=self.boxes, labels=self.labels,
+                     off=self.off, height=self.height, width=self.width, track_ids=self.track_ids)
+
+    @classmethod
+    def from_annotations(cls, annos):
+        """From a list of per-frame dicts: parse_annotation()'s keys plus "track_ids" [n]."""
+        self = cls.__new__(cls)
+        self.image_set_index = None
+        self._set_annos(annos)
+        return self
+
+    def _set_annos(self, annos):
+        super(VIDTrackGroundTruth, self)._set_annos(annos)
+        for a in annos:
+            if "track_ids" not in a or len(np.asarray(a["track_ids"]).reshape(-1)) != len(a["labels"]):
+                raise ValueError("VIDTrackGroundTruth: every frame needs one track id per GT box")
+        self.track_ids = np.concatenate([np.asarray(a["track_ids"], np.int64).reshape(-1) for a in annos]) if annos else \
+            np.zeros((0,), np.int64)
+
+
 def load_motion_iou(path):
     """vid_groundtruth_motion_iou.mat -> list (one entry per frame) of f64 arrays, entry j of frame i =
     m['motion_iou'][i][0][j][0], or 0 where that cell is empty (the values vid_eval.py:133-137 means to build).  In the

@@ -44,7 +44,9 @@ def video_lengths(videos, frames, rng, longest=2400):
 
 
 def make_set(videos=555, frames=176126, dets=300, classes=30, seed=0, lengths=None):
-    """-> {"box" [N,4] f32, "score" [N] f32, "label" [N] i64, "videos" [(start, length)], "dets"}, N = frames * dets."""
+    """-> {"box" [N,4] f32, "score" [N] f32, "label" [N] i64, "videos" [(start, length)], "dets"}, N = frames * dets; and
+    the tracks the detections were jittered around as ground truth: "gt_box" [G,4] f32 (rounded, clipped), "gt_label" [G]
+    i64, "gt_track" [G] i64 (the track's number within its video), "gt_off" [F+1] i64 (frame f's GT boxes)."""
     rng = np.random.default_rng(seed)
     lens = np.asarray(lengths, np.int64) if lengths is not None else video_lengths(videos, frames, rng)
     F = int(lens.sum())
@@ -54,6 +56,7 @@ def make_set(videos=555, frames=176126, dets=300, classes=30, seed=0, lengths=No
     W, H, DUP = 640.0, 480.0, 3
     f0 = 0
     vids = []
+    gt_box, gt_label, gt_track, gt_count = [], [], [], np.zeros(F, np.int64)
     for L in lens.tolist():
         vids.append((f0, L))
         K = int(rng.integers(1, 7))                          # tracks in this video
@@ -89,9 +92,17 @@ def make_set(videos=555, frames=176126, dets=300, classes=30, seed=0, lengths=No
         box[f0:f0 + L] = np.clip(vb, 0, [W - 1, H - 1, W - 1, H - 1])
         score[f0:f0 + L] = vs
         label[f0:f0 + L] = vl
+        tt, kk = np.nonzero(active.T)                        # (frame, track) of every GT box, frame-major
+        gt_box.append(np.round(np.clip(tb[kk, tt], 0, [W - 1, H - 1, W - 1, H - 1])).astype(np.float32))
+        gt_label.append(tcls[kk].astype(np.int64))
+        gt_track.append(kk.astype(np.int64))
+        gt_count[f0:f0 + L] = active.sum(0)
         f0 += L
+    gt_off = np.zeros(F + 1, np.int64)
+    gt_off[1:] = np.cumsum(gt_count)
     return {"box": box.reshape(-1, 4), "score": score.reshape(-1), "label": label.reshape(-1), "videos": vids,
-            "dets": dets}
+            "dets": dets, "gt_box": np.concatenate(gt_box).reshape(-1, 4), "gt_label": np.concatenate(gt_label),
+            "gt_track": np.concatenate(gt_track), "gt_off": gt_off}
 
 
 def to_boxlists(s, lo=0, hi=None):

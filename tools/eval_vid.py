@@ -16,6 +16,11 @@ the detections (what Seq-NMS kept, with --seq-nms) into tracks (mega.pytorch_amd
 field "track_ids", tracks.txt with one line per track, and with --tracks-rescore avg|max result_tracks.txt, the evaluation
 of the rescored detections.
 
+--tubelet-ap (with --tubelet-score mean|max) scores tracks against the annotations' <trackid> tracks
+(mega.pytorch_amd.track_eval): the tubelet AP at temporal IoU 0.25 / 0.5 / 0.75 -> result_tubelets.txt.  With --tracks it
+judges the tracks just linked; without, --predictions must already carry the field "track_ids" (a
+predictions_tracks.pth).
+
 --box-only evaluates proposals instead (predictions made with MODEL.RPN_ONLY True, field "objectness"): the recall of the
 GT boxes at IoU 0.5 by each frame's first --limit proposals -> proposal_result.txt ("Recall: x", the reference's
 do_vid_evaluation(box_only=True)); --recall-table adds the recall at limits 10 / 50 / 100 / 300 and IoU 0.50 .. 0.95 with
@@ -53,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--tracks-min-len", type=int, default=1, help="tracks: shorter tracks get no id")
     ap.add_argument("--tracks-rescore", choices=("none", "avg", "max"), default="none",
                     help="tracks: replace a linked box's score by its track's mean / max -> result_tracks.txt")
+    ap.add_argument("--tubelet-ap", action="store_true", help="tubelet AP of the tracks against the GT tracks "
+                    "(result_tubelets.txt)")
+    ap.add_argument("--tubelet-score", choices=("mean", "max"), default="mean", help="--tubelet-ap: a tubelet's score")
     ap.add_argument("--box-only", action="store_true", help="proposal recall of RPN-only predictions (proposal_result.txt)")
     ap.add_argument("--limit", type=int, default=300, help="--box-only: proposals used per frame (at most 1024)")
     ap.add_argument("--recall-table", action="store_true", help="--box-only: also the recall per limit and IoU threshold")
@@ -61,9 +69,16 @@ def main(argv=None):
         ap.error("--box-only evaluates proposals: --seq-nms / --motion-iou apply to detections")
     if a.box_only and a.tracks:
         ap.error("--box-only evaluates proposals: --tracks applies to detections")
+    if a.box_only and a.tubelet_ap:
+        ap.error("--box-only evaluates proposals: --tubelet-ap applies to tracks")
     from mega.pytorch_amd import inference, vid_eval
     preds = inference.load_predictions(a.predictions)
-    gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
+    if a.tubelet_ap and not a.tracks and not all(p.has_field("track_ids") for p in preds):
+        ap.error("--tubelet-ap without --tracks needs predictions with the field \"track_ids\" (predictions_tracks.pth)")
+    if a.tubelet_ap:        # (the same boxes and labels, plus each object's <trackid>; its cache holds the ids too)
+        gt = vid_eval.VIDTrackGroundTruth(a.img_index, a.anno_path, cache=a.cache)
+    else:
+        gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
     motion = vid_eval.load_motion_iou(a.motion_iou) if a.motion_iou else None
     out = a.output_folder or os.path.dirname(os.path.abspath(a.predictions))
     if a.box_only:
@@ -102,6 +117,13 @@ def main(argv=None):
             res = vid_eval.evaluate_detections(tracked, gt, motion_iou=motion, output_folder=out, device=a.device,
                                                result_name="result_tracks.txt")
             sys.stdout.write("Tracks, rescored:\n" + vid_eval.format_result(res))
+        preds = tracked
+    if a.tubelet_ap:
+        from mega.pytorch_amd import track_eval
+        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
+        res = track_eval.evaluate_tracks(preds, gt, videos, tubelet_score=a.tubelet_score, output_folder=out,
+                                         device=a.device)
+        sys.stdout.write("Tubelets:\n" + res["text"])
     return 0
 
 
