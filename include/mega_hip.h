@@ -599,6 +599,27 @@ int mega_tubelet_match(const float* box, const int* frame, const int* rank, cons
 int mega_tubelet_scores(const float* score, const long long* off, long long U, long long M, int use_max, double* out,
                         void* stream);
 
+/* Motion IoU of every GT box (mega/pytorch_amd/motion_iou.py defines it; the reference reads such values from a file):
+ * the mean IoU of a box with the boxes of its own track in the +-W neighbouring frames of its video.  One wave64 per
+ * frame: its lanes stride over the frame's (box, offset) pairs, each scanning the neighbour frame's track ids; the pair
+ * IoUs (the box with +1 on x2 / y2 against the neighbour: mega_vid_eval_match's IoU of a detection that coincides with
+ * the box) are kept per box in offset order (-W .. -1, +1 .. +W), in LDS while a frame's boxes x 2W <= 2048, else in the
+ * workspace; one lane per box then adds the found ones in that order in f64 and divides by their count.  No atomics: the
+ * same bits on every run.
+ *   gt_box [G][4] f32, gt_track [G] i64 (unique within a frame), gt_off [F + 1] i64 (frame f's boxes), video_start /
+ *   video_end [F] i32: the frame range [start, end) of frame f's video; W in 1..64; max_gt: the most boxes of a frame
+ *   (<= 4096).
+ * Outputs: values [G] f64 (0.0 without a neighbour, the quiet NaN 0x7ff8000000000000 if a pair IoU is NaN), counts [G] i32
+ * (the neighbours found).  A frame whose offsets do not fit G or that holds more than max_gt boxes is skipped.
+ * NULL pointers (gt_box / gt_track / values / counts may be NULL only when G = 0, video_start / video_end only when F = 0),
+ * F < 0, G < 0, W outside 1..64, max_gt outside 0..4096: MEGA_ERR_ARG; a workspace below mega_motion_iou_workspace_bytes(G, W, max_gt) (0 when max_gt * 2W <=
+ * 2048, else the slots of all G boxes): MEGA_ERR_WS; both before any launch.  F = 0 or G = 0 launches nothing.  Does not
+ * synchronise. */
+size_t mega_motion_iou_workspace_bytes(long long G, int W, int max_gt);
+int mega_motion_iou(const float* gt_box, const long long* gt_track, const long long* gt_off, const int* video_start,
+                    const int* video_end, int F, long long G, int W, int max_gt, double* values, int* counts, void* ws,
+                    size_t ws_bytes, void* stream);
+
 /* Detection overlay of the demo (mega/pytorch_amd/demo.py defines it), in place on F original-size frames, no host round
  * trip.  Per frame: rows i < counts[f] with score > thr (strict), drawn in descending score order (equal scores: ascending
  * row); box -> original frame by ONE f32 multiply per coordinate (x * sx, y * sy; sx = f32(W / resized width) computed by

@@ -103,6 +103,8 @@ SIGNATURES = {
     "mega_tubelet_match_workspace_bytes": (c_size_t, [c_longlong]),
     "mega_tubelet_match": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_longlong] * 7 + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "mega_tubelet_scores": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_void_p]),
+    "mega_motion_iou_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
+    "mega_motion_iou": (c_int, [c_void_p] * 5 + [c_int, c_longlong, c_int, c_int] + [c_void_p] * 3 + [c_size_t, c_void_p]),
     "mega_overlay_detections_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mega_overlay_detections": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                         c_float, c_float, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,

@@ -34,6 +34,7 @@ SOURCES = {
     "overlay.hip": ["-ffp-contract=off"],     # box rescale is one f32 multiply, the score digits one f64 multiply
     "proposal_recall.hip": ["-ffp-contract=off"],   # rescale + IoU round like the reference's separate f32 torch ops
     "track_eval.hip": ["-ffp-contract=off"],  # the detection AP's rescale + IoU (box_math.h's vid_iou), bit for bit
+    "motion_iou.hip": ["-ffp-contract=off"],  # the same vid_iou between the boxes of one GT track, bit for bit
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -310,7 +310,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
     evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
     result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
-    vid_eval.load_motion_iou() lists (motion-specific AP).  The return value is the list[BoxList] either way.
+    vid_eval.load_motion_iou() lists (motion-specific AP); or "derive" / {"derive": True, "window": N}: the table is
+    derived from the <trackid> tracks of the annotations under anno_path (motion_iou.derive, window 10 by default) and
+    goes to every evaluation of the run.  The return value is the list[BoxList] either way.
     seq_nms: None (off), True or a dict of seq_nms.seq_nms's link_iou / nms_iou / rescore: Seq-NMS over all videos on
     the main process after the gather.  predictions.pth stays the raw list; the rescored one goes to
     predictions_seq_nms.pth and its evaluation to result_seq_nms.txt (result.txt stays the raw evaluation); the return
@@ -341,6 +343,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
             from . import track_eval
             track_eval.check_params(tubelet_score=tubelet_score)
         tr.check_params(**track_params)                          # (a bad value raises before the run, not after it)
+    if isinstance(motion_iou, dict) or motion_iou == "derive":
+        from . import motion_iou as mi
+        mi.check_request(motion_iou, anno_path)                  # (a bad window raises before the run, not after it)
     if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
         raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
     final = _final_filter(cfg) or _final_filter(model.cfg)      # (raises ValueError for a bad value, before any device work)
@@ -388,9 +393,10 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         logger.info("Linked %d tracks", len(table))
     if anno_path is not None:
         from . import vid_eval
-        if isinstance(motion_iou, str):
-            motion_iou = vid_eval.load_motion_iou(motion_iou)
-        gt = vid_eval.VIDGroundTruth(img_index, anno_path)
+        from . import motion_iou as mi
+        motion_iou, gt = mi.resolve(motion_iou, img_index, anno_path, device=device)     # (a path, lists: as ever)
+        if gt is None:
+            gt = vid_eval.VIDGroundTruth(img_index, anno_path)
         if box_only:
             vid_eval.evaluate_proposals(predictions, gt, output_folder=output_folder, device=device, logger=logger)
             return predictions

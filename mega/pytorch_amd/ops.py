@@ -1574,6 +1574,39 @@ def tubelet_match(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off
     return match, matched_gt, hits, both
 
 
+# ------------------------------------------------------------------------------------------------ motion IoU
+def motion_iou(gt_box, gt_track, gt_off, video_start, video_end, window, max_gt, return_workspace=False):
+    """The motion IoU of every GT box (include/mega_hip.h mega_motion_iou; mega/pytorch_amd/motion_iou.py defines it).
+    gt_box [G,4] f32, gt_track [G] i64, gt_off [F+1] i64, video_start / video_end [F] i32 (the frame range of each frame's
+    video), window: W in 1..64, max_gt: the most boxes of one frame.  -> values [G] f64, counts [G] i32 on the device
+    (counts preset to -1: a frame the kernel skipped keeps it); with return_workspace also the workspace's slots as
+    [G, 2W] i32 (the pair IoUs' bits, -1: no neighbour; preset to -1), or None when no frame needs it.  Does not
+    synchronise."""
+    _gpu(gt_box, gt_track, gt_off, video_start, video_end)
+    lib = _lib.load()
+    G, F, W = gt_box.shape[0], gt_off.shape[0] - 1, int(window)
+    for t, dt in ((gt_box, torch.float32), (gt_track, torch.int64), (gt_off, torch.int64), (video_start, torch.int32),
+                  (video_end, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert gt_box.shape == (G, 4) and gt_track.shape == (G,) and gt_off.shape == (F + 1,)
+    assert video_start.shape == (F,) and video_end.shape == (F,)
+    dev = gt_box.device
+    values = torch.zeros(G, dtype=torch.float64, device=dev)
+    counts = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    nb = lib.mega_motion_iou_workspace_bytes(G, W, int(max_gt))
+    ws = _ws(max(nb, 1), dev)
+    if return_workspace:
+        ws.fill_(0xFF)
+    _tok = _pb("motion_iou")
+    rc = lib.mega_motion_iou(_ptr(gt_box), _ptr(gt_track), _ptr(gt_off), _ptr(video_start), _ptr(video_end), F, G, W,
+                             int(max_gt), _ptr(values), _ptr(counts), _ptr(ws), nb, _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_motion_iou")
+    if return_workspace:
+        return values, counts, (ws[:8 * G * W].view(torch.int32).reshape(G, 2 * W) if nb else None)
+    return values, counts
+
+
 # ------------------------------------------------------------------------------------------------ demo overlay
 def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, thickness, palette, atlas,
                        select_only=False):

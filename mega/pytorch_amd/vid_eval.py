@@ -355,7 +355,8 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
     """eval_detection_vid (+ do_vid_evaluation's result.txt) for `predictions` (list[BoxList] with "scores" / "labels",
     boxes in the size each BoxList carries: what inference() returns or inference.load_predictions() reads, written by this
     package or by the reference) against `groundtruth` (VIDGroundTruth, same frames, same order).
-    motion_iou: None (one range, "all") or load_motion_iou()'s per-frame lists (the 4 ranges all / fast / medium / slow).
+    motion_iou: None (one range, "all") or load_motion_iou()'s per-frame lists (the 4 ranges all / fast / medium / slow);
+    motion_iou.derive() computes such lists from the annotations' tracks.
     result_name: the file the text goes to in output_folder (result_seq_nms.txt for Seq-NMS-rescored predictions).
     -> {motion_index: {"ap": ndarray [n_fg_class] f64 (NaN: class not seen or without non-ignored GT), "map": nanmean}}."""
     if box_only:

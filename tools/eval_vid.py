@@ -2,10 +2,16 @@
 the reference's inference_no_model (mega_core/engine/inference.py:135-160), matching on the GPU (mega.pytorch_amd.vid_eval).
 
   python tools/eval_vid.py --predictions OUT/predictions.pth --img-index ImageSets/VID_val_videos.txt \\
-      --anno-path Annotations/VID/val [--motion-iou vid_groundtruth_motion_iou.mat] [--output-folder OUT] [--cache gt.npz]
+      --anno-path Annotations/VID/val [--motion-iou vid_groundtruth_motion_iou.mat | derive] [--output-folder OUT]
+      [--cache gt.npz]
 
 predictions.pth may be written by this package or by the reference.  result.txt goes to --output-folder (default: the
 folder of predictions.pth); the text is also printed.
+
+--motion-iou derive (the literal word instead of a path; with --motion-window N, default 10) derives the motion IoU table
+from the annotations' <trackid> tracks (mega.pytorch_amd.motion_iou) instead of reading the file, so that motion-specific
+AP works on any subset of videos or VID-style dataset; the table goes to every evaluation of the run (raw, --seq-nms,
+--tracks).  --save-motion-iou PATH also writes it as a .mat in the file's layout.
 
 --seq-nms (with --seq-nms-link-iou / --seq-nms-iou / --seq-nms-rescore) also applies Seq-NMS (mega.pytorch_amd.seq_nms)
 over the videos of --img-index, writes predictions_seq_nms.pth and result_seq_nms.txt to the output folder and prints
@@ -41,7 +47,11 @@ def main(argv=None):
     ap.add_argument("--predictions", required=True, help="predictions.pth (list[BoxList])")
     ap.add_argument("--img-index", required=True, help="the 4-column VID index file the predictions were made on")
     ap.add_argument("--anno-path", required=True, help="directory of <video>/<frame>.xml annotations")
-    ap.add_argument("--motion-iou", default=None, help="vid_groundtruth_motion_iou.mat: adds fast / medium / slow AP")
+    ap.add_argument("--motion-iou", default=None, help="vid_groundtruth_motion_iou.mat, or the word 'derive' (the table "
+                    "is computed from the annotations' tracks): adds fast / medium / slow AP")
+    ap.add_argument("--motion-window", type=int, default=None, help="--motion-iou derive: neighbour frames on each side "
+                    "(1 .. 64, default 10)")
+    ap.add_argument("--save-motion-iou", default=None, help="--motion-iou derive: also write the derived table to this .mat")
     ap.add_argument("--output-folder", default=None, help="where result.txt goes (default: next to predictions.pth)")
     ap.add_argument("--cache", default=None, help="optional .npz cache of the parsed annotations")
     ap.add_argument("--device", default="cuda:0")
@@ -71,15 +81,27 @@ def main(argv=None):
         ap.error("--box-only evaluates proposals: --tracks applies to detections")
     if a.box_only and a.tubelet_ap:
         ap.error("--box-only evaluates proposals: --tubelet-ap applies to tracks")
+    derive = a.motion_iou == "derive"
+    if not derive and (a.motion_window is not None or a.save_motion_iou):
+        ap.error("--motion-window / --save-motion-iou apply to --motion-iou derive")
+    if derive and a.motion_window is not None and not 1 <= a.motion_window <= 64:
+        ap.error("--motion-window must be in 1 .. 64, got %d" % a.motion_window)
     from mega.pytorch_amd import inference, vid_eval
     preds = inference.load_predictions(a.predictions)
     if a.tubelet_ap and not a.tracks and not all(p.has_field("track_ids") for p in preds):
         ap.error("--tubelet-ap without --tracks needs predictions with the field \"track_ids\" (predictions_tracks.pth)")
-    if a.tubelet_ap:        # (the same boxes and labels, plus each object's <trackid>; its cache holds the ids too)
+    if a.tubelet_ap or derive:      # (the same boxes and labels, plus each object's <trackid>; its cache holds the ids too)
         gt = vid_eval.VIDTrackGroundTruth(a.img_index, a.anno_path, cache=a.cache)
     else:
         gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
-    motion = vid_eval.load_motion_iou(a.motion_iou) if a.motion_iou else None
+    if derive:
+        from mega.pytorch_amd import motion_iou
+        motion = motion_iou.derive(gt, inference.VIDTestIndex(a.img_index).videos,
+                                   motion_iou.WINDOW if a.motion_window is None else a.motion_window, device=a.device)
+        if a.save_motion_iou:
+            motion_iou.save_mat(a.save_motion_iou, motion, off=gt.off)
+    else:
+        motion = vid_eval.load_motion_iou(a.motion_iou) if a.motion_iou else None
     out = a.output_folder or os.path.dirname(os.path.abspath(a.predictions))
     if a.box_only:
         res = vid_eval.evaluate_proposals(preds, gt, limit=a.limit, output_folder=out, device=a.device,
