@@ -103,6 +103,8 @@ int mega_stem_conv_bn_relu_bf16_u8(const void* frames_u8, const void* w_n176_bf1
 /* dtype = MEGA_BF16 or MEGA_F16 is the type of w_n176 and of `out`. */
 int mega_stem_pool_dt(const void* in, int u8, const void* w_n176, const float* scale, const float* bias, void* out, int N,
                       int H, int W, float mean0, float mean1, float mean2, int to_bgr, int dtype, void* stream);
+/* The pooled tile (rows x columns) that is one unit of mega_stem_pool_dt's work. */
+void mega_stem_pool_tile(int* rows, int* cols);
 
 /* F.max_pool2d(kernel 3, stride 2, padding 1) on NHWC (resnet.py:365). */
 int mega_maxpool3x3s2_nhwc(const void* in, void* out, int N, int H, int W, int C, int dtype, void* stream);

@@ -672,150 +672,237 @@ __global__ __launch_bounds__(256, 4) void stem_mfma_kernel(const void* __restric
 
 // ------------------------------------------------------------------------------- stem + 3x3/2 max-pool in one kernel (bf16)
 // The stem's output (300 x 500 x 64 per frame, 19 MB) was written by stem_mfma_kernel only to be read back by the max-pool
-// (resnet.py:361-366: F.max_pool2d(x, 3, 2, 1)).  Here a block owns a 4 x 16 tile of POOLED pixels: it computes the 9 x 33
-// stem pixels their windows cover (297 GEMM rows in ten 32-row MFMA blocks, pixel p = row * 33 + col), stages them in LDS as
-// bf16 with everything outside the stem map forced to 0 (every window holds at least one real pixel and all values are >= 0
-// after the ReLU, so 0 is the identity of this max), and writes max over the 3 x 3 windows: the 19 MB never reach HBM.
-// Same patch / weight layout, same MFMA and K order as stem_mfma_kernel; max of bf16 values is exact: bit-identical to
-// stem + max-pool (tests/test_kernels_gpu.py::test_stem_pool_bit_equal).
-constexpr int SP_PY = 4, SP_PX = 16;                       // pooled tile
-constexpr int SP_TY = 2 * SP_PY + 1, SP_TX = 2 * SP_PX + 1; // stem pixels it needs: 9 x 33
-constexpr int SP_NPIX = SP_TY * SP_TX;                     // 297
-constexpr int SP_NBLK = (SP_NPIX + 31) / 32;               // 10 MFMA row blocks
-constexpr int SP_PH = 2 * SP_TY + 5, SP_PW = 2 * SP_TX + 5, SP_PS = 72;   // input patch 23 x 71, row stride 72
+// (resnet.py:361-366: F.max_pool2d(x, 3, 2, 1)).  Here a tile of 7 x 12 POOLED pixels is one unit of work: the 15 x 25 stem
+// pixels its windows cover are 375 GEMM rows in twelve 32-row MFMA blocks (pixel p = row * 25 + col; three blocks per wave,
+// 9 padding rows of 384), staged in LDS as bf16 with everything outside the stem map forced to 0 (every window holds at least
+// one real pixel and all values are >= 0 after the ReLU, so 0 is the identity of this max), then the max over the 3 x 3
+// windows is written: the 19 MB never reach HBM.
+//   * Two blocks per CU walk the tiles (linear tile index strided by the grid).  A lane keeps its 22 weight fragments
+//     in registers for the kernel's life: they are read from L2 once per block, not once per tile, and never pass through LDS.
+//   * The uint8 patch is fetched as 12-byte runs (4 pixels of one row, any byte alignment) and de-interleaved in registers;
+//     a run that hangs over the row's ends is fetched pixel by pixel, so no address outside the frames is ever formed.
+//   * The weights are the FIRST MFMA operand (the accumulator is channels x pixels): a lane owns 4 consecutive channels of
+//     one pixel per register group, so the staging writes are 8 bytes wide and the pixel's in-map test is once per row block.
+// Same patch layout and ascending K order as stem_mfma_kernel, a product a b of an MFMA does not depend on which operand
+// brought a; max of bf16 values is exact: bit-identical to stem + max-pool (tests/test_kernels_gpu.py::
+// test_stem_pool_bit_equal, tests/test_stem_pool_tiles_gpu.py).
+constexpr int SP_PY = 7, SP_PX = 12;                        // pooled tile (mega_stem_pool_tile reports it)
+constexpr int SP_TY = 2 * SP_PY + 1, SP_TX = 2 * SP_PX + 1; // stem pixels it needs: 15 x 25
+constexpr int SP_NPIX = SP_TY * SP_TX;                     // 375
+constexpr int SP_NBLK = (SP_NPIX + 31) / 32;               // 12 MFMA row blocks
+constexpr int SP_NB = SP_NBLK / 4;                         // per wave
+static_assert(SP_NBLK % 4 == 0, "the four waves share the row blocks evenly");
+constexpr int SP_PH = 2 * SP_TY + 5, SP_PW = 2 * SP_TX + 5, SP_PS = 56;   // input patch 35 x 55, row stride 56
 static_assert(SP_PW + 1 <= SP_PS, "the zero-weight 8th tap reads one column past the patch");
+static_assert(SP_PS % 4 == 0, "a patch row is filled in runs of 4 pixels");
+constexpr int SP_NGX = SP_PS / 4, SP_NG = SP_PH * SP_NGX;  // 4-pixel runs per patch row / per patch: 14, 490
+constexpr int SP_GPT = (SP_NG + 255) / 256;                // runs per thread
+constexpr int SP_OUT_PS = 144;                             // staged pixel stride (bytes)
+constexpr int SP_PATCH_B = 3 * SP_PH * SP_PS * 2, SP_STAGE_B = SP_NBLK * 32 * SP_OUT_PS;   // (padding rows staged too: no branch)
+static_assert(SP_PATCH_B % 16 == 0 && SP_STAGE_B % 16 == 0, "16-byte LDS vectors");
+constexpr int SP_LDS = SP_PATCH_B + SP_STAGE_B + 128 * 4;  // patch | staged tile | scale, bias: 67568 B, two blocks per CU
 
 __host__ __device__ constexpr int sp_group_off(int g) {
   const int gg = g < 21 ? g : 20;
   return (gg / 7) * (SP_PH * SP_PS) + (gg % 7) * SP_PS;
 }
 
-// HT: bf16_t or f16_t (IEEE half, round 6) = the type of the patch / weights in LDS and of the pooled output
-template <bool U8, typename HT = bf16_t>
-__global__ __launch_bounds__(256, 3) void stem_pool_kernel(const void* __restrict__ in_, const bf16_t* __restrict__ w,
-                                                        const float* __restrict__ scale, const float* __restrict__ bias,
-                                                        bf16_t* __restrict__ out, int N, int H, int W, int Ho, int Wo, int Hp,
-                                                        int Wp, float m0, float m1, float m2, int to_bgr) {
-  const float* __restrict__ in = reinterpret_cast<const float*>(in_);
-  const unsigned char* __restrict__ in8 = reinterpret_cast<const unsigned char*>(in_);
-  constexpr int PATCH_B = (3 * SP_PH * SP_PS * 2 + 15) / 16 * 16, OUT_PS = 144;
-  constexpr int LDS_B = SP_NBLK * 32 * OUT_PS > PATCH_B + 64 * SM_WS * 2 ? SP_NBLK * 32 * OUT_PS : PATCH_B + 64 * SM_WS * 2;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_B];
-  unsigned short* patch = reinterpret_cast<unsigned short*>(smem);
-  unsigned short* wl = reinterpret_cast<unsigned short*>(smem + PATCH_B);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.z;
-  const int py0 = blockIdx.y * SP_PY, px0 = blockIdx.x * SP_PX;
-  const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1;          // first stem pixel of the tile (may be -1: outside)
-  const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
-  constexpr int NPL = (3 * SP_PH * SP_PS + 255) / 256, NWL = (64 * (SM_K / 8) + 255) / 256;
-  float pv[NPL];
-  u32x4_t wv[NWL];      // (ext vector, not HIP's uint4 class: an array of those is placed in scratch memory)
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int e = tid + 256 * i;
-    const int c = e / (SP_PH * SP_PS);
-    const int rem = e - c * (SP_PH * SP_PS);
-    const int y = rem / SP_PS, x = rem - y * SP_PS;
-    const int iy = iy0 + y, ix = ix0 + x;
-    pv[i] = 0.f;
-    if (e < 3 * SP_PH * SP_PS && x < SP_PW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-      if (U8) {
-        const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2);
-        pv[i] = (float)in8[(((size_t)n * H + iy) * W + ix) * 3 + (to_bgr ? 2 - c : c)] - mean;
-      } else {
-        pv[i] = in[((size_t)(n * 3 + c) * H + iy) * W + ix];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NWL; ++i) {
-    const int e = tid + 256 * i;
-    const int row = e / (SM_K / 8), v = e - row * (SM_K / 8);
-    if (e < 64 * (SM_K / 8)) wv[i] = *reinterpret_cast<const u32x4_t*>(w + row * SM_K + v * 8);
-  }
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int e = tid + 256 * i;
-    if (e < 3 * SP_PH * SP_PS) patch[e] = Half16<HT>::cvt(pv[i]);
-  }
-#pragma unroll
-  for (int i = 0; i < NWL; ++i) {
-    const int e = tid + 256 * i;
-    const int row = e / (SM_K / 8), v = e - row * (SM_K / 8);
-    if (e < 64 * (SM_K / 8)) *reinterpret_cast<u32x4_t*>(&wl[row * SM_WS + v * 8]) = wv[i];
-  }
-  __syncthreads();
+typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 
-  const int p = lane & 31, half = lane >> 5;
-  // wave w owns MFMA row blocks w, w + 4, w + 8 (waves 0 and 1: three blocks, 2 and 3: two)
-  constexpr int NB = 3;
-  f32x16_t acc[NB][2];
-  int pbase[NB];                       // patch element offset of this lane's pixel (row * 33 + col -> stem (r, c) -> patch (2 r, 2 c))
+// the 12 bytes of pixels ix .. ix + 3 of frame row (n, iy) as three dwords (byte 3 k + s = source channel s of pixel ix + k)
+// and the mask of the pixels that lie in the frame; bytes of the others are 0 and are not fetched
+__device__ __forceinline__ void sp_load_run(const unsigned char* __restrict__ in8, int n, int iy, int ix, int H, int W, bool active,
+                                            u32x3_t& raw, unsigned& mask) {
+  raw = u32x3_t{0u, 0u, 0u};
+  mask = 0u;
+  if (active && (unsigned)iy < (unsigned)H) {
+    const unsigned char* row = in8 + ((size_t)n * H + iy) * (size_t)W * 3;
+    if (ix >= 0 && ix + 3 < W) {
+      __builtin_memcpy(&raw, row + (ptrdiff_t)ix * 3, 12);          // (one 12-byte load: global memory takes any byte alignment)
+      mask = 0xfu;
+    } else {
 #pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const int pix = min(32 * (wave + 4 * b) + p, SP_NPIX - 1);
-    const int r = pix / SP_TX, c = pix - r * SP_TX;
-    pbase[b] = 2 * r * SP_PS + 2 * c;
+      for (int k = 0; k < 4; ++k) {
+        if ((unsigned)(ix + k) < (unsigned)W) {
+          mask |= 1u << k;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[b][j][q] = 0.f;
-  }
-#pragma unroll
-  for (int ks = 0; ks < SM_K / 16; ++ks) {
-    u32x4_t bfr[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bfr[j] = *reinterpret_cast<const u32x4_t*>(&wl[(j * 32 + p) * SM_WS + ks * 16 + half * 8]);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (wave + 4 * b < SP_NBLK) {    // (wave-uniform)
-        const unsigned* base = reinterpret_cast<const unsigned*>(patch + pbase[b] + (half ? sp_group_off(2 * ks + 1) : sp_group_off(2 * ks)));
-        const u32x4_t a = {base[0], base[1], base[2], base[3]};
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[b][j] = Half16<HT>::mfma32(a, bfr[j], acc[b][j]);
-      }
-    }
-  }
-  __syncthreads();                     // every wave is done with the patch / weights
-  // ---- stem pixels -> LDS as bf16 [pixel][64 ch] (144-B stride); 0 outside the stem map
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int ch = j * 32 + p;
-    const float sc = scale[ch], bi = bias[ch];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (wave + 4 * b < SP_NBLK) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int pix = 32 * (wave + 4 * b) + (q & 3) + 8 * (q >> 2) + 4 * half;
-          const int r = pix / SP_TX, c = pix - r * SP_TX;
-          const int oy = oy0 + r, ox = ox0 + c;
-          const bool ok = pix < SP_NPIX && (unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo;
-          const unsigned short hv = (unsigned short)(Half16<HT>::cvt(fmaxf(acc[b][j][q] * sc + bi, 0.f)) & 0x7fffu);   // +0, never -0: the pool below orders bit patterns
-          *reinterpret_cast<unsigned short*>(smem + pix * OUT_PS + ch * 2) = ok ? hv : (unsigned short)0;
+          for (int s = 0; s < 3; ++s) {
+            const int q = 3 * k + s;
+            raw[q >> 2] |= (unsigned)row[(ptrdiff_t)(ix + k) * 3 + s] << (8 * (q & 3));
+          }
         }
       }
     }
   }
-  __syncthreads();
-  // ---- 3 x 3 / 2 max over the staged tile: pooled (y, x) of the tile = stem rows 2 y .. 2 y + 2, cols 2 x .. 2 x + 2 of the tile
+}
+
+// HT: bf16_t or f16_t (IEEE half, round 6) = the type of the patch / weights in LDS and of the pooled output
+template <bool U8, typename HT = bf16_t>
+__global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restrict__ in_, const bf16_t* __restrict__ w,
+                                                        const float* __restrict__ scale, const float* __restrict__ bias,
+                                                        bf16_t* __restrict__ out, int N, int H, int W, int Ho, int Wo, int Hp,
+                                                        int Wp, float m0, float m1, float m2, int to_bgr, int tiles_y,
+                                                        int tiles_x, int ntiles) {
+  const float* __restrict__ in = reinterpret_cast<const float*>(in_);
+  const unsigned char* __restrict__ in8 = reinterpret_cast<const unsigned char*>(in_);
+  extern __shared__ __attribute__((aligned(16))) unsigned char sp_smem[];
+  unsigned short* patch = reinterpret_cast<unsigned short*>(sp_smem);
+  unsigned char* stage = sp_smem + SP_PATCH_B;
+  float* sb = reinterpret_cast<float*>(sp_smem + SP_PATCH_B + SP_STAGE_B);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = lane & 31, half = lane >> 5;
+
+  // ---- once per block: this lane's weight fragments (channel 32 j + p, K 16 ks + 8 half ..), scale / bias to LDS
+  u32x4_t wf[2][SM_K / 16];
 #pragma unroll
-  for (int i = 0; i < SP_PY * SP_PX * 8 / 256; ++i) {
-    const int v = tid + 256 * i;
-    const int pl = v >> 3, cv = v & 7;
-    const int ty = pl / SP_PX, tx = pl - ty * SP_PX;
-    const int oy = py0 + ty, ox = px0 + tx;
-    typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
-    u16x8_t m = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
+    for (int ks = 0; ks < SM_K / 16; ++ks)
+      wf[j][ks] = *reinterpret_cast<const u32x4_t*>(w + (j * 32 + p) * SM_K + ks * 16 + half * 8);
+  if (tid < 64) {
+    sb[tid] = scale[tid];
+    sb[64 + tid] = bias[tid];
+  }
+  // wave w owns MFMA row blocks w, w + 4, w + 8; this lane's pixel of each: row * 25 + col -> stem (r, c) -> patch (2 r, 2 c)
+  int pbase[SP_NB], prc[SP_NB];
 #pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const u16x8_t q = *reinterpret_cast<const u16x8_t*>(smem + ((2 * ty + dy) * SP_TX + 2 * tx + dx) * OUT_PS + cv * 16);
-        m = __builtin_elementwise_max(m, q);      // (non-negative bf16 / f16 values order like their bit patterns)
+  for (int b = 0; b < SP_NB; ++b) {
+    const int pix = min(32 * (wave + 4 * b) + p, SP_NPIX - 1);
+    const int r = pix / SP_TX, c = pix - r * SP_TX;
+    pbase[b] = 2 * r * SP_PS + 2 * c;
+    prc[b] = (r << 16) | c;
+  }
+  // this thread's 4-pixel runs of the patch: row gy, pixels 4 gx .. 4 gx + 3; source channel s -> patch plane, mean
+  int gy[SP_GPT], gx4[SP_GPT];
+#pragma unroll
+  for (int i = 0; i < SP_GPT; ++i) {
+    const int g = tid + 256 * i;
+    gy[i] = g / SP_NGX;
+    gx4[i] = 4 * (g - gy[i] * SP_NGX);
+  }
+  const float ms[3] = {to_bgr ? m2 : m0, m1, to_bgr ? m0 : m2};
+  const int plane[3] = {to_bgr ? 2 * SP_PH * SP_PS : 0, SP_PH * SP_PS, to_bgr ? 0 : 2 * SP_PH * SP_PS};
+  const int tiles_per_image = tiles_y * tiles_x;
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int n = t / tiles_per_image, rem = t - n * tiles_per_image;
+    const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
+    const int py0 = ty * SP_PY, px0 = tx * SP_PX;
+    const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1;          // first stem pixel of the tile (may be -1: outside)
+    const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
+    // ---- patch -> LDS, planar [3][35][56] in HT, 0 outside the frame
+    if (U8) {
+      u32x3_t raw[SP_GPT];
+      unsigned mask[SP_GPT];
+#pragma unroll
+      for (int i = 0; i < SP_GPT; ++i)      // (all requested before the first one is used)
+        sp_load_run(in8, n, iy0 + gy[i], ix0 + gx4[i], H, W, tid + 256 * i < SP_NG, raw[i], mask[i]);
+#pragma unroll
+      for (int i = 0; i < SP_GPT; ++i) {
+        if (tid + 256 * i < SP_NG) {
+#pragma unroll
+          for (int s = 0; s < 3; ++s) {
+            float f[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int q = 3 * k + s;
+              const float v = (float)((raw[i][q >> 2] >> (8 * (q & 3))) & 0xffu) - ms[s];
+              f[k] = (mask[i] >> k) & 1u ? v : 0.f;
+            }
+            typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<u32x2_t*>(patch + plane[s] + gy[i] * SP_PS + gx4[i]) =
+                u32x2_t{Half16<HT>::pack2(f[0], f[1]), Half16<HT>::pack2(f[2], f[3])};
+          }
+        }
       }
-    if (oy < Hp && ox < Wp) *reinterpret_cast<u16x8_t*>(out + (((size_t)n * Hp + oy) * Wp + ox) * 64 + cv * 8) = m;
+    } else {
+      // (the scalar loader, eight elements in flight at a time: fully unrolled, the compiler keeps every element's
+      //  offsets live across the tile loop, next to the 88 weight registers, and spills)
+      constexpr int NE = 3 * SP_PH * SP_PS;
+#pragma unroll 1
+      for (int e0 = tid; e0 < NE; e0 += 256 * 8) {
+        float pv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int e = e0 + 256 * i;
+          const int c = e / (SP_PH * SP_PS);
+          const int r2 = e - c * (SP_PH * SP_PS);
+          const int y = r2 / SP_PS, x = r2 - y * SP_PS;
+          const int iy = iy0 + y, ix = ix0 + x;
+          pv[i] = 0.f;
+          if (e < NE && x < SP_PW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+            pv[i] = in[((size_t)(n * 3 + c) * H + iy) * W + ix];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int e = e0 + 256 * i;
+          if (e < NE) patch[e] = Half16<HT>::cvt(pv[i]);
+        }
+      }
+    }
+    __syncthreads();                     // patch (and, the first time, scale / bias) visible; every wave is done with the staged tile
+
+    // ---- one row block at a time (the weights are in registers, so nothing is re-read for it and only 32 accumulator
+    // registers are live): 22 MFMAs, then the block's stem pixels -> LDS as bf16 [pixel][64 ch] (144-B stride), 0 outside
+    // the stem map.  acc[j][4 g + i] is channel 32 j + 8 g + 4 half + i of the lane's pixel.  The 9 padding rows are staged
+    // like the others (nothing reads them): without a branch here the compiler overlaps a block's staging with the next
+    // block's MFMAs
+#pragma unroll
+    for (int b = 0; b < SP_NB; ++b) {
+      f32x16_t acc[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < SM_K / 16; ++ks) {
+        // K group 2 ks (lanes 0-31) or 2 ks + 1 (32-63): the lane's part is one of three values, the rest an immediate
+        const int dk = sp_group_off(2 * ks + 1) - sp_group_off(2 * ks);
+        const unsigned* base = reinterpret_cast<const unsigned*>(patch + (pbase[b] + (half ? dk : 0)) + sp_group_off(2 * ks));
+        const u32x4_t a = {base[0], base[1], base[2], base[3]};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[j] = Half16<HT>::mfma32(wf[j][ks], a, acc[j]);
+      }
+      const int pix = 32 * (wave + 4 * b) + p;
+      const int oy = oy0 + (prc[b] >> 16), ox = ox0 + (prc[b] & 0xffff);
+      const bool ok = (unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int ch0 = 32 * j + 8 * g + 4 * half;
+          const f32x4_t sc = *reinterpret_cast<const f32x4_t*>(sb + ch0), bi = *reinterpret_cast<const f32x4_t*>(sb + 64 + ch0);
+          float v[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc[j][4 * g + i] * sc[i] + bi[i], 0.f);
+          // (& 0x7fff: +0, never -0: the pool below orders bit patterns)
+          const unsigned lo = Half16<HT>::pack2(v[0], v[1]) & 0x7fff7fffu, hi = Half16<HT>::pack2(v[2], v[3]) & 0x7fff7fffu;
+          typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+          *reinterpret_cast<u32x2_t*>(stage + pix * SP_OUT_PS + ch0 * 2) = ok ? u32x2_t{lo, hi} : u32x2_t{0u, 0u};
+        }
+      }
+    }
+    __syncthreads();                     // the tile is staged; every wave is done with the patch
+    // ---- 3 x 3 / 2 max over the staged tile: pooled (y, x) of the tile = stem rows 2 y .. 2 y + 2, cols 2 x .. 2 x + 2 of the tile
+#pragma unroll
+    for (int i = 0; i < (SP_PY * SP_PX * 8 + 255) / 256; ++i) {
+      const int v = tid + 256 * i;
+      const int pl = v >> 3, cv = v & 7;
+      const int yy = pl / SP_PX, xx = pl - yy * SP_PX;
+      const int oy = py0 + yy, ox = px0 + xx;
+      if (v < SP_PY * SP_PX * 8) {
+        typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
+        u16x8_t m = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx) {
+            const u16x8_t q = *reinterpret_cast<const u16x8_t*>(stage + ((2 * yy + dy) * SP_TX + 2 * xx + dx) * SP_OUT_PS + cv * 16);
+            m = __builtin_elementwise_max(m, q);      // (non-negative bf16 / f16 values order like their bit patterns)
+          }
+        if (oy < Hp && ox < Wp) *reinterpret_cast<u16x8_t*>(out + (((size_t)n * Hp + oy) * Wp + ox) * 64 + cv * 8) = m;
+      }
+    }
   }
 }
 
@@ -1000,19 +1087,48 @@ extern "C" int mega_stem_pool_dt(const void* in, int u8, const void* w_n176, con
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
   const int Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-  dim3 grid(cdiv(Wp, SP_PX), cdiv(Hp, SP_PY), N);
+  const int tiles_y = cdiv(Hp, SP_PY), tiles_x = cdiv(Wp, SP_PX);
+  const long tiles = (long)N * tiles_y * tiles_x;
+  if (tiles > 0x7FFF0000L) return MEGA_ERR_ARG;                // (the kernel's tile index + grid stays an int)
+  if (u8 && (size_t)H * W * 3 > 0x7FFFFFFFu) return MEGA_ERR_ARG;
+  int cus = 256;
+  {
+    static int cached[64] = {0};       // per device id: a multi-GPU process may hold devices with different CU counts
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!cached[dev]) {
+      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cached[dev] = n;
+      else cached[dev] = 256;
+    }
+    cus = cached[dev];
+  }
+  const dim3 grid((unsigned)(tiles < 2L * cus ? tiles : 2L * cus));   // two resident blocks per CU, each walks the tiles
+  const int nt = (int)tiles;
   hipStream_t st = (hipStream_t)stream;
   const bf16_t* w = (const bf16_t*)w_n176;
   bf16_t* o = (bf16_t*)out;
   if (!u8) { mean0 = mean1 = mean2 = 0.f; to_bgr = 0; }
+#define MEGA_SP_LAUNCH(U8_, HT_)                                                                                           \
+  do {                                                                                                                     \
+    (void)hipFuncSetAttribute((const void*)stem_pool_kernel<U8_, HT_>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS); \
+    hipLaunchKernelGGL((stem_pool_kernel<U8_, HT_>), grid, dim3(256), SP_LDS, st, in, w, scale, bias, o, N, H, W, Ho, Wo,   \
+                       Hp, Wp, mean0, mean1, mean2, to_bgr, tiles_y, tiles_x, nt);                                         \
+  } while (0)
   if (dtype == MEGA_F16) {
-    if (u8) hipLaunchKernelGGL((stem_pool_kernel<true, f16_t>), grid, dim3(256), 0, st, in, w, scale, bias, o, N, H, W, Ho, Wo, Hp, Wp, mean0, mean1, mean2, to_bgr);
-    else hipLaunchKernelGGL((stem_pool_kernel<false, f16_t>), grid, dim3(256), 0, st, in, w, scale, bias, o, N, H, W, Ho, Wo, Hp, Wp, mean0, mean1, mean2, to_bgr);
+    if (u8) MEGA_SP_LAUNCH(true, f16_t);
+    else MEGA_SP_LAUNCH(false, f16_t);
   } else {
-    if (u8) hipLaunchKernelGGL((stem_pool_kernel<true, bf16_t>), grid, dim3(256), 0, st, in, w, scale, bias, o, N, H, W, Ho, Wo, Hp, Wp, mean0, mean1, mean2, to_bgr);
-    else hipLaunchKernelGGL((stem_pool_kernel<false, bf16_t>), grid, dim3(256), 0, st, in, w, scale, bias, o, N, H, W, Ho, Wo, Hp, Wp, mean0, mean1, mean2, to_bgr);
+    if (u8) MEGA_SP_LAUNCH(true, bf16_t);
+    else MEGA_SP_LAUNCH(false, bf16_t);
   }
+#undef MEGA_SP_LAUNCH
   return mega_check_launch();
+}
+
+// The pooled tile (rows, columns) one unit of mega_stem_pool_dt's work covers: what a test of its tile edges is built on.
+extern "C" void mega_stem_pool_tile(int* rows, int* cols) {
+  if (rows) *rows = SP_PY;
+  if (cols) *cols = SP_PX;
 }
 
 // mega_roi_align_fwd for f32 NHWC features with the result as split-precision planes: out bf16 [K][2 PH PW C] =

@@ -425,6 +425,13 @@ def stem_pool(x, w_n160, scale, bias, mean=None, to_bgr=True):
     return out
 
 
+def stem_pool_tile():
+    """(rows, columns) of the pooled tile that is one unit of stem_pool's work, as the kernel was compiled."""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.load().mega_stem_pool_tile(ctypes.byref(th), ctypes.byref(tw))
+    return th.value, tw.value
+
+
 def pack_stem_weight_bf16(w_oihw, dtype=torch.bfloat16):
     """conv1.weight [64,3,7,7] -> bf16 (or f16) [64,176]: column k = ((c*7+r)*8 + s for the 7 taps s of kernel row (c, r); the
     8th column of every group and columns 168..175 are zero (the kernel reads 8 consecutive patch pixels per group)."""
