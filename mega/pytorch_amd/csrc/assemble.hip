@@ -12,7 +12,7 @@
 // 2-byte aligned) are the same thing.  All segments of a call go out in ONE launch of copy_any_kernel (16-byte units at
 // whatever alignment a segment has; since the end of round 4 -- the form before it, one launch per copy width 16 / 8 / 4 /
 // 2 bytes, is gone).  Pure data movement, bit-exact by construction.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -134,9 +134,7 @@ extern "C" int mega_split_f32_to_bf16x3(const float* src, void* dst, int rows, i
   if (!src || !dst || rows < 0 || K <= 0 || K % 8 || (reinterpret_cast<size_t>(src) & 15) || (reinterpret_cast<size_t>(dst) & 15))
     return MEGA_ERR_ARG;
   const size_t total = (size_t)rows * (K / 8);
-  size_t nb = (total + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(split3_f32_bf16_kernel<3>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, rows, K / 8);
+  hipLaunchKernelGGL(split3_f32_bf16_kernel<3>, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, rows, K / 8);
   return mega_check_launch();
 }
 
@@ -149,13 +147,12 @@ extern "C" int mega_split_f32_to_planes_dt(const float* src, void* dst, int rows
   if (!src || !dst || rows < 0 || K <= 0 || K % 8 || (reinterpret_cast<size_t>(src) & 15) || (reinterpret_cast<size_t>(dst) & 15))
     return MEGA_ERR_ARG;
   const size_t total = (size_t)rows * (K / 8);
-  size_t nb = (total + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  if (dtype == MEGA_F16)
-    hipLaunchKernelGGL((split3_f32_bf16_kernel<2, f16_t>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, rows, K / 8);
-  else
-    hipLaunchKernelGGL((split3_f32_bf16_kernel<2, bf16_t>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, rows, K / 8);
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    using HT = decltype(tag);
+    hipLaunchKernelGGL((split3_f32_bf16_kernel<2, HT>), dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, src,
+                       (bf16_t*)dst, rows, K / 8);
+    return mega_check_launch();
+  });
 }
 
 // dst[i] = bf16(src[i]) for n contiguous elements (both 16-byte aligned).  The aggregation head keeps its activation
@@ -167,14 +164,13 @@ extern "C" int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int 
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (!src || !dst || (reinterpret_cast<size_t>(src) & 15) || (reinterpret_cast<size_t>(dst) & 15)) return MEGA_ERR_ARG;
   const size_t n8 = n / 8;
-  size_t nb = (n8 + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  if (dtype == MEGA_F16)
-    hipLaunchKernelGGL(cast_f32_bf16_kernel<f16_t>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n8, n);
-  else
-    hipLaunchKernelGGL(cast_f32_bf16_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n8, n);
-  return mega_check_launch();
+  const unsigned nb = grid1d(n8, 4096);
+  return dispatch_half(dtype, [&](auto tag) {
+    using HT = decltype(tag);
+    hipLaunchKernelGGL(cast_f32_bf16_kernel<HT>, dim3(nb < 1 ? 1 : nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst,
+                       n8, n);                                 // (n < 8: the tail alone still needs its block)
+    return mega_check_launch();
+  });
 }
 
 struct MegaCopySegC {
@@ -198,16 +194,15 @@ extern "C" int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, vo
     }
   }
   hipStream_t st = (hipStream_t)stream;
+  const auto kernel = dtype == MEGA_F16 ? copy_cast_segments_kernel<f16_t> : copy_cast_segments_kernel<bf16_t>;
   CopyBatch b;
   b.n = 0;
   unsigned long long units = 0;
   auto flush = [&]() {
     if (b.n == 0) return;
     b.ubase[b.n] = (unsigned)units;
-    unsigned long long nb = (units + 1023) / 1024;
-    if (nb > 2048) nb = 2048;
-    if (dtype == MEGA_F16) hipLaunchKernelGGL(copy_cast_segments_kernel<f16_t>, dim3((unsigned)(nb < 1 ? 1 : nb)), dim3(256), 0, st, b);
-    else hipLaunchKernelGGL(copy_cast_segments_kernel<bf16_t>, dim3((unsigned)(nb < 1 ? 1 : nb)), dim3(256), 0, st, b);
+    const unsigned nb = grid1d((units + 3) / 4, 2048);       // ~4 units per thread
+    hipLaunchKernelGGL(kernel, dim3(nb < 1 ? 1 : nb), dim3(256), 0, st, b);
     b.n = 0;
     units = 0;
   };
@@ -248,9 +243,8 @@ extern "C" int mega_copy_segments(const void* segs, int n, void* stream) {
   auto flush = [&]() {
     if (b.n == 0) return;
     b.ubase[b.n] = (unsigned)units;
-    unsigned long long nb = (units + 1023) / 1024;        // ~4 units per thread
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(copy_any_kernel, dim3((unsigned)(nb < 1 ? 1 : nb)), dim3(256), 0, st, b);
+    const unsigned nb = grid1d((units + 3) / 4, 2048);       // ~4 units per thread
+    hipLaunchKernelGGL(copy_any_kernel, dim3(nb < 1 ? 1 : nb), dim3(256), 0, st, b);
     b.n = 0;
     units = 0;
   };

@@ -12,6 +12,7 @@
 // and view 0 this is mega_postprocess's P2-P4 on the same candidates: the same bits.
 // Compiled with -ffp-contract=off: the flip / resize products and differences round like the reference's torch ops.
 #include "aug_views.h"
+#include "launch.h"
 
 namespace {
 
@@ -97,14 +98,11 @@ int mega_bbox_aug_load_nms(const float* cboxes, const float* cscores, int F, int
   const int C1 = NC - 1, P = F * C1, KR = K * R;
   int ns = 64;
   while (ns < KR) ns <<= 1;
-  (void)hipFuncSetAttribute((const void*)aug_load_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kMaxRows * (int)sizeof(u64));
-  hipLaunchKernelGGL(aug_load_sort_kernel, dim3(P), dim3(1024), (size_t)ns * sizeof(u64), st, (const float4*)cboxes,
-                     cscores, K, F, C1, R, score_thresh, v, w.mboxes, w.mscores, w.flags, w.sboxes, w.order, w.counts);
-  int rc = mega_check_launch();
+  const int rc = launch_lds(aug_load_sort_kernel, dim3(P), dim3(1024), (size_t)ns * sizeof(u64), st, (const float4*)cboxes,
+                            cscores, K, F, C1, R, score_thresh, v, w.mboxes, w.mscores, w.flags, w.sboxes, w.order, w.counts);
   if (rc != MEGA_OK) return rc;
-  return mega_boxes_nms_lazy((const float*)w.sboxes, w.counts, w.order, P, KR, nms_thresh, strict_gt, KR, w.keep_pos,
-                             w.keep_cnt, w.flags, st);
+  return mega_boxes_nms_lazy((const float*)w.sboxes, w.counts, nullptr, w.order, P, KR, nms_thresh, strict_gt, KR,
+                             w.keep_pos, w.keep_cnt, w.flags, st);
 }
 
 // cboxes [K][F][NC-1][R][4], cscores [K][F][NC-1][R]; view_w / view_h [K] (host) the views' image sizes, view_flip [K]

@@ -25,7 +25,7 @@
 // test_fused_bottleneck64_bit_equal_to_unfused).
 #include <cstdlib>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -601,26 +601,11 @@ extern "C" int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const flo
   const long tiles = (long)N * p.tiles_y * p.tiles_x;
   if (tiles > 0x7FFFFFFF) return MEGA_ERR_ARG;
   p.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cached[64] = {0};
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cached[dev]) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cached[dev] = n;
-      else cached[dev] = 256;
-    }
-    cus = cached[dev];
-  }
+  const int cus = mega_cu_count();
   const int grid = (int)(tiles < cus ? tiles : cus);
-  if (dtype == MEGA_F16) {
-    (void)hipFuncSetAttribute((const void*)bneck64_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, BK_LDS);
-    hipLaunchKernelGGL(bneck64_kernel<f16_t>, dim3(grid), dim3(BK_NT), BK_LDS, (hipStream_t)stream, p);
-  } else {
-    (void)hipFuncSetAttribute((const void*)bneck64_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, BK_LDS);
-    hipLaunchKernelGGL(bneck64_kernel<bf16_t>, dim3(grid), dim3(BK_NT), BK_LDS, (hipStream_t)stream, p);
-  }
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    return launch_lds(bneck64_kernel<decltype(tag)>, dim3(grid), dim3(BK_NT), BK_LDS, (hipStream_t)stream, p);
+  });
 }
 
 // The stage's first block with the 1x1 downsample branch: x NHWC bf16 [N][H][W][64] -> out [N][H][W][256],
@@ -644,25 +629,10 @@ extern "C" int mega_bottleneck64_ds_fwd_dt(const void* x, const void* w1, const 
   const long tiles = (long)N * p.tiles_y * p.tiles_x;
   if (tiles > 0x7FFFFFFF) return MEGA_ERR_ARG;
   p.ntiles = (int)tiles;
-  int cus = 256;
-  {
-    static int cached[64] = {0};
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cached[dev]) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cached[dev] = n;
-      else cached[dev] = 256;
-    }
-    cus = cached[dev];
-  }
+  const int cus = mega_cu_count();
   const int grid = (int)(tiles < cus ? tiles : cus);
-  if (dtype == MEGA_F16) {
-    (void)hipFuncSetAttribute((const void*)bneck64_ds_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, BD_LDS);
-    hipLaunchKernelGGL(bneck64_ds_kernel<f16_t>, dim3(grid), dim3(BK_NT), BD_LDS, (hipStream_t)stream, p);
-  } else {
-    (void)hipFuncSetAttribute((const void*)bneck64_ds_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, BD_LDS);
-    hipLaunchKernelGGL(bneck64_ds_kernel<bf16_t>, dim3(grid), dim3(BK_NT), BD_LDS, (hipStream_t)stream, p);
-  }
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    return launch_lds(bneck64_ds_kernel<decltype(tag)>, dim3(grid), dim3(BK_NT), BD_LDS, (hipStream_t)stream, p);
+  });
 }
 

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "aug_views.h"
+#include "launch.h"
 
 namespace {
 
@@ -97,7 +98,8 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__
 // One wavefront per problem: the 64-bit suppression words of nms.cu map 1:1 onto wave64 lanes/ballots.
 // keep_pos[P][max_keep] : kept positions (in score-sorted order), ascending = score-descending
 // flags[P][nmax]        : optional, flags[order[pos]] = 1 for kept boxes (order may be null -> identity)
-constexpr int SCAN_MAXCB = 128;  // up to 8192 boxes per problem
+constexpr int SCAN_MAXCB = 32;   // up to 2048 boxes per problem: mega_nms_sorted sends longer lists to the lazy form
+static_assert(SCAN_MAXCB <= 64, "nms_scan_kernel keeps one removal word per lane");
 
 __global__ __launch_bounds__(64) void nms_scan_kernel(const u64* __restrict__ mask, const int* __restrict__ counts,
                                                       const unsigned char* __restrict__ valid,
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const u64* __restrict__ ma
   const int n = min(counts[p], nmax);
   const int ncb = (n + 63) >> 6;
   const u64* mk = mask + (size_t)p * nmax * cbmax;
-  u64 remv0 = 0, remv1 = 0;  // lane l holds removal words l and l+64
+  u64 remv = 0;  // lane l holds removal word l
   int nkeep = 0;
   for (int blk = 0; blk < ncb && nkeep < max_keep; ++blk) {
     const int i = blk * 64 + lane;
@@ -118,11 +120,9 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const u64* __restrict__ ma
     u64 diag = 0;
     if (i < n) diag = mk[(size_t)i * cbmax + blk];
     const unsigned dlo = (unsigned)diag, dhi = (unsigned)(diag >> 32);
-    const u64 mine = blk < 64 ? remv0 : remv1;
-    const int src = blk & 63;
     // NB: the builtin returns a signed int -- go through unsigned or bit 31 sign-extends into the high word
-    u64 cur = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mine >> 32), src) << 32) |
-              (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)mine, src);
+    u64 cur = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(remv >> 32), blk) << 32) |
+              (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)remv, blk);
     cur |= ~okmask;
     u64 kept = 0;
     for (int t = 0; t < 64; ++t) {
@@ -144,28 +144,27 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const u64* __restrict__ ma
     if (nkeep >= max_keep) break;
     // OR the rows of the kept boxes into the removal words of later column blocks
     u64 k2 = kept;
-    const bool w0 = lane > blk && lane < ncb;
-    const bool w1 = (lane + 64) > blk && (lane + 64) < ncb;
+    const bool later = lane > blk && lane < ncb;
     while (k2) {
-      u64 acc0[4] = {0, 0, 0, 0}, acc1[4] = {0, 0, 0, 0};
+      u64 acc[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (k2) {
           const int t = __ffsll((long long)k2) - 1;
           k2 &= k2 - 1;
           const u64* row = mk + (size_t)(blk * 64 + t) * cbmax;
-          if (w0) acc0[u] = row[lane];
-          if (w1) acc1[u] = row[lane + 64];
+          if (later) acc[u] = row[lane];
         }
       }
-      remv0 |= acc0[0] | acc0[1] | acc0[2] | acc0[3];
-      remv1 |= acc1[0] | acc1[1] | acc1[2] | acc1[3];
+      remv |= acc[0] | acc[1] | acc[2] | acc[3];
     }
   }
   if (lane == 0) keep_cnt[p] = nkeep < max_keep ? nkeep : max_keep;
 }
 
 // ---------------------------------------------------------------------------------------------- NMS, lazy form
+constexpr int LAZY_MAXN = 8192;  // boxes per problem (all of them in LDS); what the NMS entry points accept
+
 // The mask form above evaluates all n^2/2 pairs although greedy NMS only ever needs the rows of the KEPT boxes, and
 // the RPN stops after post_nms_top_n (300) of its 6000 candidates.  One 1024-thread block per problem keeps the
 // score-sorted boxes in LDS (16 B x 8192 max) and walks them in windows of 1024 boxes (one box per thread, in
@@ -802,7 +801,7 @@ extern "C" int mega_nms_sorted(const float* boxes, const int* counts, const unsi
   mega_clear_error();
   if (P == 0 || nmax == 0) return MEGA_OK;
   if (!boxes || !counts || !keep_pos || !keep_cnt || !ws || P < 0 || nmax < 0 || max_keep <= 0) return MEGA_ERR_ARG;
-  if (nmax > SCAN_MAXCB * 64) return MEGA_ERR_ARG;
+  if (nmax > LAZY_MAXN) return MEGA_ERR_ARG;
   if (ws_bytes < mega_nms_workspace_bytes(P, nmax)) return MEGA_ERR_WS;
   hipStream_t st = (hipStream_t)stream;
   const int cb = cdiv(nmax, 64);
@@ -811,14 +810,8 @@ extern "C" int mega_nms_sorted(const float* boxes, const int* counts, const unsi
   // max_keep -- it pays when few boxes are kept out of many (the RPN: 300 of 6000) or the list is long; many small
   // problems that keep everything (post-processing with R = 1024: 30 classes x B images, max_keep = R) are better
   // served by the mask + scan pair, whose work is spread over nmax^2 / 4096 blocks per problem.
-  if (nmax >= kNmsLazyMin && (4 * max_keep <= nmax || nmax > 2048)) {
-    const size_t lds = (((size_t)nmax * 17 + 15) & ~(size_t)15) + (size_t)nmax * 2 + 16;
-    if (hipFuncSetAttribute((const void*)nms_lazy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return MEGA_ERR_LAUNCH;
-    hipLaunchKernelGGL(nms_lazy_kernel, dim3(P), dim3(1024), lds, st, (const float4*)boxes, counts, valid, order, nmax,
-                       thr, strict_gt, max_keep, keep_pos, keep_cnt, flags);
-    return mega_check_launch();
-  }
+  if (nmax >= kNmsLazyMin && (4 * max_keep <= nmax || nmax > SCAN_MAXCB * 64))
+    return mega_boxes_nms_lazy(boxes, counts, valid, order, P, nmax, thr, strict_gt, max_keep, keep_pos, keep_cnt, flags, st);
   WsCarver c(ws);
   u64* mask = nms_carve(c, P, nmax);
   hipLaunchKernelGGL(nms_mask_kernel, dim3(cb, cb, P), dim3(64), 0, st, (const float4*)boxes, counts, mask, nmax, cb,
@@ -882,12 +875,10 @@ extern "C" int mega_rpn_select_idx(const float* rpn_out, const float* cell_ancho
   p.kmax = k; p.im_w = im_w; p.im_h = im_h; p.min_size = min_size; p.clip = logf(1000.f / 16.f);
   int ns = 64;
   while (ns < k) ns <<= 1;
-  // set on every call: a per-process flag would miss the second device of a multi-GPU process
-  (void)hipFuncSetAttribute((const void*)rpn_topk_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            SORT_MAX * (int)sizeof(u64));
-  hipLaunchKernelGGL(rpn_topk_decode_kernel, dim3(B), dim3(1024), (size_t)ns * sizeof(u64), st, p);
-  int rc = mega_nms_sorted((const float*)w.sboxes, w.counts, w.valid, nullptr, B, k, nms_thresh, strict_gt,
-                           post_nms_top_n, w.keep_pos, prop_cnt, nullptr, w.mask, mega_nms_workspace_bytes(B, k), stream);
+  int rc = launch_lds(rpn_topk_decode_kernel, dim3(B), dim3(1024), (size_t)ns * sizeof(u64), st, p);
+  if (rc != MEGA_OK) return rc;
+  rc = mega_nms_sorted((const float*)w.sboxes, w.counts, w.valid, nullptr, B, k, nms_thresh, strict_gt, post_nms_top_n,
+                       w.keep_pos, prop_cnt, nullptr, w.mask, mega_nms_workspace_bytes(B, k), stream);
   if (rc != MEGA_OK) return rc;
   // keep_pos rows are post_nms_top_n wide
   hipLaunchKernelGGL(gather_kept_kernel, dim3(B), dim3(256), 0, st, w.sboxes, w.sscores, w.keep_pos, prop_cnt, k,
@@ -953,15 +944,13 @@ extern "C" int mega_postprocess_candidates_batched(const float* logits, const fl
 }
 
 // Library-internal (common.h): the lazy NMS and P4 of the post-processor, for the box-augmentation merge (bbox_aug.hip).
-int mega_boxes_nms_lazy(const float* boxes, const int* counts, const int* order, int P, int nmax, float thr, int strict_gt,
-                        int max_keep, int* keep_pos, int* keep_cnt, unsigned char* flags, hipStream_t st) {
-  if (nmax > SCAN_MAXCB * 64) return MEGA_ERR_ARG;
-  const size_t lds = (((size_t)nmax * 17 + 15) & ~(size_t)15) + (size_t)nmax * 2 + 16;
-  if (hipFuncSetAttribute((const void*)nms_lazy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return MEGA_ERR_LAUNCH;
-  hipLaunchKernelGGL(nms_lazy_kernel, dim3(P), dim3(1024), lds, st, (const float4*)boxes, counts,
-                     (const unsigned char*)nullptr, order, nmax, thr, strict_gt, max_keep, keep_pos, keep_cnt, flags);
-  return mega_check_launch();
+int mega_boxes_nms_lazy(const float* boxes, const int* counts, const unsigned char* valid, const int* order, int P, int nmax,
+                        float thr, int strict_gt, int max_keep, int* keep_pos, int* keep_cnt, unsigned char* flags,
+                        hipStream_t st) {
+  if (nmax > LAZY_MAXN) return MEGA_ERR_ARG;
+  const size_t lds = (((size_t)nmax * 17 + 15) & ~(size_t)15) + (size_t)nmax * 2 + 16;   // boxes, removed bytes, kept list
+  return launch_lds(nms_lazy_kernel, dim3(P), dim3(1024), lds, st, (const float4*)boxes, counts, valid, order, nmax, thr,
+                    strict_gt, max_keep, keep_pos, keep_cnt, flags);
 }
 
 int mega_boxes_post_finalize(const unsigned char* flags, const float* cboxes, const float* cscores, int B, int NCm1, int R,

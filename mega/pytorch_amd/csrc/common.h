@@ -148,10 +148,12 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Library-internal launchers of boxes.hip, shared with bbox_aug.hip and soft_nms.hip (not part of the C ABI):
 //   mega_boxes_nms_lazy      greedy NMS over P score-sorted problems, always in the lazy one-block-per-problem form
-//                            (nmax <= 8192; no workspace); flags[p][order[p][pos]] = 1 for the kept boxes
+//                            (nmax <= 8192; no workspace; valid [P][nmax] u8 or null); flags[p][order[p][pos]] = 1 for
+//                            the kept boxes
 //   mega_boxes_post_finalize the post-processor's class-major compaction + detections-per-image cut of B images
-int mega_boxes_nms_lazy(const float* boxes, const int* counts, const int* order, int P, int nmax, float thr, int strict_gt,
-                        int max_keep, int* keep_pos, int* keep_cnt, unsigned char* flags, hipStream_t st);
+int mega_boxes_nms_lazy(const float* boxes, const int* counts, const unsigned char* valid, const int* order, int P, int nmax,
+                        float thr, int strict_gt, int max_keep, int* keep_pos, int* keep_cnt, unsigned char* flags,
+                        hipStream_t st);
 int mega_boxes_post_finalize(const unsigned char* flags, const float* cboxes, const float* cscores, int B, int NCm1, int R,
                              int max_det, float* out_boxes, float* out_scores, long long* out_labels, int* out_cnt,
                              int* tmp_idx, hipStream_t st);

@@ -21,7 +21,7 @@
 // HBM per tile: 41.5 KB in (27 % halo) + 32 KB out against 147 k MFMA cycles per CU-tile: HBM-bound by design.
 #include <cstdlib>
 
-#include "common.h"
+#include "launch.h"
 #include "igemm_params.h"
 
 namespace {
@@ -188,24 +188,9 @@ int mega_conv64_launch(const ConvParams& p, int half_dtype, hipStream_t st) {
   const int ty = cdiv(p.H, C64_T), tx = cdiv(p.W, C64_T);
   const long tiles = (long)p.N * ty * tx;
   if (tiles > 0x7FFFFFFF) return MEGA_ERR_ARG;
-  int cus = 256;
-  {
-    static int cached[64] = {0};       // per device id: a multi-GPU process may hold devices with different CU counts
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cached[dev]) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cached[dev] = n;
-      else cached[dev] = 256;
-    }
-    cus = cached[dev];
-  }
+  const int cus = mega_cu_count();
   const int grid = (int)(tiles < cus ? tiles : cus);
-  if (half_dtype == MEGA_F16) {
-    (void)hipFuncSetAttribute((const void*)conv3x3_c64_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
-    hipLaunchKernelGGL(conv3x3_c64_kernel<f16_t>, dim3(grid), dim3(C64_NT), C64_LDS, st, p, ty, tx, (int)tiles);
-  } else {
-    (void)hipFuncSetAttribute((const void*)conv3x3_c64_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
-    hipLaunchKernelGGL(conv3x3_c64_kernel<bf16_t>, dim3(grid), dim3(C64_NT), C64_LDS, st, p, ty, tx, (int)tiles);
-  }
-  return mega_check_launch();
+  return dispatch_half(half_dtype, [&](auto tag) {
+    return launch_lds(conv3x3_c64_kernel<decltype(tag)>, dim3(grid), dim3(C64_NT), C64_LDS, st, p, ty, tx, (int)tiles);
+  });
 }

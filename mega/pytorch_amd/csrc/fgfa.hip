@@ -11,7 +11,7 @@
 // One workgroup per output pixel; a wave reads 64 consecutive 16-byte channel vectors of one neighbour pixel
 // (1 KiB, fully coalesced).  Two passes over the T frames: the cosine weights from the embedding channels first, then the
 // weighted sum of the feature channels in registers; LDS holds the key frame's embedding and the frame groups' partial sums.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -324,17 +324,16 @@ extern "C" int mega_dff_warp_scale(const void* feats, const float* flow, const v
   const int ve = dtype == MEGA_BF16 ? 8 : 4;
   if (C % ve) return MEGA_ERR_ARG;
   const size_t total = (size_t)H * W * (C / ve);
-  const dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((dff_warp_scale_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)feats, flow,
-                       (const bf16_t*)scale, (bf16_t*)out, H, W, C);
-  else if (dtype == MEGA_F32)
-    hipLaunchKernelGGL((dff_warp_scale_kernel<float>), grid, dim3(256), 0, st, (const float*)feats, flow,
-                       (const float*)scale, (float*)out, H, W, C);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  auto go = [&](auto tag) {                                    // (no f16 form of this kernel)
+    using T = decltype(tag);
+    hipLaunchKernelGGL((dff_warp_scale_kernel<T>), dim3(grid1d(total, 16384)), dim3(256), 0, st, (const T*)feats, flow,
+                       (const T*)scale, (T*)out, H, W, C);
+    return mega_check_launch();
+  };
+  if (dtype == MEGA_BF16) return go(bf16_t{});
+  if (dtype == MEGA_F32) return go(float{});
+  return MEGA_ERR_ARG;
 }
 
 // The four entry points below share this.  fgfa2_kernel gives each frame group Cf / ve of its 256 threads (so 256 must be a
@@ -352,13 +351,13 @@ static int fgfa_impl(const void* feats, const float* flow, void* out, float* wei
   if (fvec > 256 || 256 % fvec != 0 || (size_t)H * W * (Cf + Ce) >= 0x7FFFFFFFull) return MEGA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const size_t smem = ((size_t)Ce + (size_t)(256 / fvec - 1) * Cf) * sizeof(float);
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((fgfa2_kernel<bf16_t>), dim3(H * W, G), dim3(256), smem, st, (const bf16_t*)feats, flow,
-                       (bf16_t*)out, weights_out, T, H, W, Cf, Ce, key, order, flow_key_pos);
-  else
-    hipLaunchKernelGGL((fgfa2_kernel<float>), dim3(H * W, G), dim3(256), smem, st, (const float*)feats, flow,
-                       (float*)out, weights_out, T, H, W, Cf, Ce, key, order, flow_key_pos);
-  return mega_check_launch();
+  auto go = [&](auto tag) {
+    using E = decltype(tag);
+    hipLaunchKernelGGL((fgfa2_kernel<E>), dim3(H * W, G), dim3(256), smem, st, (const E*)feats, flow, (E*)out, weights_out,
+                       T, H, W, Cf, Ce, key, order, flow_key_pos);
+    return mega_check_launch();
+  };
+  return dtype == MEGA_BF16 ? go(bf16_t{}) : go(float{});
 }
 
 extern "C" int mega_fgfa_warp_aggregate(const void* feats, const float* flow, void* out, float* weights_out, int T,
@@ -405,13 +404,12 @@ extern "C" int mega_fgfa_pair_taps(const float* ring, long long ring_stride, con
   if (Hp + 6 > 65535 || (reinterpret_cast<size_t>(out) & 15)) return MEGA_ERR_ARG;
   const dim3 grid((unsigned)((Wp + 249) / 250), (unsigned)(Hp + 6), (unsigned)T);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((pair_taps_kernel<bf16_t>), grid, dim3(256), 0, st, ring, ring_stride, cur, cur_stride, order, (bf16_t*)out, H, W, Hp, Wp);
-  else if (dtype == MEGA_F16)
-    hipLaunchKernelGGL((pair_taps_kernel<f16_t>), grid, dim3(256), 0, st, ring, ring_stride, cur, cur_stride, order, (f16_t*)out, H, W, Hp, Wp);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    using HT = decltype(tag);
+    hipLaunchKernelGGL((pair_taps_kernel<HT>), grid, dim3(256), 0, st, ring, ring_stride, cur, cur_stride, order, (HT*)out, H,
+                       W, Hp, Wp);
+    return mega_check_launch();
+  });
 }
 
 // ---- FlowNetS refinement level (flownet.py:94-111): concatN = cat([skip, crop(leaky(deconvN(x))), crop(upsample_flowN(flow))], 1)
@@ -482,18 +480,13 @@ extern "C" int mega_flow_level_assemble(const void* skip, const void* flow, cons
     return MEGA_ERR_ARG;
   if ((reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(skip) & 15)) return MEGA_ERR_ARG;
   const long long total = (long long)N * H2 * W2 * ((Cs + (ldo - Cs - C)) / ve);
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((flow_level_assemble_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)skip, (const bf16_t*)flow,
-                       w_up, b_up, (bf16_t*)out, N, H2, W2, Cs, C, ldo, h, w, crop);
-  else if (dtype == MEGA_F16)
-    hipLaunchKernelGGL((flow_level_assemble_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, (const f16_t*)skip, (const f16_t*)flow,
-                       w_up, b_up, (f16_t*)out, N, H2, W2, Cs, C, ldo, h, w, crop);
-  else
-    hipLaunchKernelGGL((flow_level_assemble_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)skip, (const float*)flow,
-                       w_up, b_up, (float*)out, N, H2, W2, Cs, C, ldo, h, w, crop);
-  return mega_check_launch();
+  return dispatch_elem(dtype, [&](auto tag) {
+    using E = decltype(tag);
+    hipLaunchKernelGGL((flow_level_assemble_kernel<E>), dim3(grid1d(total, 16384)), dim3(256), 0, st, (const E*)skip,
+                       (const E*)flow, w_up, b_up, (E*)out, N, H2, W2, Cs, C, ldo, h, w, crop);
+    return mega_check_launch();
+  });
 }
 
 // ---- FlowNetS flow prediction (flownet.py:40-52 Convolution1..5: nn.Conv2d(Cin, 2, 3, padding=1)), second half.  A 3 x 3 conv
@@ -532,13 +525,13 @@ extern "C" int mega_flow_pred_finish(const float* z, int ldz, const float* bias,
   mega_clear_error();
   if (!z || !bias || !out || N <= 0 || H <= 0 || W <= 0 || ldz < 18 || (ldz & 1) || (reinterpret_cast<size_t>(z) & 7)) return MEGA_ERR_ARG;
   const long long total = (long long)N * H * W;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == MEGA_F32) hipLaunchKernelGGL((flow_pred_finish_kernel<float>), dim3(blocks), dim3(256), 0, st, z, ldz, bias, scale, (float*)out, N, H, W);
-  else if (out_dtype == MEGA_BF16) hipLaunchKernelGGL((flow_pred_finish_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, z, ldz, bias, scale, (bf16_t*)out, N, H, W);
-  else if (out_dtype == MEGA_F16) hipLaunchKernelGGL((flow_pred_finish_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, z, ldz, bias, scale, (f16_t*)out, N, H, W);
-  else return MEGA_ERR_ARG;
-  return mega_check_launch();
+  return dispatch_elem(out_dtype, [&](auto tag) {
+    using OT = decltype(tag);
+    hipLaunchKernelGGL((flow_pred_finish_kernel<OT>), dim3(grid1d(total, 16384)), dim3(256), 0, st, z, ldz, bias, scale,
+                       (OT*)out, N, H, W);
+    return mega_check_launch();
+  });
 }
 
 // ---- FlowNetS flow_conv1 per FRAME instead of per pair (round 6).  flow_conv1 (flownet.py:52,:56: Conv2d(6, 64, 7, stride 2) +
@@ -599,13 +592,11 @@ extern "C" int mega_flow_conv1_combine(const float* ab, const float* bias, const
       (reinterpret_cast<size_t>(out) & 15) || nwin < 0 || (nwin > 0 && (!order || T % nwin != 0)))
     return MEGA_ERR_ARG;
   const long long total = (long long)T * P * 8;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((flow_conv1_combine_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, ab, bias, order, key, (unsigned short*)out, T, P, nwin);
-  else if (dtype == MEGA_F16)
-    hipLaunchKernelGGL((flow_conv1_combine_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, ab, bias, order, key, (unsigned short*)out, T, P, nwin);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    using HT = decltype(tag);
+    hipLaunchKernelGGL((flow_conv1_combine_kernel<HT>), dim3(grid1d(total, 32768)), dim3(256), 0, st, ab, bias, order, key,
+                       (unsigned short*)out, T, P, nwin);
+    return mega_check_launch();
+  });
 }

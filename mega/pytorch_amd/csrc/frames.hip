@@ -2,7 +2,7 @@
 // transform chain of the reference for a frame whose size is already a fixed point of the resize rule
 // (600x1000): ToTensor (/255), to_bgr255 (channel flip, *255), Normalize(mean, std = 1)
 // (mega_core/data/transforms/transforms.py:83-129, data/transforms/build.py:26-45).
-#include "common.h"
+#include "launch.h"
 
 namespace {
 __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
@@ -114,8 +114,7 @@ extern "C" int mega_preprocess_frames(const unsigned char* in, float* out, int N
   mega_clear_error();
   if (!in || !out || N <= 0 || H <= 0 || W <= 0) return MEGA_ERR_ARG;
   const size_t total = (size_t)N * H * W;
-  const int blocks = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-  hipLaunchKernelGGL(preprocess_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, out, N, H, W, mean0,
+  hipLaunchKernelGGL(preprocess_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream, in, out, N, H, W, mean0,
                      mean1, mean2, to_bgr);
   return mega_check_launch();
 }
@@ -129,7 +128,7 @@ extern "C" int mega_resize_bilinear_u8(const unsigned char* in, unsigned char* o
   if ((need_h && (!bounds_h || !coef_h || ksize_h <= 0)) || (need_v && (!bounds_v || !coef_v || ksize_v <= 0)) ||
       (need_h && need_v && !tmp))
     return MEGA_ERR_ARG;
-  auto grid = [](size_t total) { return dim3((unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256)); };
+  auto grid = [](size_t total) { return dim3(grid1d(total, 32768)); };
   hipStream_t st = (hipStream_t)stream;
   if (!need_h && !need_v) {
     hipError_t e = hipMemcpyAsync(out, in, (size_t)N * Hi * Wi * 3, hipMemcpyDeviceToDevice, st);
@@ -163,7 +162,7 @@ extern "C" int mega_resize_bilinear_u8_flip(const unsigned char* in, unsigned ch
   if ((need_h && (!bounds_h || !coef_h || ksize_h <= 0)) || (need_v && (!bounds_v || !coef_v || ksize_v <= 0)) ||
       (need_h && need_v && !tmp))
     return MEGA_ERR_ARG;
-  auto grid = [](size_t total) { return dim3((unsigned)((total + 255) / 256 > 32768 ? 32768 : (total + 255) / 256)); };
+  auto grid = [](size_t total) { return dim3(grid1d(total, 32768)); };
   hipStream_t st = (hipStream_t)stream;
   if (!need_h && !need_v) {
     hipLaunchKernelGGL(mirror_kernel, grid((size_t)N * Hi * Wi), dim3(256), 0, st, in, out, N, Hi, Wi);

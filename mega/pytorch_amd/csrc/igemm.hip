@@ -19,7 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "common.h"
+#include "launch.h"
 #include "igemm_params.h"
 
 namespace {
@@ -416,10 +416,7 @@ template <typename T, typename OT, int BM, int BN, bool PS = false>
 int launch(const ConvParams& p, hipStream_t st) {
   const int ntm = cdiv(p.M, BM), ntn = cdiv(p.Cout, BN);
   const size_t smem = 2 * (BM + BN) * LDS_STRIDE;
-  // set on every launch: a per-process flag would miss the second device of a multi-GPU process (cheap host call)
-  (void)hipFuncSetAttribute((const void*)igemm_kernel<T, OT, BM, BN, PS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL((igemm_kernel<T, OT, BM, BN, PS>), dim3(ntm * ntn, 1, p.ksplit), dim3(NTHREADS), smem, st, p);
-  return mega_check_launch();
+  return launch_lds(igemm_kernel<T, OT, BM, BN, PS>, dim3(ntm * ntn, 1, p.ksplit), dim3(NTHREADS), smem, st, p);
 }
 
 // out[m][n] = act((sum_z partial[z][m][n]) * scale[n] + bias[n] + res[m][n]); fixed summation order -> deterministic
@@ -448,8 +445,7 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(ConvParams p) {
 template <typename T, typename OT>
 int launch_finalize(const ConvParams& p, hipStream_t st) {
   const size_t total = (size_t)p.M * p.Cout;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  hipLaunchKernelGGL((splitk_finalize_kernel<T, OT>), dim3(blocks), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((splitk_finalize_kernel<T, OT>), dim3(grid1d(total, 8192)), dim3(256), 0, st, p);
   return mega_check_launch();
 }
 

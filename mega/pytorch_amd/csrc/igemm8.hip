@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 #include "igemm_params.h"
 
 namespace {
@@ -769,10 +769,7 @@ int launch8(const ConvParams& p0, hipStream_t st) {
   magic_div(p.Ho * p.Wo, p.mg_howo, p.sh_howo);
   magic_div(p.Wo, p.mg_wo, p.sh_wo);
   const int ntm = cdiv(p.M, BM), ntn = cdiv(p.Cout, 256);
-  // set on every launch (a per-process flag would miss the second device of a multi-GPU process)
-  (void)hipFuncSetAttribute((const void*)igemm8_kernel<OT, MF1, CLS, ABL, SP, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_ALLOC);
-  hipLaunchKernelGGL((igemm8_kernel<OT, MF1, CLS, ABL, SP, HT>), dim3(ntm * ntn, 1, p.ksplit), dim3(NT8), LDS8_ALLOC, st, p);
-  return mega_check_launch();
+  return launch_lds(igemm8_kernel<OT, MF1, CLS, ABL, SP, HT>, dim3(ntm * ntn, 1, p.ksplit), dim3(NT8), LDS8_ALLOC, st, p);
 }
 
 }  // namespace

@@ -24,7 +24,7 @@
 //                       problems: a single-problem entry point launches a batch of one.
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -830,9 +830,11 @@ static int pos_tiled_launch(const MegaPosDescC* d, int n, const float* wg_t, con
     max_k = d[i].Nk > max_k ? d[i].Nk : max_k;
   }
   dim3 grid(cdiv(max_k, 64), cdiv(max_q, 8), n);
-  if (dtype == MEGA_F16) hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
-  else hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg, dim_mat);
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(pos_logits_tiled_batched_kernel<decltype(tag)>, grid, dim3(256), 0, (hipStream_t)stream, b, wg_t, bg,
+                       dim_mat);
+    return mega_check_launch();
+  });
 }
 
 // round 6: the tile-ordered logits in the head's 16-bit operand type (dtype = MEGA_BF16 / MEGA_F16)
@@ -952,25 +954,17 @@ static int attn_launch(const MegaAttnDescC* d, int n, int groups, float scale, i
   // fit three waves per SIMD, and at most 168, without spills, under a 3-block bound (886 against 1020 us at stage 0
   // before dead waves skipped the tile arithmetic, about 700 us since: 166 VGPRs in bf16, 168 in f16);
   // every other variant fits 166 under the 2-block bound and is 4 % faster that way.
-#define MEGA_ATTN_LAUNCH(T, TILED)                                                                              \
-  do {                                                                                                          \
-    if (any_seg) hipLaunchKernelGGL((attn_batched_kernel<T, TILED, true>), grid, dim3(256), 0, st, b);          \
-    else hipLaunchKernelGGL((attn_batched_kernel<T, TILED, false>), grid, dim3(256), 0, st, b);                 \
-  } while (0)
-  if (dtype == MEGA_BF16 && tiled) MEGA_ATTN_LAUNCH(bf16_t, true);
-  else if (dtype == MEGA_BF16) MEGA_ATTN_LAUNCH(bf16_t, false);
-  else if (dtype == MEGA_F16 && tiled) MEGA_ATTN_LAUNCH(f16_t, true);
-  else if (dtype == MEGA_F16) MEGA_ATTN_LAUNCH(f16_t, false);
-  else if (dtype == MEGA_F32) MEGA_ATTN_LAUNCH(float, false);      // (f32: 192 / 211 VGPRs, two blocks per CU)
-#undef MEGA_ATTN_LAUNCH
-  else return MEGA_ERR_ARG;
-  if (any_split) {
-    const int blocks = (int)((max_total + 255) / 256 > 4096 ? 4096 : (max_total + 255) / 256);
-    if (dtype == MEGA_BF16) hipLaunchKernelGGL((attn_combine_batched_kernel<bf16_t>), dim3(blocks, n), dim3(256), 0, st, b);
-    else if (dtype == MEGA_F16) hipLaunchKernelGGL((attn_combine_batched_kernel<f16_t>), dim3(blocks, n), dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((attn_combine_batched_kernel<float>), dim3(blocks, n), dim3(256), 0, st, b);
-  }
-  return mega_check_launch();
+  // (f32: 192 / 211 VGPRs, two blocks per CU; no tile-ordered form: attn_fill has refused pos_tiled with MEGA_F32)
+  return dispatch_elem(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto kernel = any_seg ? attn_batched_kernel<T, false, true> : attn_batched_kernel<T, false, false>;
+    if constexpr (!std::is_same<T, float>::value)
+      if (tiled) kernel = any_seg ? attn_batched_kernel<T, true, true> : attn_batched_kernel<T, true, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, b);
+    if (any_split)
+      hipLaunchKernelGGL(attn_combine_batched_kernel<T>, dim3(grid1d(max_total, 4096), n), dim3(256), 0, st, b);
+    return mega_check_launch();
+  });
 }
 
 extern "C" int mega_relation_attention_batched(const void* descs, int n, int groups, float scale, int dtype,

@@ -222,15 +222,10 @@ extern "C" int mega_soft_merge(const float* cboxes, const float* cscores, int F,
     int T = (KR + 63) / 64 * 64;
     if (T > 1024) T = 1024;
     const int nr = (KR + T - 1) / T;
-#define MEGA_SOFT_LAUNCH(NR)                                                                                          \
-  hipLaunchKernelGGL(soft_nms_kernel<NR>, dim3(P), dim3(T), 0, st, (const float4*)cboxes, cscores, K, F, C1, R,       \
-                     score_thresh, v, nms_thresh, strict_gt, soft_method, sigma, w.mboxes, w.mscores, w.flags, fscores, \
-                     w.keep_pos, w.keep_cnt)
-    if (nr <= 1) MEGA_SOFT_LAUNCH(1);
-    else if (nr <= 2) MEGA_SOFT_LAUNCH(2);
-    else if (nr <= 4) MEGA_SOFT_LAUNCH(4);
-    else MEGA_SOFT_LAUNCH(8);
-#undef MEGA_SOFT_LAUNCH
+    const auto kernel = nr <= 1 ? soft_nms_kernel<1> : nr <= 2 ? soft_nms_kernel<2> : nr <= 4 ? soft_nms_kernel<4> : soft_nms_kernel<8>;
+    hipLaunchKernelGGL(kernel, dim3(P), dim3(T), 0, st, (const float4*)cboxes, cscores, K, F, C1, R, score_thresh, v,
+                       nms_thresh, strict_gt, soft_method, sigma, w.mboxes, w.mscores, w.flags, fscores, w.keep_pos,
+                       w.keep_cnt);
     rc = mega_check_launch();
   } else {
     rc = mega_bbox_aug_load_nms(cboxes, cscores, F, K, R, NC, v, score_thresh, nms_thresh, strict_gt, w, st);

@@ -4,7 +4,7 @@
 //   * ROIAlign forward                                           (mega_core/csrc/cuda/ROIAlign_cuda.cu:15-122,
 //                                                                 csrc/cpu/ROIAlign_cpu.cpp:18-219)
 // Activations are NHWC so that a pixel's channels are one contiguous, coalesced run.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -941,15 +941,14 @@ extern "C" int mega_stem_conv_bn_relu(const float* in, const float* w_tap64, con
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
   dim3 grid(cdiv(Wo, ST_T), cdiv(Ho, ST_T), N);
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == MEGA_BF16)
-    hipLaunchKernelGGL((stem_conv_kernel<bf16_t>), grid, dim3(256), 0, st, in, w_tap64, scale, bias, (bf16_t*)out, N, H,
-                       W, Ho, Wo);
-  else if (out_dtype == MEGA_F32)
-    hipLaunchKernelGGL((stem_conv_kernel<float>), grid, dim3(256), 0, st, in, w_tap64, scale, bias, (float*)out, N, H, W,
-                       Ho, Wo);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  auto go = [&](auto tag) {                                    // (no f16 form of this kernel)
+    using T = decltype(tag);
+    hipLaunchKernelGGL((stem_conv_kernel<T>), grid, dim3(256), 0, st, in, w_tap64, scale, bias, (T*)out, N, H, W, Ho, Wo);
+    return mega_check_launch();
+  };
+  if (out_dtype == MEGA_BF16) return go(bf16_t{});
+  if (out_dtype == MEGA_F32) return go(float{});
+  return MEGA_ERR_ARG;
 }
 
 extern "C" int mega_maxpool3x3s2_nhwc(const void* in, void* out, int N, int H, int W, int C, int dtype, void* stream) {
@@ -957,28 +956,15 @@ extern "C" int mega_maxpool3x3s2_nhwc(const void* in, void* out, int N, int H, i
   if (!in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0) return MEGA_ERR_ARG;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEGA_BF16) {
-    if (C % 8) return MEGA_ERR_ARG;
-    const size_t total = (size_t)N * Ho * Wo * (C / 8);
-    const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL((maxpool_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, N, H,
-                       W, C, Ho, Wo);
-  } else if (dtype == MEGA_F16) {
-    if (C % 8) return MEGA_ERR_ARG;
-    const size_t total = (size_t)N * Ho * Wo * (C / 8);
-    const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL((maxpool_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, (const f16_t*)in, (f16_t*)out, N, H,
-                       W, C, Ho, Wo);
-  } else if (dtype == MEGA_F32) {
-    if (C % 4) return MEGA_ERR_ARG;
-    const size_t total = (size_t)N * Ho * Wo * (C / 4);
-    const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL((maxpool_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)in, (float*)out, N, H, W,
-                       C, Ho, Wo);
-  } else {
-    return MEGA_ERR_ARG;
-  }
-  return mega_check_launch();
+  return dispatch_elem(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int VE = Elem<T>::VE;
+    if (C % VE) return MEGA_ERR_ARG;
+    const size_t total = (size_t)N * Ho * Wo * (C / VE);
+    hipLaunchKernelGGL((maxpool_kernel<T>), dim3(grid1d(total, 8192)), dim3(256), 0, st, (const T*)in, (T*)out, N, H, W, C,
+                       Ho, Wo);
+    return mega_check_launch();
+  });
 }
 
 extern "C" int mega_roi_align_fwd(const void* feat, const float* rois, void* out, int K, int C, int H, int W,
@@ -994,63 +980,37 @@ extern "C" int mega_roi_align_fwd(const void* feat, const float* rois, void* out
     const long long total = (long long)K * pooled_h * pooled_w * CV;
     const bool xcd_slices = CV % 8 == 0 && CV / 8 >= 16;         // >= 16 channel vectors for each of the 8 XCDs
     const bool sliced = xcd_slices && total / 8 >= 256 * 64;
-    long long nb = ((sliced ? total / 8 : total) + 255) / 256;
-    if (nb > 131072) nb = 131072;
-    dim3 vgrid((unsigned)(sliced ? nb * 8 : nb));
+    const unsigned nb = grid1d(sliced ? total / 8 : total, 131072);
+    dim3 vgrid(sliced ? nb * 8 : nb);
     // the separable per-ROI form: 16-bit types, adaptive grid only (sampling_ratio > 0 spreads a bin's samples over a sparse
     // patch); ROIs whose patch exceeds its tables fall back inside the kernel, so no bound on the boxes is assumed here
     const bool separable = (dtype == MEGA_F16 || dtype == MEGA_BF16) && sampling_ratio <= 0 && pooled_w <= RS_MAXPW &&
                            pooled_h <= RS_MAXPW;
-    if (separable) {
-      auto launch_sep = [&](auto elem) {
-        using T = decltype(elem);
-        if (xcd_slices)
-          hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<T, 8>), dim3((unsigned)(K * 8)), dim3(256), 0, st, (const T*)feat,
-                             rois, (T*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
-        else
-          hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<T, 1>), dim3((unsigned)K), dim3(256), 0, st, (const T*)feat, rois,
-                             (T*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
-      };
-      if (dtype == MEGA_F16) launch_sep(f16_t{});
-      else launch_sep(bf16_t{});
+    if (separable)
+      return dispatch_half(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const auto kernel = xcd_slices ? roi_align_nhwc_sep_kernel<T, 8> : roi_align_nhwc_sep_kernel<T, 1>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(xcd_slices ? K * 8 : K)), dim3(256), 0, st, (const T*)feat, rois, (T*)out,
+                           K, C, H, W, spatial_scale, pooled_h, pooled_w);
+        return mega_check_launch();
+      });
+    return dispatch_elem(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      const auto kernel = sliced ? roi_align_nhwc_vec_kernel<T, true> : roi_align_nhwc_vec_kernel<T, false>;
+      hipLaunchKernelGGL(kernel, vgrid, dim3(256), 0, st, (const T*)feat, rois, (T*)out, K, C, H, W, spatial_scale, pooled_h,
+                         pooled_w, sampling_ratio);
       return mega_check_launch();
-    }
-    if (dtype == MEGA_BF16 && sliced)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<bf16_t, true>), vgrid, dim3(256), 0, st, (const bf16_t*)feat, rois,
-                         (bf16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else if (dtype == MEGA_BF16)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<bf16_t, false>), vgrid, dim3(256), 0, st, (const bf16_t*)feat, rois,
-                         (bf16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else if (dtype == MEGA_F16 && sliced)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<f16_t, true>), vgrid, dim3(256), 0, st, (const f16_t*)feat, rois,
-                         (f16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else if (dtype == MEGA_F16)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<f16_t, false>), vgrid, dim3(256), 0, st, (const f16_t*)feat, rois,
-                         (f16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else if (dtype == MEGA_F32 && sliced)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, true>), vgrid, dim3(256), 0, st, (const float*)feat, rois,
-                         (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else if (dtype == MEGA_F32)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, false>), vgrid, dim3(256), 0, st, (const float*)feat, rois,
-                         (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else
-      return MEGA_ERR_ARG;
-    return mega_check_launch();
+    });
   }
+  if (dtype != out_dtype) return MEGA_ERR_ARG;
   dim3 grid((unsigned)(K * pooled_h * pooled_w));
   const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-  if (dtype == MEGA_BF16 && out_dtype == MEGA_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<bf16_t, bf16_t>), grid, dim3(threads), 0, st, (const bf16_t*)feat, rois,
-                       (bf16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio, in_nhwc, out_nhwc);
-  else if (dtype == MEGA_F16 && out_dtype == MEGA_F16)
-    hipLaunchKernelGGL((roi_align_kernel<f16_t, f16_t>), grid, dim3(threads), 0, st, (const f16_t*)feat, rois,
-                       (f16_t*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio, in_nhwc, out_nhwc);
-  else if (dtype == MEGA_F32 && out_dtype == MEGA_F32)
-    hipLaunchKernelGGL((roi_align_kernel<float, float>), grid, dim3(threads), 0, st, (const float*)feat, rois,
-                       (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio, in_nhwc, out_nhwc);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  return dispatch_elem(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((roi_align_kernel<T, T>), grid, dim3(threads), 0, st, (const T*)feat, rois, (T*)out, K, C, H, W,
+                       spatial_scale, pooled_h, pooled_w, sampling_ratio, in_nhwc, out_nhwc);
+    return mega_check_launch();
+  });
 }
 
 extern "C" int mega_avgpool2x2_ceil_nhwc(const void* in, void* out, int N, int H, int W, int C, int dtype,
@@ -1062,16 +1022,15 @@ extern "C" int mega_avgpool2x2_ceil_nhwc(const void* in, void* out, int N, int H
   const int ve = dtype == MEGA_BF16 ? 8 : 4;
   if (C % ve) return MEGA_ERR_ARG;
   const size_t total = (size_t)N * Ho * Wo * (C / ve);
-  const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  if (dtype == MEGA_BF16)
-    hipLaunchKernelGGL((avgpool2_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, N, H,
-                       W, C, Ho, Wo);
-  else if (dtype == MEGA_F32)
-    hipLaunchKernelGGL((avgpool2_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)in, (float*)out, N, H, W,
-                       C, Ho, Wo);
-  else
-    return MEGA_ERR_ARG;
-  return mega_check_launch();
+  auto go = [&](auto tag) {                                    // (no f16 form of this kernel)
+    using T = decltype(tag);
+    hipLaunchKernelGGL((avgpool2_kernel<T>), dim3(grid1d(total, 8192)), dim3(256), 0, st, (const T*)in, (T*)out, N, H, W, C,
+                       Ho, Wo);
+    return mega_check_launch();
+  };
+  if (dtype == MEGA_BF16) return go(bf16_t{});
+  if (dtype == MEGA_F32) return go(float{});
+  return MEGA_ERR_ARG;
 }
 
 // 7x7/2 stem conv + FrozenBN + ReLU + 3x3/2 max-pool (pad 1) in one kernel, bf16: in = preprocessed f32 NCHW [N][3][H][W]
@@ -1091,38 +1050,18 @@ extern "C" int mega_stem_pool_dt(const void* in, int u8, const void* w_n176, con
   const long tiles = (long)N * tiles_y * tiles_x;
   if (tiles > 0x7FFF0000L) return MEGA_ERR_ARG;                // (the kernel's tile index + grid stays an int)
   if (u8 && (size_t)H * W * 3 > 0x7FFFFFFFu) return MEGA_ERR_ARG;
-  int cus = 256;
-  {
-    static int cached[64] = {0};       // per device id: a multi-GPU process may hold devices with different CU counts
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cached[dev]) {
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cached[dev] = n;
-      else cached[dev] = 256;
-    }
-    cus = cached[dev];
-  }
+  const int cus = mega_cu_count();
   const dim3 grid((unsigned)(tiles < 2L * cus ? tiles : 2L * cus));   // two resident blocks per CU, each walks the tiles
   const int nt = (int)tiles;
   hipStream_t st = (hipStream_t)stream;
   const bf16_t* w = (const bf16_t*)w_n176;
   bf16_t* o = (bf16_t*)out;
   if (!u8) { mean0 = mean1 = mean2 = 0.f; to_bgr = 0; }
-#define MEGA_SP_LAUNCH(U8_, HT_)                                                                                           \
-  do {                                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)stem_pool_kernel<U8_, HT_>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS); \
-    hipLaunchKernelGGL((stem_pool_kernel<U8_, HT_>), grid, dim3(256), SP_LDS, st, in, w, scale, bias, o, N, H, W, Ho, Wo,   \
-                       Hp, Wp, mean0, mean1, mean2, to_bgr, tiles_y, tiles_x, nt);                                         \
-  } while (0)
-  if (dtype == MEGA_F16) {
-    if (u8) MEGA_SP_LAUNCH(true, f16_t);
-    else MEGA_SP_LAUNCH(false, f16_t);
-  } else {
-    if (u8) MEGA_SP_LAUNCH(true, bf16_t);
-    else MEGA_SP_LAUNCH(false, bf16_t);
-  }
-#undef MEGA_SP_LAUNCH
-  return mega_check_launch();
+  return dispatch_half(dtype, [&](auto tag) {
+    using HT = decltype(tag);
+    return launch_lds(u8 ? stem_pool_kernel<true, HT> : stem_pool_kernel<false, HT>, grid, dim3(256), SP_LDS, st, in, w, scale,
+                      bias, o, N, H, W, Ho, Wo, Hp, Wp, mean0, mean1, mean2, to_bgr, tiles_y, tiles_x, nt);
+  });
 }
 
 // The pooled tile (rows, columns) one unit of mega_stem_pool_dt's work covers: what a test of its tile edges is built on.
@@ -1144,35 +1083,22 @@ extern "C" int mega_roi_align_fwd_planes_dt(const float* feat, const float* rois
   const int CV = C / 4;
   const long long total = (long long)K * pooled_h * pooled_w * CV;
   const bool sliced = CV % 8 == 0 && CV / 8 >= 16 && total / 8 >= 256 * 64;
-  long long nb = ((sliced ? total / 8 : total) + 255) / 256;
-  if (nb > 131072) nb = 131072;
-  dim3 vgrid((unsigned)(sliced ? nb * 8 : nb));
+  const unsigned nb = grid1d(sliced ? total / 8 : total, 131072);
+  dim3 vgrid(sliced ? nb * 8 : nb);
   hipStream_t st = (hipStream_t)stream;
   // the separable per-ROI form (adaptive grid, one block per ROI x XCD channel slice), as the 16-bit kernels: the sums differ
   // from the exact-term-order kernel at f32 round-off (~1e-7 relative)
   const bool separable = sliced && sampling_ratio <= 0 && pooled_w <= RS_MAXPW && pooled_h <= RS_MAXPW;
-  if (separable) {
-    if (dtype == MEGA_F16)
-      hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<float, 8, true, f16_t>), dim3((unsigned)(K * 8)), dim3(256), 0, st, feat, rois,
+  return dispatch_half(dtype, [&](auto tag) {
+    using PT = decltype(tag);                                  // the planes' 16-bit type
+    const auto vec_kernel = sliced ? roi_align_nhwc_vec_kernel<float, true, true, PT> : roi_align_nhwc_vec_kernel<float, false, true, PT>;
+    if (separable)
+      hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<float, 8, true, PT>), dim3((unsigned)(K * 8)), dim3(256), 0, st, feat, rois,
                          (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
     else
-      hipLaunchKernelGGL((roi_align_nhwc_sep_kernel<float, 8, true, bf16_t>), dim3((unsigned)(K * 8)), dim3(256), 0, st, feat, rois,
-                         (float*)out, K, C, H, W, spatial_scale, pooled_h, pooled_w);
+      hipLaunchKernelGGL(vec_kernel, vgrid, dim3(256), 0, st, feat, rois, (float*)out, K, C, H, W, spatial_scale, pooled_h,
+                         pooled_w, sampling_ratio);
     return mega_check_launch();
-  }
-  if (dtype == MEGA_F16) {
-    if (sliced)
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, true, true, f16_t>), vgrid, dim3(256), 0, st, feat, rois, (float*)out, K, C,
-                         H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-    else
-      hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, false, true, f16_t>), vgrid, dim3(256), 0, st, feat, rois, (float*)out, K,
-                         C, H, W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-  } else if (sliced)
-    hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, true, true>), vgrid, dim3(256), 0, st, feat, rois, (float*)out, K, C, H,
-                       W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-  else
-    hipLaunchKernelGGL((roi_align_nhwc_vec_kernel<float, false, true>), vgrid, dim3(256), 0, st, feat, rois, (float*)out, K, C, H,
-                       W, spatial_scale, pooled_h, pooled_w, sampling_ratio);
-  return mega_check_launch();
+  });
 }
 
