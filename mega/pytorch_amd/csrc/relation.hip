@@ -122,17 +122,20 @@ __device__ __forceinline__ float sin_shifted(float a, float shift_rev) {
 }
 
 // The same value with the argument already in REVOLUTIONS: sin(2 pi (x_rev + shift_rev)).  The position arguments are
-// 100 * log-ratio / 1000^(i/8) with |log-ratio| <= 6.91 (the 1e-3 floor and a 1000-pixel image), i.e. |x_rev| <= 110:
+// 100 * log-ratio / 1000^(i/8) with |log-ratio| <= 6.91 (the 1e-3 floor and a 1000-pixel image), i.e. |x_rev| <= 110
+// -- 7.2 and 114.5 on a 1333-pixel image, and anything below 128 revolutions has the same ulp:
 // an f32 at that magnitude resolves 7.6e-6 revolutions = 4.8e-5 rad, the same as the radian argument the Cody-Waite
 // form starts from (ulp of 690 rad = 6.1e-5), so v_fract + v_sin loses nothing -- and costs 3 VALU per value (fma,
-// fract, sin) instead of 7.  (gfx9+ v_sin_f32 wants its argument pre-reduced to [0, 1).)
+// fract, sin) instead of 7.  (gfx9+ v_sin_f32 wants its argument pre-reduced to [0, 1).)  tests/test_position_gpu.py
+// holds every embedding entry to a bound derived from these roundings, 1-pixel against 1333-pixel boxes included.
 __device__ __forceinline__ float sin_rev(float x_rev) {
   return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(x_rev));
 }
 
-// fast-mode (bf16 path) logarithm / division: v_log_f32 (1 ulp in log2) and v_rcp_f32 -- the position arguments are
-// 100 x log(ratio): an absolute error of ~1e-6 in the log moves the phase by 1e-4 rad, far below the bf16 rounding
-// of the embedding that follows.
+// fast-mode (bf16 path) logarithm / division: v_log_f32 (nominally 1 ulp in log2) and v_rcp_f32 -- the position
+// arguments are 100 x log(ratio): an absolute error of ~1e-6 in the log moves the phase by 1e-4 rad, far below the bf16
+// rounding of the embedding that follows.  (The 1 ulp is not a guarantee: the library's logf, which is v_log_f32 x ln 2 in
+// extended precision, was seen 1.0e-6 = 2.2 ulp from float64 at log 918.001, i.e. v_log_f32 at least 1.2 ulp off there.)
 __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 __device__ __forceinline__ float fast_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
