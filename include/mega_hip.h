@@ -78,6 +78,15 @@ int mega_conv2d_nhwc_ws(const void* in, const void* w, const float* scale, const
                         void* out, int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,
                         int relu, int ldo, int ldr, int in_dtype, int out_dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* mega_conv2d_nhwc for a 1x1 / stride 1 / unpadded conv whose residual is read at a pixel stride: output pixel (t, y, x) adds
+ * pixel (res_stride y, res_stride x) of the NHWC tensor residual [N][res_H][res_W][ldr], i.e. residual[:, ::s, ::s, :] read in
+ * place (a bottleneck's conv3 run at the even pixels only, the identity taken from the block's dense input).  dtype MEGA_BF16 /
+ * MEGA_F16 = operands and output; Cin % 64 == 0, Cin <= 512, Cout % 256 == 0, (H - 1) res_stride < res_H, (W - 1) res_stride <
+ * res_W.  Same bits as mega_conv2d_nhwc on the gathered residual. */
+int mega_conv2d_nhwc_rs(const void* in, const void* w, const float* scale, const float* bias, const void* residual, void* out,
+                        int N, int H, int W, int Cin, int Cout, int relu, int ldo, int ldr, int res_H, int res_W, int res_stride,
+                        int dtype, void* stream);
+
 /* ResNet stem: 7x7 stride-2 pad-3 conv (3->64) + FrozenBN + ReLU  (resnet.py:347-366 BaseStem.forward,
  * without the max-pool).  in: NCHW f32 [N][3][H][W]; w_tap64: [147][64] f32 with tap = (c*7+r)*7+s;
  * out: NHWC [N][Ho][Wo][64], Ho = (H-1)/2+1. */
@@ -322,6 +331,13 @@ int mega_copy_segments(const void* segs, int n, void* stream);
 int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
                              const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
                              int dtype, void* stream);
+
+/* mega_bottleneck64_fwd_dt at the even pixels only: out = y[:, ::2, ::2, :] as a contiguous [N][ceil(H/2)][ceil(W/2)][256]
+ * tensor, for a block whose only reader is a stride-2 1x1 conv.  conv1 runs on every pixel (the 3x3 windows need it); conv2,
+ * conv3, the residual and the stores on a quarter of them.  Bit-identical to the dense form at those pixels. */
+int mega_bottleneck64_even_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                                  const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
+                                  int dtype, void* stream);
 
 /* The stage's first block with the 1x1 downsample branch on the residual (layer1 block 0: 64 -> 64 -> 64 (3x3) -> 256,
  * backbone/resnet.py:266-276,:324-344), one persistent kernel:

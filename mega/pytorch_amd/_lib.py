@@ -18,6 +18,7 @@ SIGNATURES = {
     "mega_conv2d_nhwc": (c_int, [c_void_p] * 6 + [c_int] * 15 + [c_void_p]),
     "mega_conv2d_nhwc_ws": (c_int, [c_void_p] * 6 + [c_int] * 15 + [c_void_p, c_size_t, c_void_p]),
     "mega_conv2d_nhwc_workspace_bytes": (c_size_t, [c_int] * 3),
+    "mega_conv2d_nhwc_rs": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
     "mega_stem_conv_bn_relu": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "mega_stem_conv_bn_relu_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "mega_stem_conv_bn_relu_bf16_u8": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float] * 3 + [c_int, c_void_p]),
@@ -74,6 +75,7 @@ SIGNATURES = {
     "mega_fgfa_warp_aggregate_ring": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "mega_copy_segments": (c_int, [c_void_p, c_int, c_void_p]),
     "mega_bottleneck64_fwd_dt": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
+    "mega_bottleneck64_even_fwd_dt": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
     "mega_bottleneck64_ds_fwd_dt": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_void_p]),
     "mega_cast_f32_to_half": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "mega_copy_cast_segments_dt": (c_int, [c_void_p, c_int, c_int, c_void_p]),

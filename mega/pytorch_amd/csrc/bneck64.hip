@@ -55,7 +55,7 @@ struct Bneck64Params {
   const bf16_t* w2;     // [64][3][3][64]
   const bf16_t* w3;     // [256][64]
   const float *s1, *b1, *s2, *b2, *s3, *b3;
-  bf16_t* out;          // [N][H][W][256]
+  bf16_t* out;          // [N][H][W][256]; even-pixel form: [N][ceil(H/2)][ceil(W/2)][256]
   int N, H, W, tiles_y, tiles_x, ntiles;
 };
 
@@ -78,8 +78,15 @@ __device__ __forceinline__ bf16_t bk_relu1(float a) {
   return (short)h < 0 ? (bf16_t)0 : h;
 }
 
-template <typename HT>
-__global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
+// EVEN: the even-pixel form -- out = y[:, ::2, ::2, :] as a contiguous [N][ceil(H/2)][ceil(W/2)][256] tensor, for a block whose
+// only reader is a stride-2 1x1 conv (the next stage's conv1 / downsample read pixels (2i, 2j) and nothing else).  conv1 still
+// runs on the whole halo patch (the 3x3 windows around the even pixels cover it); conv2, conv3, the residual, the ReLU and the
+// staged stores run for the tile's 4 x 8 even pixels only (tile origins are multiples of 8 / 16: even already) -- ONE 32-pixel
+// MFMA block: conv2 on waves 0 / 1 (32 channels each), conv3 on every wave (its 32 output channels).  An output element keeps
+// its MFMA, its ascending (r, s, c) K order, the roundings of t1 / t2 and its epilogue arithmetic: the dense form's bits.
+template <typename HT, bool EVEN>
+__device__ __forceinline__ void bneck64_body(const Bneck64Params p) {
+  constexpr int NMB = EVEN ? 1 : 4;             // 32-pixel blocks of conv3 / the epilogue per tile
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const w2l = smem + BK_OFF_W2;
   unsigned char* const t1l = smem + BK_OFF_T1;
@@ -103,7 +110,9 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
   // an out-of-range offset, which the hardware range check turns into zeros -- no 64-bit address arithmetic per load
   const unsigned xbytes = (unsigned)((size_t)p.N * p.H * p.W * 512);
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.x), 0, (int)xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)xbytes, 0x00020000);
+  const int oH = (p.H + 1) >> 1, oW = (p.W + 1) >> 1;          // (EVEN) the compact output's size
+  const unsigned obytes = EVEN ? (unsigned)((size_t)p.N * oH * oW * 512) : xbytes;
+  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)obytes, 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
 
   auto tile_origin = [&](int t, int& n, int& y0, int& x0) {
@@ -147,8 +156,9 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
   const unsigned a1_base = (unsigned)(r1 * 128), a1_sw = (unsigned)((r1 >> 1) & 7);
   const unsigned b1_base = (unsigned)(l31 * BK_WROW + h * 16);
   // conv2: wave (mb, nb): pixels of tile rows 2 mb, 2 mb + 1; channels 32 nb ..
-  const int mb2 = wave >> 1, nb2 = wave & 1;
-  const int ay = 2 * mb2 + (l31 >> 4), ax = l31 & 15;
+  // (EVEN: waves 0 / 1 only, mb = 0: A fragment row l31 = even pixel (l31 >> 3, l31 & 7) = tile pixel (2 (l31 >> 3), 2 (l31 & 7)))
+  const int mb2 = EVEN ? 0 : wave >> 1, nb2 = wave & 1;
+  const int ay = EVEN ? 2 * (l31 >> 3) : 2 * mb2 + (l31 >> 4), ax = EVEN ? 2 * (l31 & 7) : l31 & 15;
   const unsigned a2_base = (unsigned)((ay * BK_PX + ax) * 128);
   const int b2_off = (32 * nb2 + l31) * BK_W2ROW + h * 16;
   // conv3: wave w owns output channels 32 w .. 32 w + 31; A fragment row = 32 mb + l31 of t2 (the swizzle repeats every 16 rows)
@@ -229,23 +239,23 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
     prefetch(t + gridDim.x);
     __syncthreads();                            // t1 and w3 are visible
     // ================= conv2: 9 taps x 4 channel steps
-    f32x16_t c2;
+    if (!EVEN || wave < 2) {
+      f32x16_t c2;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) c2[r] = 0.f;
+      for (int r = 0; r < 16; ++r) c2[r] = 0.f;
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+      for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
+        for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const unsigned sw2 = (unsigned)(((ax + kw) >> 1) & 7);
-          const uint4 a = *reinterpret_cast<const uint4*>(t1l + a2_base + (kh * BK_PX + kw) * 128 +
-                                                          (((unsigned)(2 * ks + h) ^ sw2) << 4));
-          const uint4 b = *reinterpret_cast<const uint4*>(w2l + b2_off + (kh * 3 + kw) * 128 + ks * 32);
-          c2 = bk_mma<HT>(c2, a, b);
-        }
-    // ---- t2 = relu(bn2(.)) as bf16 [128 px][64 ch], rows swizzled for conv3's A fragments
-    {
+          for (int ks = 0; ks < 4; ++ks) {
+            const unsigned sw2 = (unsigned)(((ax + kw) >> 1) & 7);
+            const uint4 a = *reinterpret_cast<const uint4*>(t1l + a2_base + (kh * BK_PX + kw) * 128 +
+                                                            (((unsigned)(2 * ks + h) ^ sw2) << 4));
+            const uint4 b = *reinterpret_cast<const uint4*>(w2l + b2_off + (kh * 3 + kw) * 128 + ks * 32);
+            c2 = bk_mma<HT>(c2, a, b);
+          }
+      // ---- t2 = relu(bn2(.)) as bf16 [128 px][64 ch] (EVEN: [32 even px][64 ch]), rows swizzled for conv3's A fragments
       const int c = 32 * nb2 + lo;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -257,24 +267,31 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
     // ================= conv3 (64 -> 256) + bn3 + residual + ReLU, one 32-pixel block at a time: this wave's 32 output
     //                   channels; the residual elements of a lane (its channel, its 16 pixels) are 2-byte loads (L2 hits:
     //                   the centre of the patch this CU loaded a tile ago) requested before the block's MFMAs
-    unsigned pk[4][8];                          // results as bf16 pairs: pk[mb][q] = (r = 2 q, r = 2 q + 1)
+    unsigned pk[NMB][8];                        // results as bf16 pairs: pk[mb][q] = (r = 2 q, r = 2 q + 1)
     {
       uint4 bf[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) bf[ks] = *reinterpret_cast<const uint4*>(xbl + b3_base + ks * 32);
       const int c3ch = 32 * wave + lo;
       // byte offset of (tile pixel (0, 4 h), this lane's channel); the rest of a residual element's address is wave-uniform
-      const unsigned res_base = (unsigned)(((n * p.H + y0) * p.W + x0 + 4 * ho) * 512 + c3ch * 2);
+      // (EVEN: even pixel (r >> 2, (r & 3) + 4 h) = tile pixel (2 (r >> 2), 2 (r & 3) + 8 h))
+      const unsigned res_base = (unsigned)(((n * p.H + y0) * p.W + x0 + (EVEN ? 8 : 4) * ho) * 512 + c3ch * 2);
 #pragma unroll
-      for (int mb = 0; mb < 4; ++mb) {
+      for (int mb = 0; mb < NMB; ++mb) {
         __builtin_amdgcn_sched_barrier(0);      // (keeps the 64 residual loads of the four blocks from being hoisted together)
         float rs[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {          // pixel 32 mb + (r&3) + 8 (r>>2) + 4 h of the tile = (row 2 mb + (r>>3), column ...)
-          const int yy = y0 + 2 * mb + (r >> 3), xx = x0 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * ho;
-          const unsigned o = (yy < p.H && xx < p.W) ? res_base : OOB;
-          const unsigned short q = __builtin_amdgcn_raw_buffer_load_b16(
-              rs_x, o, ((2 * mb + (r >> 3)) * p.W + (r & 3) + 8 * ((r >> 2) & 1)) * 512, 0);
+          unsigned short q;
+          if constexpr (EVEN) {
+            const int yy = y0 + 2 * (r >> 2), xx = x0 + 2 * (r & 3) + 8 * ho;
+            const unsigned o = (yy < p.H && xx < p.W) ? res_base : OOB;
+            q = __builtin_amdgcn_raw_buffer_load_b16(rs_x, o, (2 * (r >> 2) * p.W + 2 * (r & 3)) * 512, 0);
+          } else {
+            const int yy = y0 + 2 * mb + (r >> 3), xx = x0 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * ho;
+            const unsigned o = (yy < p.H && xx < p.W) ? res_base : OOB;
+            q = __builtin_amdgcn_raw_buffer_load_b16(rs_x, o, ((2 * mb + (r >> 3)) * p.W + (r & 3) + 8 * ((r >> 2) & 1)) * 512, 0);
+          }
           rs[r] = Half16<HT>::one(q);
         }
         f32x16_t c3;
@@ -295,11 +312,12 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
       }
     }
     __syncthreads();                            // every wave is done with t2 / w3: the staging area may overwrite them
-    // ================= the tile as bf16 [128 px][256 ch] through LDS (528-byte rows), out as whole 16-byte vectors
+    // ================= the tile as bf16 [128 px][256 ch] (EVEN: [32 even px]) through LDS (528-byte rows), out as whole
+    //                   16-byte vectors
     {
       const int c3ch = 32 * wave + lo;
 #pragma unroll
-      for (int mb = 0; mb < 4; ++mb)
+      for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int P = 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * ho;
@@ -309,18 +327,29 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) {
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < 2 * NMB; ++i) {
       const int id = tid + BK_NT * i;           // 0 .. 4095: pixel P = id >> 5, 8-channel vector cv = id & 31
       const int P = id >> 5, cv = id & 31;
-      const int yy = y0 + (P >> 4), xx = x0 + (P & 15);
       const uint4 v = *reinterpret_cast<const uint4*>(sbl + P * BK_SBROW + cv * 16);
       const u32x4_t q = {v.x, v.y, v.z, v.w};
-      const unsigned o = (yy < p.H && xx < p.W) ? (unsigned)(((n * p.H + yy) * p.W + xx) * 512 + cv * 16) : OOB;
+      unsigned o;
+      if constexpr (EVEN) {                     // image pixel (yy, xx), both even, is pixel (yy / 2, xx / 2) of the compact output
+        const int yy = y0 + 2 * (P >> 3), xx = x0 + 2 * (P & 7);
+        o = (yy < p.H && xx < p.W) ? (unsigned)(((n * oH + (yy >> 1)) * oW + (xx >> 1)) * 512 + cv * 16) : OOB;
+      } else {
+        const int yy = y0 + (P >> 4), xx = x0 + (P & 15);
+        o = (yy < p.H && xx < p.W) ? (unsigned)(((n * p.H + yy) * p.W + xx) * 512 + cv * 16) : OOB;
+      }
       __builtin_amdgcn_raw_buffer_store_b128(q, rs_o, o, 0, 0);
     }
     __syncthreads();                            // the staging area is free again (the next tile's conv1 chunks, t1)
   }
 }
+
+template <typename HT>
+__global__ __launch_bounds__(BK_NT, 2) void bneck64_kernel(Bneck64Params p) { bneck64_body<HT, false>(p); }
+template <typename HT>
+__global__ __launch_bounds__(BK_NT, 2) void bneck64_even_kernel(Bneck64Params p) { bneck64_body<HT, true>(p); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The stage's FIRST block (layer1 block 0: 64 -> 64 -> 64 (3x3) -> 256 channels with the 1x1 downsample branch on the
@@ -584,9 +613,9 @@ __global__ __launch_bounds__(BK_NT, 2) void bneck64_ds_kernel(Bneck64DsParams p)
 
 // y = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + x) for a 256 -> 64 -> 64 (3x3, pad 1) -> 256 identity bottleneck,
 // NHWC bf16, FrozenBN as f32 scale / bias vectors.  Bit-identical to the three mega_conv2d_nhwc launches it replaces.
-extern "C" int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
-                                        const float* s2, const float* b2, const void* w3, const float* s3, const float* b3,
-                                        void* out, int N, int H, int W, int dtype, void* stream) {
+static int bottleneck64_launch(const void* x, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                               const float* b2, const void* w3, const float* s3, const float* b3, void* out, int N, int H, int W,
+                               int dtype, bool even, void* stream) {
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (!x || !w1 || !s1 || !b1 || !w2 || !s2 || !b2 || !w3 || !s3 || !b3 || !out || N <= 0 || H <= 0 || W <= 0) return MEGA_ERR_ARG;
@@ -604,8 +633,23 @@ extern "C" int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const flo
   const int cus = mega_cu_count();
   const int grid = (int)(tiles < cus ? tiles : cus);
   return dispatch_half(dtype, [&](auto tag) {
+    if (even) return launch_lds(bneck64_even_kernel<decltype(tag)>, dim3(grid), dim3(BK_NT), BK_LDS, (hipStream_t)stream, p);
     return launch_lds(bneck64_kernel<decltype(tag)>, dim3(grid), dim3(BK_NT), BK_LDS, (hipStream_t)stream, p);
   });
+}
+
+extern "C" int mega_bottleneck64_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
+                                        const float* s2, const float* b2, const void* w3, const float* s3, const float* b3,
+                                        void* out, int N, int H, int W, int dtype, void* stream) {
+  return bottleneck64_launch(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, out, N, H, W, dtype, false, stream);
+}
+
+// The same block at its even pixels only: out = y[:, ::2, ::2, :] as a contiguous [N][ceil(H/2)][ceil(W/2)][256] tensor, for a
+// block whose only reader is a stride-2 1x1 conv (bneck64_body, EVEN).  Bit-identical to the dense form at those pixels.
+extern "C" int mega_bottleneck64_even_fwd_dt(const void* x, const void* w1, const float* s1, const float* b1, const void* w2,
+                                             const float* s2, const float* b2, const void* w3, const float* s3, const float* b3,
+                                             void* out, int N, int H, int W, int dtype, void* stream) {
+  return bottleneck64_launch(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, out, N, H, W, dtype, true, stream);
 }
 
 // The stage's first block with the 1x1 downsample branch: x NHWC bf16 [N][H][W][64] -> out [N][H][W][256],

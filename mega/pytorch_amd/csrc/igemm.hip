@@ -508,6 +508,11 @@ inline ConvPlan plan_conv(const ConvParams& p, bool half, bool f32_out) {
   const int M = p.M, Cout = p.Cout, K = p.K, z = p.ksplit;
   int bm = 0, bn = 0;
   bool want8 = false;
+  if (conv_res_strided(p)) {           // the strided residual read exists in igemm8's epilogue only: whatever the launch's size
+    bm = igemm8_rows(M, Cout, z);      // (its launcher refuses what that epilogue does not serve)
+    if (force) sscanf(force, "8:%d", &bm);
+    return {mega_igemm8_streaming(p.R * p.S, K) && z == 1 ? KERNEL_IGEMM8S : KERNEL_IGEMM8, bm, 256};
+  }
   if (force && sscanf(force, "8:%d", &bm) == 1) want8 = true;
   else if (force && sscanf(force, "%dx%d", &bm, &bn) == 2) {      // (a size that is not instantiated runs on 64x64)
     for (const ConvPlan& t : {ConvPlan{0, 256, 256}, {0, 256, 128}, {0, 128, 128}, {0, 128, 64}})
@@ -585,10 +590,11 @@ extern "C" size_t mega_conv2d_nhwc_ks_workspace_bytes(int M, int Cout, int K, in
   return z > 1 ? (size_t)z * M * Cout * sizeof(float) : 0;
 }
 
+struct ResGeom { int H, W, stride; };      // the residual as pixels (stride y, stride x) of [N][H][W][ldr]; stride <= 1: [M][ldr]
 static int conv2d_impl(const void* in, const void* w, const float* scale, const float* bias,
                        const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
                        int R, int S, int stride, int pad, int dil, int relu, int ldo, int ldr,
-                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream);
+                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream, ResGeom rg = {0, 0, 0});
 
 extern "C" int mega_conv2d_nhwc_ws(const void* in, const void* w, const float* scale, const float* bias,
                                    const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
@@ -613,7 +619,7 @@ extern "C" int mega_conv2d_nhwc_ks(const void* in, const void* w, const float* s
 static int conv2d_impl(const void* in, const void* w, const float* scale, const float* bias,
                        const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
                        int R, int S, int stride, int pad, int dil, int relu, int ldo, int ldr,
-                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream) {
+                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream, ResGeom rg) {
   mega_clear_error();
   if (!in || !w || !out) return MEGA_ERR_ARG;
   if (in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
@@ -624,6 +630,10 @@ static int conv2d_impl(const void* in, const void* w, const float* scale, const 
   p.ldo = ldo > 0 ? ldo : Cout;
   p.ldr = ldr > 0 ? ldr : Cout;
   p.relu = relu;
+  if (rg.stride > 1) {      // (igemm8's launcher checks the rest: plan_conv sends every such launch there)
+    if (!residual || in_dtype == MEGA_F32 || out_dtype != in_dtype || ws || ksplit > 0 || rg.H <= 0 || rg.W <= 0) return MEGA_ERR_ARG;
+    conv_rs_H(p) = rg.H; conv_rs_W(p) = rg.W; conv_rs_stride(p) = rg.stride;
+  }
   if (ksplit > 0 || ws) {   // with a workspace the K range of long-K layers is split (mega_conv2d_nhwc_workspace_bytes)
     const int z = ksplit > 0 ? clamp_ksplit(p.K, in_dtype, ksplit) : choose_ksplit(p.K);
     if (z > 1) {
@@ -647,6 +657,19 @@ extern "C" int mega_conv2d_nhwc(const void* in, const void* w, const float* scal
                                 int in_dtype, int out_dtype, void* stream) {
   return mega_conv2d_nhwc_ws(in, w, scale, bias, residual, out, N, H, W, Cin, Cout, R, S, stride, pad, dil, relu, ldo,
                              ldr, in_dtype, out_dtype, nullptr, 0, stream);
+}
+
+// mega_conv2d_nhwc for a 1x1 / stride 1 / unpadded conv whose residual is read at a pixel stride: output pixel (t, y, x) adds
+// pixel (res_stride y, res_stride x) of the NHWC tensor residual [N][res_H][res_W][ldr] -- residual[:, ::s, ::s, :] in place,
+// without the gather (a bottleneck's conv3 run at the even pixels only, its identity taken from the block's dense input).
+// 16-bit operands and output, K <= 512, Cout % 256 == 0; runs on igemm8's tiles at every size.  Same bits as mega_conv2d_nhwc on
+// the gathered residual.
+extern "C" int mega_conv2d_nhwc_rs(const void* in, const void* w, const float* scale, const float* bias, const void* residual,
+                                   void* out, int N, int H, int W, int Cin, int Cout, int relu, int ldo, int ldr, int res_H,
+                                   int res_W, int res_stride, int dtype, void* stream) {
+  if (res_stride < 1) return MEGA_ERR_ARG;
+  return conv2d_impl(in, w, scale, bias, residual, out, N, H, W, Cin, Cout, 1, 1, 1, 0, 1, relu, ldo, ldr, dtype, dtype, nullptr, 0,
+                     0, stream, {res_H, res_W, res_stride});
 }
 
 // ConvTranspose2d(Cin -> C, kernel 4, stride 2, no padding) + bias + activation, cropped, written into a channel slice of an

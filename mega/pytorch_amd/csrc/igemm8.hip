@@ -443,6 +443,10 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   // (t, mh, mw), column (a, b, co) of a transposed conv's four phases goes to pixel (2 mh + a - crop, 2 mw + b - crop), channel
   // ps_coff + co of an NHWC tensor [N][ps_H][ps_W][ldo] (igemm_params.h); the launcher admits only what this path serves
   constexpr bool PS = ABL == 6;
+  // ABL == 7 (a product instantiation too): the residual read at a pixel stride (igemm_params.h rs_*; mega_conv2d_nhwc_rs) -- the
+  // residual row of GEMM row (t, y, x) is pixel (s y, s x) of [N][rs_H][rs_W][ldr], formed by the prologue's magic division.
+  // The launcher admits only what the fast path serves (16-bit output, Cout % 256 == 0, no split-K, a residual tensor below 2 GiB).
+  constexpr bool RS = ABL == 7;
   const size_t out_elems = PS ? (size_t)p.N * p.ps_H * p.ps_W * p.ldo : (size_t)(p.M - 1) * p.ldo + (size_t)oplanes * p.Cout;
   const bool fast = vec_ok && p.ksplit == 1 && (SP ? p.Cout % OVE == 0 : n0 + BN <= p.Cout) && (res == nullptr || sizeof(OT) == 2 || SP) &&
                     out_elems * sizeof(OT) < 0x7FF00000ull &&
@@ -451,7 +455,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
         p.out, 0, (int)(out_elems * sizeof(OT)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(p.res ? p.res : p.out), 0, res ? (int)(((size_t)(p.M - 1) * p.ldr + (size_t)(SP ? 2 : 1) * p.Cout) * 2) : 0, 0x00020000);
+        const_cast<void*>(p.res ? p.res : p.out), 0, res ? (int)(((size_t)(RS ? p.N * conv_rs_H(p) * conv_rs_W(p) - 1 : p.M - 1) * p.ldr + (size_t)(SP ? 2 : 1) * p.Cout) * 2) : 0, 0x00020000);
     constexpr int RSTEP = NT8 / VPR;                   // slab rows between a thread's consecutive vectors
     const int row0 = tid / VPR, ncol = n0 + (tid % VPR) * OVE;
     const unsigned cmask = SP && ncol >= p.Cout ? OOB : 0u;      // (SP) this thread's columns do not exist: loads give 0, stores are dropped
@@ -512,8 +516,17 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
       u32x4_t rr[2][NIT];
       auto ldres = [&](int i, int f, u32x4_t (&dst)[NIT]) {
 #pragma unroll
-        for (int it = 0; it < NIT; ++it)
-          dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, (unsigned)(slab_m(i, f, it) * p.ldr + ncol) * 2u, 0, 0);
+        for (int it = 0; it < NIT; ++it) {
+          if constexpr (RS) {      // a row past M has no pixel: an out-of-range offset (the contiguous form's rows past M are past the buffer)
+            const int m = slab_m(i, f, it);
+            const int t = fast_div(m, p.mg_howo, p.sh_howo), rem = m - t * (p.Ho * p.Wo);
+            const int y = fast_div(rem, p.mg_wo, p.sh_wo), x = rem - y * p.Wo;
+            const unsigned off = m < p.M ? (unsigned)(((t * conv_rs_H(p) + y * conv_rs_stride(p)) * conv_rs_W(p) + x * conv_rs_stride(p)) * p.ldr + ncol) * 2u : OOB;
+            dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0);
+          } else {
+            dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, (unsigned)(slab_m(i, f, it) * p.ldr + ncol) * 2u, 0, 0);
+          }
+        }
       };
       auto ldres_sp = [&](int i, int f) {
 #pragma unroll
@@ -659,6 +672,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   // ---- general path: partial sums of a split-K launch, Cout not a multiple of 256, unaligned rows, outputs >= 2 GiB
   //      (SP kernels get here for split-K partial sums only)
   if (SP && p.ksplit == 1) return;                     // (launch8 refuses such launches: nothing to do here)
+  if (RS) return;                                      // (likewise)
   const bool res_vec = res != nullptr && vec_ok && sizeof(OT) == 2 && p.ksplit == 1;
   uint4 rres2[2][NIT];
   auto load_res = [&](int i, int f, uint4 (&dst)[NIT]) {
@@ -806,6 +820,17 @@ int mega_igemm8_launch(const ConvParams& p, int bm, int out_f32, int half_dtype,
       return MEGA_ERR_ARG;
     if (half_dtype == MEGA_F16) return bm == 192 ? launch8<f16_t, 1, 0, 6, 0, f16_t>(p, st) : launch8<f16_t, 2, 0, 6, 0, f16_t>(p, st);
     if (half_dtype == MEGA_BF16) return bm == 192 ? launch8<bf16_t, 1, 0, 6>(p, st) : launch8<bf16_t, 2, 0, 6>(p, st);
+    return MEGA_ERR_ARG;
+  }
+  if (conv_res_strided(p)) {           // residual read at a pixel stride: streaming class, 16-bit output, the buffer-addressed epilogue only
+    if (p.sp || out_f32 || p.ksplit != 1 || !mega_igemm8_streaming(p.R * p.S, p.K) || p.stride != 1 || p.pad != 0 ||
+        p.Cout % 256 != 0 || p.ldo % 8 != 0 || p.ldr % 8 != 0 || p.ldr < p.Cout ||
+        (long)(p.Ho - 1) * conv_rs_stride(p) >= conv_rs_H(p) || (long)(p.Wo - 1) * conv_rs_stride(p) >= conv_rs_W(p) ||
+        ((size_t)(p.M - 1) * p.ldo + p.Cout) * 2 >= 0x7FF00000ull ||
+        (((size_t)p.N * conv_rs_H(p) * conv_rs_W(p) - 1) * p.ldr + p.Cout) * 2 >= 0x7FF00000ull)
+      return MEGA_ERR_ARG;
+    if (half_dtype == MEGA_F16) return bm == 192 ? launch8<f16_t, 1, 1, 7, 0, f16_t>(p, st) : bm == 256 ? launch8<f16_t, 2, 1, 7, 0, f16_t>(p, st) : MEGA_ERR_ARG;
+    if (half_dtype == MEGA_BF16) return bm == 192 ? launch8<bf16_t, 1, 1, 7>(p, st) : bm == 256 ? launch8<bf16_t, 2, 1, 7>(p, st) : MEGA_ERR_ARG;
     return MEGA_ERR_ARG;
   }
   if (half_dtype == MEGA_F16) {        // IEEE half operands (same tiles, same launch classes)

@@ -32,7 +32,20 @@ struct ConvParams {
   //      2 mw + b - ps_crop), channel ps_coff + co of an NHWC tensor [N][ps_H][ps_W][ldo]; pixels outside it are dropped
   int ps;            // 1: the fields below apply
   int ps_H, ps_W, ps_C, ps_crop, ps_coff;
+  // ---- igemm8 only, ps == 0.  Residual read at a pixel stride (mega_conv2d_nhwc_rs, a 1x1 / stride 1 conv): GEMM row
+  //      m = (t, y, x) adds pixel (s y, s x) of an NHWC tensor [N][rs_H][rs_W][ldr] -- res[:, ::s, ::s, :] read in place.  The two
+  //      launch forms exclude each other, and this one borrows the other's words (conv_rs_* below): rs_H = ps_H, rs_W = ps_W,
+  //      s = ps_C.  The kernels' argument block, and with it every other instantiation's code, stays what it was.
 };
+
+__host__ __device__ inline int& conv_rs_H(ConvParams& p) { return p.ps_H; }
+__host__ __device__ inline int& conv_rs_W(ConvParams& p) { return p.ps_W; }
+__host__ __device__ inline int& conv_rs_stride(ConvParams& p) { return p.ps_C; }
+__host__ __device__ inline int conv_rs_H(const ConvParams& p) { return p.ps_H; }
+__host__ __device__ inline int conv_rs_W(const ConvParams& p) { return p.ps_W; }
+__host__ __device__ inline int conv_rs_stride(const ConvParams& p) { return p.ps_C; }
+// the launch reads its residual at a pixel stride (s <= 1: res is [M][ldr])
+inline bool conv_res_strided(const ConvParams& p) { return !p.ps && p.res && conv_rs_stride(p) > 1; }
 
 // igemm8.hip: bf16 operands, 8 waves, 256 (BM8 rows) x 256 tile; returns MEGA_OK / MEGA_ERR_*.  out_f32: 0 bf16, 1 f32.
 // half_dtype: MEGA_BF16 / MEGA_F16 = the 16-bit type of in / w / residual (and of the output when out_f32 == 0)

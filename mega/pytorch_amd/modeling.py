@@ -268,23 +268,45 @@ class Bottleneck(_Packed):
                 and x.shape[0] * (-(-x.shape[1] // 8)) * (-(-x.shape[2] // 16)) >= 128
                 and os.environ.get("MEGA_FUSE_BOTTLENECK", "1") not in ("0", "id"))
 
-    def run(self, x, out=None):
-        """out: optional destination of the block's output (a contiguous [N,Ho,Wo,Cout] view, e.g. a batch slice)"""
+    def reads_even_pixels_only(self):
+        """the block touches its input through stride-2 1x1 convs alone (conv1 and the downsample, no padding): pixels
+        (2i, 2j) and nothing else -- block 0 of layer2 / layer3 (STRIDE_IN_1X1; res5 is dilated and runs at stride 1)"""
+        return self.stride == 2 and self.dilation == 1 and self.downsample is not None and self.down_stride == 2
+
+    def can_subsample(self, x):
+        """the block can write its output's even pixels alone (run(subsample=True)): an identity block on plain 16-bit device
+        tensors whose conv3 + strided residual igemm8's streaming class serves"""
+        return (not isinstance(x, ops.Planes) and self.sp_mode is None and x.dtype in _HALF and x.is_cuda
+                and self.downsample is None and self.stride == 1 and self.dilation == 1
+                and self.conv3.in_channels <= 512 and self.conv3.out_channels % 256 == 0)
+
+    def run(self, x, out=None, subsample=False, compact_in=False):
+        """out: optional destination of the block's output (a contiguous [N,Ho,Wo,Cout] view, e.g. a batch slice).
+        subsample (can_subsample): -> y[:, ::2, ::2, :] as a contiguous tensor, for a block whose only reader
+        reads_even_pixels_only: conv1 on every pixel (the 3x3 windows around the even pixels cover the map), conv2 as a
+        stride-2 conv, conv3 on its output with the identity read at a pixel stride of 2; same bits at those pixels.
+        compact_in (reads_even_pixels_only): x is such a tensor -- conv1 and the downsample run on it with stride 1."""
         if isinstance(x, ops.Planes) or self.sp_mode is not None:
-            assert out is None
+            assert out is None and not subsample and not compact_in
             return self.run_sp(x)
         pk = self._packed(x.dtype, x.device)
+        assert not subsample or self.can_subsample(x)
+        assert not compact_in or self.reads_even_pixels_only()
         if out is not None:
             assert not self._fusable(x) and not self._fusable_ds(x)
         if self._fusable(x):
-            return ops.bottleneck64(x, pk["w1"], pk["s1"], pk["b1"], pk["w2"], pk["s2"], pk["b2"], pk["w3"], pk["s3"], pk["b3"])
+            return ops.bottleneck64(x, pk["w1"], pk["s1"], pk["b1"], pk["w2"], pk["s2"], pk["b2"], pk["w3"], pk["s3"], pk["b3"],
+                                    subsample=subsample)
         if self._fusable_ds(x):
             return ops.bottleneck64_ds(x, pk["w1"], pk["s1"], pk["b1"], pk["w2"], pk["s2"], pk["b2"], pk["w3"], pk["s3"],
                                        pk["b3"], pk["wd"], pk["sd"], pk["bd"])
         identity = x
         if self.downsample is not None:
-            identity = ops.conv2d_nhwc(x, pk["wd"], pk["sd"], pk["bd"], stride=self.down_stride)
-        t = ops.conv2d_nhwc(x, pk["w1"], pk["s1"], pk["b1"], stride=self.stride, relu=True)
+            identity = ops.conv2d_nhwc(x, pk["wd"], pk["sd"], pk["bd"], stride=1 if compact_in else self.down_stride)
+        t = ops.conv2d_nhwc(x, pk["w1"], pk["s1"], pk["b1"], stride=1 if compact_in else self.stride, relu=True)
+        if subsample:
+            t = ops.conv2d_nhwc(t, pk["w2"], pk["s2"], pk["b2"], stride=2, pad=1, relu=True)
+            return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out=out, residual_stride=2)
         t = ops.conv2d_nhwc(t, pk["w2"], pk["s2"], pk["b2"], pad=self.dilation, dil=self.dilation, relu=True)
         return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out=out)
 
@@ -361,6 +383,10 @@ class ResNet(nn.Module):
                 if isinstance(m, Bottleneck):
                     m.sp_mode = self.mode
 
+    # layer1's and layer2's last blocks write only the pixels layer2.block0 / layer3.block0 read (the even ones; plain 16-bit
+    # modes).  False: every stage output dense, as before -- same C4 bits (tests)
+    skip_unread_pixels = True
+
     def forward(self, x, u8_norm=None):
         """x [N,3,H,W] f32 image batch -> [C4] (logical NCHW, channels-last memory, compute dtype).
         u8_norm = (mean, to_bgr) with x the uint8 frames [N,H,W,3] (bf16 mode): preprocessing fused into the stem.
@@ -381,9 +407,18 @@ class ResNet(nn.Module):
             y = self.stem.run(x.float().contiguous(), torch.float32 if self.mode == "h2" else self.dtype)
         if self.mode in _PLANES3:
             y = ops.split_planes(y, _plane_dtype(self.mode))   # the stem (exact f32 direct conv + max-pool) hands over its f32 map as planes
-        for name in self.stages:
+        compact = False        # y holds the even pixels of the previous stage's output only
+        for si, name in enumerate(self.stages):
             blocks = list(getattr(self, name))
             n = y.shape[0]
+            first_kw = {"compact_in": True} if compact else {}
+            # A stage's output has ONE reader, the next stage's block 0 (this loop; only the last stage's output is returned).
+            # When that block reads_even_pixels_only, three quarters of the last block's pixels are never loaded: it writes the
+            # even ones alone, as a compact tensor, and the next block 0 runs its 1x1 convs on that with stride 1.
+            nxt = getattr(self, self.stages[si + 1])[0] if si + 1 < len(self.stages) else None
+            compact = (self.skip_unread_pixels and nxt is not None and nxt.reads_even_pixels_only()
+                       and len(blocks) > 1 and blocks[-1].can_subsample(y))
+            last_kw = {"subsample": True} if compact else {}
             if name == "layer3" and _L3_SPLIT and not isinstance(y, ops.Planes) and y.is_cuda and y.dtype in _HALF and n >= 32 and n % 2 == 0:
                 # layer3 in two halves of the batch, each through all its blocks: at 20 frames of 600x1000 the working set of a
                 # conv3 + residual layer (221 MB) stays in the 256 MB Infinity Cache -- 4.6 TB/s of algorithmic bytes against
@@ -393,16 +428,17 @@ class ResNet(nn.Module):
                     z = y[lo:lo + n // 2]
                     for bi, blk in enumerate(blocks):
                         if bi + 1 < len(blocks):
-                            z = blk.run(z)
+                            z = blk.run(z, **(first_kw if bi == 0 else {}))
                         else:
+                            assert not compact      # (layer3 is the body's last stage)
                             if out is None:
                                 out = torch.empty((n,) + tuple(z.shape[1:3]) + (blk.conv3.out_channels,), dtype=z.dtype,
                                                   device=z.device)
                             blk.run(z, out=out[lo:lo + n // 2])
                 y = out
                 continue
-            for blk in blocks:
-                y = blk.run(y)
+            for bi, blk in enumerate(blocks):
+                y = blk.run(y, **(first_kw if bi == 0 else {}), **(last_kw if bi + 1 == len(blocks) else {}))
         return y
 
 

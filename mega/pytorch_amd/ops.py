@@ -137,11 +137,15 @@ def _igemm_family(lib, M, Cout, K, dtype, shape=None):
 
 
 def conv2d_nhwc(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_dtype=None,
-                out=None, ksplit=None):
+                out=None, ksplit=None, residual_stride=1):
     """x [N,H,W,Cin] (contiguous), w [Cout,R,S,Cin] -> [N,Ho,Wo,Cout].  y = act(conv*scale + bias (+res));
     relu: False/0 none, True/1 ReLU, 2 LeakyReLU(0.1).  ksplit (int >= 1): the caller's split-K count
-    (mega_conv2d_nhwc_ks: small-M / long-K layers of FlowNetS and the FGFA box head); None: the library's K-only rule."""
+    (mega_conv2d_nhwc_ks: small-M / long-K layers of FlowNetS and the FGFA box head); None: the library's K-only rule.
+    residual_stride s > 1 (a 1x1 / stride 1 conv on 16-bit tensors): residual is [N,Hr,Wr,Cout] with ceil(Hr / s) == Ho,
+    ceil(Wr / s) == Wo and residual[:, ::s, ::s, :] is what is added, read in place (mega_conv2d_nhwc_rs)."""
     _gpu(x, w, scale, bias, residual)
+    if residual_stride != 1:
+        return _conv1x1_strided_residual(x, w, scale, bias, residual, int(residual_stride), relu, out_dtype, out, stride, pad, dil, ksplit)
     lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout, R, S, Cin2 = w.shape
@@ -185,6 +189,33 @@ def conv2d_nhwc(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil
                                  _stream())
     _pe(_tok)
     _lib.check(rc, "mega_conv2d_nhwc")
+    return out
+
+
+def _conv1x1_strided_residual(x, w, scale, bias, residual, rs, relu, out_dtype, out, stride, pad, dil, ksplit):
+    lib = _lib.load()
+    N, H, W, Cin = x.shape
+    Cout, R, S, Cin2 = w.shape
+    assert rs > 1 and residual is not None and (R, S, stride, pad, dil) == (1, 1, 1, 0, 1) and ksplit is None
+    assert Cin == Cin2 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype and x.dtype in _HALF
+    assert out_dtype is None or out_dtype == x.dtype
+    Hr, Wr = residual.shape[1:3]
+    assert residual.dtype == x.dtype and residual.is_contiguous() and residual.shape[0] == N and residual.shape[3] == Cout
+    assert -(-Hr // rs) == H and -(-Wr // rs) == W, "residual[:, ::s, ::s] must have the output's size"
+    if out is None:
+        out = torch.empty((N, H, W, Cout), dtype=x.dtype, device=x.device)
+    else:
+        assert out.dtype == x.dtype and out.shape == (N, H, W, Cout) and out.is_contiguous()
+    for v in (scale, bias):
+        assert v is None or (v.dtype == torch.float32 and v.numel() == Cout and v.is_contiguous())
+    if max(t.numel() * 2 for t in (x, w, out, residual)) >= 0x7FF00000:
+        raise ValueError("conv2d_nhwc: operand of 2 GiB or more; the kernels use 32-bit buffer offsets")
+    _tok = _pb("igemm8s_%s_rs" % {torch.bfloat16: "bf16", torch.float16: "f16"}[x.dtype], 2.0 * N * H * W * Cout * Cin,
+               (x.numel() + w.numel() + 2 * out.numel()) * 2.0, detail="%dx%dx%d (1x1, residual stride %d)" % (N * H * W, Cout, Cin, rs))
+    rc = lib.mega_conv2d_nhwc_rs(_ptr(x), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin, Cout,
+                                 int(relu), Cout, Cout, Hr, Wr, rs, _dt(x), _stream())
+    _pe(_tok)
+    _lib.check(rc, "mega_conv2d_nhwc_rs")
     return out
 
 
@@ -293,10 +324,12 @@ def flow_level_assemble(skip, flow, w_up, b_up, out, C):
     return out
 
 
-def bottleneck64(x, w1, s1, b1, w2, s2, b2, w3, s3, b3):
+def bottleneck64(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, subsample=False):
     """The fused identity bottleneck 256 -> 64 -> 64 (3x3) -> 256 (layer1 blocks 1, 2): x NHWC bf16 [N,H,W,256] ->
     relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + x) in one persistent kernel; same bits as the three conv2d_nhwc
-    launches.  w1 [64,1,1,256], w2 [64,3,3,64], w3 [256,1,1,64] (OHWI bf16), s / b f32 FrozenBN scale / bias."""
+    launches.  w1 [64,1,1,256], w2 [64,3,3,64], w3 [256,1,1,64] (OHWI bf16), s / b f32 FrozenBN scale / bias.
+    subsample: the even pixels only -- y[:, ::2, ::2, :] as a contiguous [N,ceil(H/2),ceil(W/2),256] tensor, same bits (for a
+    block whose only reader is a stride-2 1x1 conv: conv2 / conv3 / the residual / the stores run on a quarter of the pixels)."""
     _gpu(x, w1, s1, b1, w2, s2, b2, w3, s3, b3)
     lib = _lib.load()
     N, H, W, C = x.shape
@@ -308,8 +341,16 @@ def bottleneck64(x, w1, s1, b1, w2, s2, b2, w3, s3, b3):
         assert v.dtype == torch.float32 and v.numel() == n and v.is_contiguous()
     if x.numel() * 2 >= 0x7FF00000:
         raise ValueError("bottleneck64: operand of %.2f GiB; 32-bit buffer offsets (< 2 GiB)" % (x.numel() * 2 / 2.0 ** 30))
-    out = torch.empty_like(x)
     px = float(N * H * W)
+    if subsample:
+        out = torch.empty((N, (H + 1) // 2, (W + 1) // 2, 256), dtype=x.dtype, device=x.device)
+        _tok = _pb("bneck64_fused_even", 2.0 * px * (256 * 64 + (576 * 64 + 64 * 256) / 4.0), px * 512.0 + out.numel() * 2.0)
+        rc = lib.mega_bottleneck64_even_fwd_dt(_ptr(x), _ptr(w1), _ptr(s1), _ptr(b1), _ptr(w2), _ptr(s2), _ptr(b2), _ptr(w3),
+                                               _ptr(s3), _ptr(b3), _ptr(out), N, H, W, _dt(x), _stream())
+        _pe(_tok)
+        _lib.check(rc, "mega_bottleneck64_even_fwd_dt")
+        return out
+    out = torch.empty_like(x)
     _tok = _pb("bneck64_fused", 2.0 * px * (256 * 64 + 576 * 64 + 64 * 256), px * 1024.0)
     rc = lib.mega_bottleneck64_fwd_dt(_ptr(x), _ptr(w1), _ptr(s1), _ptr(b1), _ptr(w2), _ptr(s2), _ptr(b2), _ptr(w3), _ptr(s3),
                                       _ptr(b3), _ptr(out), N, H, W, _dt(x), _stream())
