@@ -38,8 +38,6 @@ SOURCES = {
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
-if os.environ.get("MEGA_BUILD_EXPERIMENTS") == "1":      # tools/gpu/ablate8.py: igemm8 ablation / timeline variants
-    BASE_FLAGS.append("-DMEGA_EXPERIMENTS")
 
 
 def _probe_flags(flags):

@@ -491,8 +491,8 @@ enum { KERNEL_TILE = 0,       // igemm_kernel<.., bm, bn> (this file): register-
        KERNEL_IGEMM8 = 8 };   // igemm8.hip, matrix class
 struct ConvPlan { int kernel, bm, bn; };
 
-// THE dispatch rule: conv2d_impl launches what this returns and mega_conv2d_nhwc_plan_ex reports it.  half: 16-bit
-// operands (bf16 / f16; false: f32).  p.ksplit must be set: the launch passes its own count; the report has no ksplit argument
+// THE dispatch rule: conv2d_impl and mega_conv2d_nhwc_subpixel launch what this returns and mega_conv2d_nhwc_plan_ex reports
+// it.  half: 16-bit operands (bf16 / f16; false: f32).  p.ksplit must be set: the launch passes its own count; the report has no ksplit argument
 // and assumes choose_ksplit(K), which is what mega_conv2d_nhwc_ws launches with (a mega_conv2d_nhwc_ks launch with another
 // count can land elsewhere: ksplit scales the tile counts below).
 // MEGA_IGEMM_TILE (experiments / tests; read on every call) forces "BMxBN" register-staged tiles or igemm8 "8:256" / "8:192";
@@ -504,10 +504,23 @@ struct ConvPlan { int kernel, bm, bn; };
 // keep >= ~1.5 rounds of blocks over the 256 CUs.
 inline ConvPlan plan_conv(const ConvParams& p, bool half, bool f32_out) {
   const char* force = getenv("MEGA_IGEMM_TILE");
-  if (!force && half && !f32_out && mega_conv64_supports(p, 0)) return {KERNEL_CONV64, 256, 64};
   const int M = p.M, Cout = p.Cout, K = p.K, z = p.ksplit;
+  const long b256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z, b128 = (long)cdiv(M, 128) * cdiv(Cout, 128) * z;
+  const long b12864 = (long)cdiv(M, 128) * cdiv(Cout, 64) * z;
   int bm = 0, bn = 0;
   bool want8 = false;
+  if (p.ps) {
+    // The sub-pixel read-out (mega_conv2d_nhwc_subpixel; Cout % 64 == 0) is the tiles' vector path, whole tiles of columns only:
+    // igemm8 from half a round of its tiles when Cout is a multiple of 256 (same K order, same MFMA: the same bits as the
+    // register-staged tiles), else the register-staged tiles up to 128 x 128.  MEGA_IGEMM_TILE forces no size here; set to
+    // anything, it keeps the launch off igemm8.
+    bm = igemm8_rows(M, Cout, 1, &want8);
+    if (!force && half && z == 1 && Cout % 256 == 0 && mega_igemm8_supports(p) && want8) return {KERNEL_IGEMM8, bm, 256};
+    if (b128 >= 384 && Cout % 128 == 0) return {KERNEL_TILE, 128, 128};
+    if (b12864 >= 384) return {KERNEL_TILE, 128, 64};
+    return {KERNEL_TILE, 64, 64};
+  }
+  if (!force && half && !f32_out && mega_conv64_supports(p, 0)) return {KERNEL_CONV64, 256, 64};
   if (conv_res_strided(p)) {           // the strided residual read exists in igemm8's epilogue only: whatever the launch's size
     bm = igemm8_rows(M, Cout, z);      // (its launcher refuses what that epilogue does not serve)
     if (force) sscanf(force, "8:%d", &bm);
@@ -523,15 +536,14 @@ inline ConvPlan plan_conv(const ConvParams& p, bool half, bool f32_out) {
     if (!(half && mega_igemm8_supports(p))) return {KERNEL_TILE, 128, 128};     // a shape igemm8 cannot take
     return {mega_igemm8_streaming(p.R * p.S, K) && z == 1 ? KERNEL_IGEMM8S : KERNEL_IGEMM8, bm, 256};
   }
-  const long b256 = (long)cdiv(M, 256) * cdiv(Cout, 256) * z, b128 = (long)cdiv(M, 128) * cdiv(Cout, 128) * z;
-  const long b12864 = (long)cdiv(M, 128) * cdiv(Cout, 64) * z;
   if (K >= 8192 && Cout >= 1024 && b256 >= 700) return {KERNEL_TILE, 256, 256};
   if (Cout > 64 && b128 >= 384) return {KERNEL_TILE, 128, 128};
   if (b12864 >= 384) return {KERNEL_TILE, 128, 64};
   return {KERNEL_TILE, 64, 64};
 }
 
-template <typename T, typename OT>
+// PS: the launch has the sub-pixel output (p.ps): igemm_kernel's PS instantiations, the three tiles plan_conv gives such a launch
+template <typename T, typename OT, bool PS = false>
 int launch_plan(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
   int rc = MEGA_ERR_ARG;
   if constexpr (sizeof(T) == 2) {      // (plan_conv sends 16-bit operands only to these)
@@ -539,11 +551,11 @@ int launch_plan(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
     if (pl.kernel == KERNEL_IGEMM8 || pl.kernel == KERNEL_IGEMM8S) rc = mega_igemm8_launch(p, pl.bm, sizeof(OT) == 4, Half16<T>::CODE, st);
   }
   if (pl.kernel == KERNEL_TILE) {
-    if (pl.bm == 256 && pl.bn == 256) rc = launch<T, OT, 256, 256>(p, st);
-    else if (pl.bm == 256 && pl.bn == 128) rc = launch<T, OT, 256, 128>(p, st);
-    else if (pl.bm == 128 && pl.bn == 128) rc = launch<T, OT, 128, 128>(p, st);
-    else if (pl.bm == 128 && pl.bn == 64) rc = launch<T, OT, 128, 64>(p, st);
-    else rc = launch<T, OT, 64, 64>(p, st);
+    if (!PS && pl.bm == 256 && pl.bn == 256) rc = launch<T, OT, 256, 256>(p, st);
+    else if (!PS && pl.bm == 256 && pl.bn == 128) rc = launch<T, OT, 256, 128>(p, st);
+    else if (pl.bm == 128 && pl.bn == 128) rc = launch<T, OT, 128, 128, PS>(p, st);
+    else if (pl.bm == 128 && pl.bn == 64) rc = launch<T, OT, 128, 64, PS>(p, st);
+    else rc = launch<T, OT, 64, 64, PS>(p, st);
   }
   if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<T, OT>(p, st);
   return rc;
@@ -594,7 +606,38 @@ struct ResGeom { int H, W, stride; };      // the residual as pixels (stride y, 
 static int conv2d_impl(const void* in, const void* w, const float* scale, const float* bias,
                        const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
                        int R, int S, int stride, int pad, int dil, int relu, int ldo, int ldr,
-                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream, ResGeom rg = {0, 0, 0});
+                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream, ResGeom rg = {0, 0, 0}) {
+  mega_clear_error();
+  if (!in || !w || !out) return MEGA_ERR_ARG;
+  if (in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
+  if (Cin % (in_dtype == MEGA_F32 ? 32 : 64) != 0 || (out_dtype != in_dtype && out_dtype != MEGA_F32)) return MEGA_ERR_ARG;
+  ConvParams p = {};
+  if (conv_geometry(p, N, H, W, Cin, Cout, R, S, stride, pad, dil, Cin, in_dtype == MEGA_F32 ? 4 : 2, 0xFFFFFFF0ull) != MEGA_OK) return MEGA_ERR_ARG;
+  p.in = in; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.out = out;
+  p.ldo = ldo > 0 ? ldo : Cout;
+  p.ldr = ldr > 0 ? ldr : Cout;
+  p.relu = relu;
+  if (rg.stride > 1) {      // (igemm8's launcher checks the rest: plan_conv sends every such launch there)
+    if (!residual || in_dtype == MEGA_F32 || out_dtype != in_dtype || ws || ksplit > 0 || rg.H <= 0 || rg.W <= 0) return MEGA_ERR_ARG;
+    p.rs_H = rg.H; p.rs_W = rg.W; p.rs_stride = rg.stride;
+  }
+  if (ksplit > 0 || ws) {   // with a workspace the K range of long-K layers is split (mega_conv2d_nhwc_workspace_bytes)
+    const int z = ksplit > 0 ? clamp_ksplit(p.K, in_dtype, ksplit) : choose_ksplit(p.K);
+    if (z > 1) {
+      if (!ws) return MEGA_ERR_ARG;
+      if (ws_bytes < (size_t)z * p.M * Cout * sizeof(float)) return MEGA_ERR_ARG;
+      p.ksplit = z;
+      p.partial = (float*)ws;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool f32_out = out_dtype == MEGA_F32;
+  const ConvPlan pl = plan_conv(p, in_dtype != MEGA_F32, f32_out);
+  return dispatch_elem(in_dtype, [&](auto tag) -> int {      // (the same kernels instantiated per operand type)
+    using T = decltype(tag);
+    return f32_out ? launch_plan<T, float>(p, pl, st) : launch_plan<T, T>(p, pl, st);
+  });
+}
 
 extern "C" int mega_conv2d_nhwc_ws(const void* in, const void* w, const float* scale, const float* bias,
                                    const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
@@ -614,41 +657,6 @@ extern "C" int mega_conv2d_nhwc_ks(const void* in, const void* w, const float* s
   if (ksplit < 1) return MEGA_ERR_ARG;
   return conv2d_impl(in, w, scale, bias, residual, out, N, H, W, Cin, Cout, R, S, stride, pad, dil, relu, ldo, ldr, in_dtype,
                      out_dtype, ws, ws_bytes, ksplit, stream);
-}
-
-static int conv2d_impl(const void* in, const void* w, const float* scale, const float* bias,
-                       const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
-                       int R, int S, int stride, int pad, int dil, int relu, int ldo, int ldr,
-                       int in_dtype, int out_dtype, void* ws, size_t ws_bytes, int ksplit, void* stream, ResGeom rg) {
-  mega_clear_error();
-  if (!in || !w || !out) return MEGA_ERR_ARG;
-  if (in_dtype != MEGA_F32 && in_dtype != MEGA_BF16 && in_dtype != MEGA_F16) return MEGA_ERR_ARG;
-  if (Cin % (in_dtype == MEGA_F32 ? 32 : 64) != 0 || (out_dtype != in_dtype && out_dtype != MEGA_F32)) return MEGA_ERR_ARG;
-  ConvParams p = {};
-  if (conv_geometry(p, N, H, W, Cin, Cout, R, S, stride, pad, dil, Cin, in_dtype == MEGA_F32 ? 4 : 2, 0xFFFFFFF0ull) != MEGA_OK) return MEGA_ERR_ARG;
-  p.in = in; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.out = out;
-  p.ldo = ldo > 0 ? ldo : Cout;
-  p.ldr = ldr > 0 ? ldr : Cout;
-  p.relu = relu;
-  if (rg.stride > 1) {      // (igemm8's launcher checks the rest: plan_conv sends every such launch there)
-    if (!residual || in_dtype == MEGA_F32 || out_dtype != in_dtype || ws || ksplit > 0 || rg.H <= 0 || rg.W <= 0) return MEGA_ERR_ARG;
-    conv_rs_H(p) = rg.H; conv_rs_W(p) = rg.W; conv_rs_stride(p) = rg.stride;
-  }
-  if (ksplit > 0 || ws) {   // with a workspace the K range of long-K layers is split (mega_conv2d_nhwc_workspace_bytes)
-    const int z = ksplit > 0 ? clamp_ksplit(p.K, in_dtype, ksplit) : choose_ksplit(p.K);
-    if (z > 1) {
-      if (!ws) return MEGA_ERR_ARG;
-      if (ws_bytes < (size_t)z * p.M * Cout * sizeof(float)) return MEGA_ERR_ARG;
-      p.ksplit = z;
-      p.partial = (float*)ws;
-    }
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool f32_out = out_dtype == MEGA_F32;
-  const ConvPlan pl = plan_conv(p, in_dtype != MEGA_F32, f32_out);
-  if (in_dtype == MEGA_BF16) return f32_out ? launch_plan<bf16_t, float>(p, pl, st) : launch_plan<bf16_t, bf16_t>(p, pl, st);
-  if (in_dtype == MEGA_F16) return f32_out ? launch_plan<f16_t, float>(p, pl, st) : launch_plan<f16_t, f16_t>(p, pl, st);
-  return launch_plan<float, float>(p, pl, st);      // (IEEE half / bf16: the same kernels instantiated per operand type)
 }
 
 extern "C" int mega_conv2d_nhwc(const void* in, const void* w, const float* scale, const float* bias,
@@ -688,53 +696,29 @@ extern "C" int mega_conv2d_nhwc_subpixel(const void* in, const void* w4, const f
                                          int Cin, int C, int relu, int out_H, int out_W, int crop, int ldo, int coff, int dtype,
                                          int ksplit, void* ws, size_t ws_bytes, void* stream) {
   mega_clear_error();
-  if (!in || !w4 || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || C <= 0 || out_H <= 0 || out_W <= 0 || crop < 0 ||
-      ksplit < 1 || coff < 0)
-    return MEGA_ERR_ARG;
+  if (!in || !w4 || !out || C <= 0 || out_H <= 0 || out_W <= 0 || crop < 0 || ksplit < 1 || coff < 0) return MEGA_ERR_ARG;
   if (dtype != MEGA_F32 && dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   const size_t esz = dtype == MEGA_F32 ? 4 : 2;
   const int ove = (int)(16 / esz);
   if (Cin % (dtype == MEGA_F32 ? 32 : 64) != 0 || C % ove != 0 || ldo % ove != 0 || coff % ove != 0 || coff + C > ldo) return MEGA_ERR_ARG;
   ConvParams p = {};
+  if (conv_geometry(p, N, H, W, Cin, 4 * C, 2, 2, 1, 1, 1, Cin, esz, 0xFFFFFFF0ull) != MEGA_OK) return MEGA_ERR_ARG;   // Ho = H + 1, K = 4 Cin
+  if ((size_t)N * out_H * out_W * ldo * esz >= 0x7FF00000ull) return MEGA_ERR_ARG;
+  // (the sub-pixel read-out is the tiles' vector path: whole tiles of columns only)
+  if (p.Cout % 64 != 0) return MEGA_ERR_ARG;
   p.in = in; p.w = w4; p.scale = nullptr; p.bias = bias4; p.res = nullptr; p.out = out;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = 4 * C; p.R = 2; p.S = 2; p.stride = 1; p.pad = 1; p.dil = 1;
-  p.Ho = H + 1; p.Wo = W + 1;
-  p.M = N * p.Ho * p.Wo;
-  p.K = 4 * Cin;
   p.ldo = ldo; p.ldr = ldo; p.relu = relu;
   p.ps = 1; p.ps_H = out_H; p.ps_W = out_W; p.ps_C = C; p.ps_crop = crop; p.ps_coff = coff;
-  const size_t ib = (size_t)N * H * W * Cin * esz, wb = (size_t)p.Cout * p.K * esz;
-  if (ib >= 0xFFFFFFF0ull || wb >= 0xFFFFFFF0ull || (size_t)N * out_H * out_W * ldo * esz >= 0x7FF00000ull) return MEGA_ERR_ARG;
-  p.in_bytes = (unsigned)ib;
-  p.w_bytes = (unsigned)wb;
   p.ksplit = clamp_ksplit(p.K, dtype, ksplit);
-  p.partial = nullptr;
   if (p.ksplit > 1) {
     if (!ws || ws_bytes < (size_t)p.ksplit * p.M * p.Cout * sizeof(float)) return MEGA_ERR_ARG;
     p.partial = (float*)ws;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const long b128 = (long)cdiv(p.M, 128) * cdiv(p.Cout, 128) * p.ksplit, b12864 = (long)cdiv(p.M, 128) * cdiv(p.Cout, 64) * p.ksplit;
-  // (the sub-pixel read-out is the tiles' vector path: whole tiles of columns only)
-  if (p.Cout % 64 != 0) return MEGA_ERR_ARG;
-  // large launches on the LDS-DMA tiles (igemm8.hip, ABL = 6 = the same read-out there): plan_conv's rule for whole tiles of
-  // columns -- Cout a multiple of 256 and at least half a round of tiles; same K order, same MFMA: the same bits as the
-  // register-staged tiles
-  if (dtype != MEGA_F32 && p.ksplit == 1 && p.Cout % 256 == 0 && !getenv("MEGA_IGEMM_TILE") && mega_igemm8_supports(p)) {
-    bool half_round;
-    const int rows = igemm8_rows(p.M, p.Cout, 1, &half_round);
-    if (half_round) return mega_igemm8_launch(p, rows, 0, dtype, st);
-  }
-  const int tile = (b128 >= 384 && p.Cout % 128 == 0) ? 0 : (b12864 >= 384 ? 1 : 2);     // (plan_conv's rule for the register-staged tiles)
-  auto go = [&](auto tag) -> int {
-    typedef decltype(tag) T;
-    int rc = tile == 0 ? launch<T, T, 128, 128, true>(p, st) : (tile == 1 ? launch<T, T, 128, 64, true>(p, st) : launch<T, T, 64, 64, true>(p, st));
-    if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<T, T>(p, st);
-    return rc;
-  };
-  if (dtype == MEGA_BF16) return go(bf16_t{});
-  if (dtype == MEGA_F16) return go(f16_t{});
-  return go(float{});
+  const ConvPlan pl = plan_conv(p, dtype != MEGA_F32, false);
+  return dispatch_elem(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return launch_plan<T, T, true>(p, pl, (hipStream_t)stream);
+  });
 }
 
 // Split-precision activation planes (igemm_params.h, igemm8.hip SP kernels).  An f32 activation x [N,H,W,C] lives in HBM as

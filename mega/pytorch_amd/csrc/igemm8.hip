@@ -24,8 +24,6 @@
 //   [MFMA segment with the phase's two DMA issues in the MFMA shadow] barrier; wave group 1 (waves 4-7, one per SIMD like group 0) runs one barrier behind group 0.
 //   RAW: the wait that retires a half-tile sits before the barrier that ends the phase BEFORE the one that reads it
 //   (for both groups); WAR: see the schedule table in DESIGN.md section 3.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "launch.h"
@@ -50,9 +48,11 @@ struct KPos {
   unsigned uni;                        // ((dh * W + dw) * Cin + kc) * 2 bytes
 };
 
-// ABL != 0: timing-only ablations for tools/gpu (1: no fragment ds_reads in the loop, 2: no DMA in the loop, 3: no MFMA);
-// results are garbage by construction.  Only ABL = 0 is instantiated unless the library is built with
-// -DMEGA_EXPERIMENTS (see mega_igemm8_launch).
+// EPI: the epilogue mode.  An int with these values because the template arguments are part of every kernel's symbol, which
+// the profiles and DESIGN.md are keyed by (older records call this parameter ABL: its values 1-5 were timing probes, since removed).
+constexpr int EPI_PLAIN = 0;         // rows [M][ldo] (+ residual rows [M][ldr]); with SP, split-precision planes
+constexpr int EPI_SUBPIXEL = 6;      // the sub-pixel scatter of mega_conv2d_nhwc_subpixel (igemm_params.h ps_*)
+constexpr int EPI_STRIDED_RES = 7;   // the residual read at a pixel stride, mega_conv2d_nhwc_rs (igemm_params.h rs_*)
 // CLS: launch class, part of the symbol only (the code is the same): 0 = matrix-core-bound layers (3x3 convs and every
 // layer with more than 8 K-tiles), 1 = streaming layers (1x1 convs / linears with K <= 512: at most 8 K-tiles per output
 // tile, so prologue, epilogue and the operand fetch set their time -- layer3's conv3, res5's conv3, layer2's 1x1s).  The
@@ -61,25 +61,6 @@ struct KPos {
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
-// ABL == 5: whole-tile timeline of EVERY block (waves 0 and 4, one per MFMA group): 16 u64 slots per wave in p.partial
-// (tools/gpu/timeline8.py): s_memtime (shader cycles) at 0 entry, 1 K loop starts, 2 K loop done, 3 + 2s slab s staged,
-// 4 + 2s slab s stores issued, 11 stores acknowledged; 12 = HW_ID | XCC_ID << 32; 13 / 14 = s_memrealtime (100 MHz) at
-// entry / end.  The results stay correct.
-#define MEGA_TS(k)                                                                                                      \
-  do {                                                                                                                  \
-    if (ABL == 5 && (wave & 3) == 0) {                                                                                  \
-      const unsigned long long tt = __builtin_amdgcn_s_memtime();                                                       \
-      if (lane == 0) reinterpret_cast<unsigned long long*>(p.partial)[((size_t)blockIdx.x * 2 + (wave >> 2)) * 16 + (k)] = tt; \
-    }                                                                                                                   \
-  } while (0)
-#define MEGA_TS_RT(k)                                                                                                   \
-  do {                                                                                                                  \
-    if (ABL == 5 && (wave & 3) == 0) {                                                                                  \
-      const unsigned long long tt = __builtin_amdgcn_s_memrealtime();                                                   \
-      if (lane == 0) reinterpret_cast<unsigned long long*>(p.partial)[((size_t)blockIdx.x * 2 + (wave >> 2)) * 16 + (k)] = tt; \
-    }                                                                                                                   \
-  } while (0)
-
 // SP != 0: split-precision activation planes (igemm_params.h: ldi, kwrap, split_out, split residual) -- its own symbols, the
 // plain kernels' code does not change.
 __device__ __forceinline__ int fast_div(int n, unsigned mg, unsigned sh) {   // n / d for 0 <= n < 2^31 (launch8 computes mg, sh)
@@ -87,7 +68,7 @@ __device__ __forceinline__ int fast_div(int n, unsigned mg, unsigned sh) {   // 
 }
 
 // HT: the 16-bit operand type (bf16_t, or f16_t = IEEE half: round 6) of in / w / residual; OT = HT or float.
-template <typename OT, int MF1, int CLS = 0, int ABL = 0, int SP = 0, typename HT = bf16_t>
+template <typename OT, int MF1, int CLS, int EPI, int SP, typename HT>
 __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   static_assert(sizeof(OT) == 4 || std::is_same<OT, HT>::value, "16-bit outputs have the operands' type");
   constexpr int BM = 128 + 64 * MF1;
@@ -100,8 +81,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  MEGA_TS(0);
-  MEGA_TS_RT(13);
 
   // ---- XCD-aware block -> tile map (bijective for any grid size): the blocks of one XCD walk N first, so they share
   //      A row panels in that XCD's L2
@@ -183,9 +162,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   unsigned char* const wbase = smem + wave * 1024;
   // `live` = the tile exists (tiles past the end of K are still "issued", with every lane out of range: the DMA
   // writes zeros into a dead slot and the vmcnt bookkeeping stays uniform).  Pure data flow, no branches.
-  bool in_loop = false;
   auto issue_A1 = [&](int i, int u, int par, const KPos& s, bool live) {     // one 1-KiB piece per wave
-    if (ABL == 2 && in_loop) return;
     const unsigned dead = live ? 0u : OOB;
     const int r = i * 2 + u;
     const int hi = a_hi0[r] + s.dh, wi = a_wi0[r] + s.dw;
@@ -194,7 +171,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(wbase + slot_a(i, par) + u * 8192), 16, off, 0, 0, 0);
   };
   auto issue_B1 = [&](int j, int u, int par, int tile, bool live) {
-    if (ABL == 2 && in_loop) return;
     const unsigned dead = live ? 0u : OOB;
     const unsigned kb = (unsigned)((kt0 + tile) * 128);
     const unsigned off = (b_off[j * 2 + u] + kb) | dead;         // b_off = OOB for rows past Cout: stays out of range
@@ -236,21 +212,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   // not know these are asynchronous, so each batch is followed (after the barrier) by an explicit lgkmcnt(0) and a
   // scheduling barrier before the first MFMA that consumes it.
   u32x4_t af[2][4], b0f[4], b1f[4];
-  // ABL == 4: s_memtime stamps of block 0 at every segment boundary (timeline experiments, tools/gpu/ablate8.py)
-  __shared__ unsigned long long tr_buf[ABL == 4 ? 8 * 96 : 1];
-  int tr_n = 0;
-#define MEGA_STAMP()                                                                                   \
-  do {                                                                                                 \
-    if (ABL == 4 && blockIdx.x == 0 && tr_n < 96) {                                                    \
-      const unsigned long long tt = __builtin_amdgcn_s_memtime();                                      \
-      if (lane == 0) tr_buf[wave * 96 + tr_n] = tt;                                                    \
-      ++tr_n;                                                                                          \
-    }                                                                                                  \
-  } while (0)
-#define MEGA_LDS_RD(dst, addr, imm)                                                                          \
-  do {                                                                                                       \
-    if (ABL != 1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory"); \
-  } while (0)
+#define MEGA_LDS_RD(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
 #define MEGA_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #define MEGA_WAIT_LDS()                                   \
   do {                                                    \
@@ -267,13 +229,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
 // m = lane & 31 and, for each r >> 2, FOUR CONSECUTIVE channels n = 8 (r >> 2) + 4 (lane >> 5) + (r & 3) -- so the epilogue
 // stages a fragment with 4 ds_write_b128 instead of 16 ds_write_b32 (its staging was LDS store-issue bound: 1.4 k cycles
 // per slab).  Same products, same K order per output element: the same bits as the (activation, weight) operand order.
-#define MEGA_MMA(acc_, a_, b_)                                                                                          \
-  do {                                                                                                                  \
-    if (ABL != 3)                                                                                                       \
-      acc_ = Half16<HT>::mfma32(b_, a_, acc_);                                                                          \
-    else                                                                                                                \
-      asm volatile("" ::"v"(a_), "v"(b_));                                                                              \
-  } while (0)
+#define MEGA_MMA(acc_, a_, b_) acc_ = Half16<HT>::mfma32(b_, a_, acc_)
 
   // ---- prologue: six half-tiles in the steady-state issue order
   issue_A(0, 0, pa0, ta0 < nkt); kpos_next(pa0); ++ta0;
@@ -283,23 +239,12 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   issue_A(0, 1, pa0, ta0 < nkt); kpos_next(pa0); ++ta0;
   issue_B(0, 1, tb0, tb0 < nkt); ++tb0;
   MEGA_WAIT_VM(4 + CA1);               // A0(0) B0(0) B1(0) have landed
-  in_loop = true;
-  if (ABL == 1) {                      // the ablation reads its fragments once
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(af[0][ks]) : "v"(a_rd[ks]) : "memory");
-      asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[1][ks]) : "v"(a_rd[ks]) : "memory");
-      asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(b0f[ks]) : "v"(b_rd[ks]) : "memory");
-      asm volatile("ds_read_b128 %0, %1 offset:32768" : "=v"(b1f[ks]) : "v"(b_rd[ks]) : "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
   MEGA_BAR();
   if (wr == 1) MEGA_BAR();             // group 1 runs one barrier behind group 0
 
   // Two phases per K-tile: (a) A0 x (B0, B1) = 16 MFMAs, (b) A1 x (B0, B1) = 8 MF1 MFMAs.  Timeline measurements
-  // (s_memtime stamps, tools/gpu/ablate8.py): the waves never wait for DMA data; what stretches a K-tile beyond its
-  // 2048 MFMA cycles is the ISSUE time of the load-side instructions -- an LDS-DMA costs ~110 cycles in a segment
+  // (s_memtime stamps, taken with a probe build that has since been removed): the waves never wait
+  // for DMA data; what stretches a K-tile beyond its 2048 MFMA cycles is the ISSUE time of the load-side instructions -- an LDS-DMA costs ~110 cycles in a segment
   // with ds_reads and ~45 in the shadow of MFMAs, a fragment ds_read ~20 -- so the 8 DMA pieces of a K-tile are spread
   // over all four segments so that each interval's two concurrent segments (one group's MFMA cluster, the other's
   // load segment) are as even as the hazards allow.  Per wave and K-tile t (parity t & 1):
@@ -329,13 +274,9 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
       MEGA_LDS_RD(b1f[ks], b_rd[ks], slot_b(1, par) - 4 * HALF);
     }
     issue_B1(1, 0, par ^ 1, tb1, tb1 < nkt); issue_B1(1, 1, par ^ 1, tb1, tb1 < nkt); ++tb1;
-    MEGA_STAMP();
     MEGA_WAIT_VM(6);
-    MEGA_STAMP();
     MEGA_BAR();
-    MEGA_STAMP();
     MEGA_WAIT_LDS();
-    MEGA_STAMP();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -344,9 +285,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     }
     __builtin_amdgcn_s_setprio(0);
     MEGA_SB();
-    MEGA_STAMP();
     MEGA_BAR();
-    MEGA_STAMP();
     // ================= phase b: A1 x (B1, B0)  -- the B fragments are still in registers
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -356,13 +295,9 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     issue_A1(1, 0, par ^ 1, pa1, ta1 < nkt);
     if (CA1 == 2) issue_A1(1, 1, par ^ 1, pa1, ta1 < nkt);
     kpos_next(pa1); ++ta1;
-    MEGA_STAMP();
     MEGA_WAIT_VM(CA1);
-    MEGA_STAMP();
     MEGA_BAR();
-    MEGA_STAMP();
     MEGA_WAIT_LDS();
-    MEGA_STAMP();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -376,25 +311,17 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     }
     __builtin_amdgcn_s_setprio(0);
     MEGA_SB();
-    MEGA_STAMP();
     MEGA_BAR();
-    MEGA_STAMP();
   };
 
-  MEGA_TS(1);
   const int nkt2 = (nkt + 1) & ~1;     // an odd tail tile is computed on all-zero operands (its DMAs are out of range)
   for (int t = 0; t < nkt2; t += 2) {
     tile_phases(std::integral_constant<int, 0>{});
     tile_phases(std::integral_constant<int, 1>{});
   }
-  if (ABL == 4 && blockIdx.x == 0 && p.partial) {
-    __syncthreads();
-    for (int e = tid; e < 8 * 96; e += NT8) reinterpret_cast<unsigned long long*>(p.partial)[e] = tr_buf[e];
-  }
   if (wr == 0) MEGA_BAR();             // group 0 waits for group 1's last MFMA segment
   MEGA_WAIT_VM(0);                     // the out-of-range tail DMAs also write (zeros) into the LDS re-used below
   MEGA_BAR();
-  MEGA_TS(2);
 
   // ---- epilogue.  Accumulator fragment [n][m] (see MEGA_MMA): lane owns output row m = lane & 31 of its fragment and
   //      channels 8 g + 4 (lane >> 5) + (0..3), g = 0..3.  The RAW accumulators are staged through LDS as f32, one 64-row
@@ -439,14 +366,14 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
   //      residual / output planes; they have no other epilogue (launch8 refuses what does not qualify), except the raw
   //      partial sums of a split-K launch.
   const int oplanes = SP && p.split_out ? 2 : 1;       // planes of Cout columns behind each other in an output row
-  // ABL == 6 (a product instantiation, not an ablation): the sub-pixel read-out of mega_conv2d_nhwc_subpixel -- GEMM row
-  // (t, mh, mw), column (a, b, co) of a transposed conv's four phases goes to pixel (2 mh + a - crop, 2 mw + b - crop), channel
-  // ps_coff + co of an NHWC tensor [N][ps_H][ps_W][ldo] (igemm_params.h); the launcher admits only what this path serves
-  constexpr bool PS = ABL == 6;
-  // ABL == 7 (a product instantiation too): the residual read at a pixel stride (igemm_params.h rs_*; mega_conv2d_nhwc_rs) -- the
-  // residual row of GEMM row (t, y, x) is pixel (s y, s x) of [N][rs_H][rs_W][ldr], formed by the prologue's magic division.
-  // The launcher admits only what the fast path serves (16-bit output, Cout % 256 == 0, no split-K, a residual tensor below 2 GiB).
-  constexpr bool RS = ABL == 7;
+  // The sub-pixel read-out of mega_conv2d_nhwc_subpixel -- GEMM row (t, mh, mw), column (a, b, co) of a transposed conv's four
+  // phases goes to pixel (2 mh + a - crop, 2 mw + b - crop), channel ps_coff + co of an NHWC tensor [N][ps_H][ps_W][ldo]
+  // (igemm_params.h); the launcher admits only what this path serves
+  constexpr bool PS = EPI == EPI_SUBPIXEL;
+  // The residual read at a pixel stride (igemm_params.h rs_*; mega_conv2d_nhwc_rs) -- the residual row of GEMM row (t, y, x) is
+  // pixel (s y, s x) of [N][rs_H][rs_W][ldr], formed by the prologue's magic division.  The launcher admits only what the fast
+  // path serves (16-bit output, Cout % 256 == 0, no split-K, a residual tensor below 2 GiB).
+  constexpr bool RS = EPI == EPI_STRIDED_RES;
   const size_t out_elems = PS ? (size_t)p.N * p.ps_H * p.ps_W * p.ldo : (size_t)(p.M - 1) * p.ldo + (size_t)oplanes * p.Cout;
   const bool fast = vec_ok && p.ksplit == 1 && (SP ? p.Cout % OVE == 0 : n0 + BN <= p.Cout) && (res == nullptr || sizeof(OT) == 2 || SP) &&
                     out_elems * sizeof(OT) < 0x7FF00000ull &&
@@ -455,7 +382,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
         p.out, 0, (int)(out_elems * sizeof(OT)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(p.res ? p.res : p.out), 0, res ? (int)(((size_t)(RS ? p.N * conv_rs_H(p) * conv_rs_W(p) - 1 : p.M - 1) * p.ldr + (size_t)(SP ? 2 : 1) * p.Cout) * 2) : 0, 0x00020000);
+        const_cast<void*>(p.res ? p.res : p.out), 0, res ? (int)(((size_t)(RS ? p.N * p.rs_H * p.rs_W - 1 : p.M - 1) * p.ldr + (size_t)(SP ? 2 : 1) * p.Cout) * 2) : 0, 0x00020000);
     constexpr int RSTEP = NT8 / VPR;                   // slab rows between a thread's consecutive vectors
     const int row0 = tid / VPR, ncol = n0 + (tid % VPR) * OVE;
     const unsigned cmask = SP && ncol >= p.Cout ? OOB : 0u;      // (SP) this thread's columns do not exist: loads give 0, stores are dropped
@@ -521,7 +448,7 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
             const int m = slab_m(i, f, it);
             const int t = fast_div(m, p.mg_howo, p.sh_howo), rem = m - t * (p.Ho * p.Wo);
             const int y = fast_div(rem, p.mg_wo, p.sh_wo), x = rem - y * p.Wo;
-            const unsigned off = m < p.M ? (unsigned)(((t * conv_rs_H(p) + y * conv_rs_stride(p)) * conv_rs_W(p) + x * conv_rs_stride(p)) * p.ldr + ncol) * 2u : OOB;
+            const unsigned off = m < p.M ? (unsigned)(((t * p.rs_H + y * p.rs_stride) * p.rs_W + x * p.rs_stride) * p.ldr + ncol) * 2u : OOB;
             dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0);
           } else {
             dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, (unsigned)(slab_m(i, f, it) * p.ldr + ncol) * 2u, 0, 0);
@@ -558,7 +485,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
           stage(csb, i, f);
           MEGA_WAIT_LDS();
           MEGA_BAR();
-          MEGA_TS(3 + 2 * (2 * i + f));
 #pragma unroll
           for (int it = 0; it < NIT; ++it) {
             const int row = row0 + it * RSTEP;
@@ -634,7 +560,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
           } else {
             if (HAS_RES && i == 0 && f < MF1) ldres(1, f, rr[f]);   // slab s + 2 into the registers slab s just freed
           }
-          MEGA_TS(4 + 2 * (2 * i + f));
         }
       }
     };
@@ -653,18 +578,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
         if (p.relu == 1) run(std::true_type{}, std::true_type{}, std::false_type{}); else run(std::true_type{}, std::false_type{}, std::false_type{});
       } else {
         if (p.relu == 1) run(std::false_type{}, std::true_type{}, std::false_type{}); else run(std::false_type{}, std::false_type{}, std::false_type{});
-      }
-    }
-    if (ABL == 5) {
-      MEGA_WAIT_VM(0);
-      MEGA_TS(11);
-      MEGA_TS_RT(14);
-      if ((wave & 3) == 0 && lane == 0) {
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        reinterpret_cast<unsigned long long*>(p.partial)[((size_t)blockIdx.x * 2 + (wave >> 2)) * 16 + 12] =
-            (unsigned long long)hwid | ((unsigned long long)xcc << 32);
       }
     }
     return;
@@ -766,7 +679,6 @@ __global__ __launch_bounds__(NT8, 2) void igemm8_kernel(ConvParams p) {
 #undef MEGA_MMA
 #undef MEGA_SB
 #undef MEGA_MMA_IF
-#undef MEGA_STAMP
 }
 
 // n / d == (umulhi(n, mg) + n) >> sh for every 0 <= n < 2^31 (round-up method: sh = ceil(log2 d), mg = floor(2^32 (2^sh - d) / d) + 1)
@@ -776,14 +688,63 @@ inline void magic_div(int d, unsigned& mg, unsigned& sh) {
   mg = (unsigned)((((1ull << sh) - (unsigned long long)d) << 32) / (unsigned long long)d + 1ull);
 }
 
-template <typename OT, int MF1, int CLS = 0, int ABL = 0, int SP = 0, typename HT = bf16_t>
+template <typename OT, int MF1, int CLS, int EPI, int SP, typename HT>
 int launch8(const ConvParams& p0, hipStream_t st) {
   constexpr int BM = 128 + 64 * MF1;
   ConvParams p = p0;
   magic_div(p.Ho * p.Wo, p.mg_howo, p.sh_howo);
   magic_div(p.Wo, p.mg_wo, p.sh_wo);
   const int ntm = cdiv(p.M, BM), ntn = cdiv(p.Cout, 256);
-  return launch_lds(igemm8_kernel<OT, MF1, CLS, ABL, SP, HT>, dim3(ntm * ntn, 1, p.ksplit), dim3(NT8), LDS8_ALLOC, st, p);
+  return launch_lds(igemm8_kernel<OT, MF1, CLS, EPI, SP, HT>, dim3(ntm * ntn, 1, p.ksplit), dim3(NT8), LDS8_ALLOC, st, p);
+}
+
+// Admission, one function per mode: what that mode's epilogue serves.  The SP, sub-pixel and strided-residual kernels have the
+// buffer-addressed epilogue only (the SP kernels also the raw partial sums of a split-K launch): a launch outside these rules
+// would run a kernel that writes nothing.  out_f32: the output's width, the one thing the rules take from outside ConvParams.
+// (tests/test_igemm8_admission.py pins them through the C ABI.)
+bool admit_sp(const ConvParams& p, int out_f32) {
+  const size_t oplanes = p.split_out ? 2 : 1, osz = out_f32 ? 4 : 2;
+  return p.ldi >= (p.kwrap > 0 ? p.kwrap : p.Cin) && p.ldi % 64 == 0 && (p.kwrap == 0 || (p.kwrap % 64 == 0 && p.kwrap < p.Cin && p.Cin - p.kwrap <= p.kwrap)) &&
+         p.Cout % 8 == 0 && !(p.split_out && out_f32) && p.ldo % (out_f32 ? 4 : 8) == 0 && p.ldo >= (int)oplanes * p.Cout &&
+         (!p.res || (p.ldr % 8 == 0 && p.ldr >= 2 * p.Cout)) &&
+         ((size_t)(p.M - 1) * p.ldo + oplanes * p.Cout) * osz < 0x7FF00000ull &&
+         (!p.res || ((size_t)(p.M - 1) * p.ldr + 2 * (size_t)p.Cout) * 2 < 0x7FF00000ull) &&
+         (p.ksplit == 1 || (!p.split_out && !p.res));
+}
+bool admit_subpixel(const ConvParams& p, int out_f32) {      // 16-bit in / out, no residual, no split-K
+  return !(p.sp || out_f32 || p.res || p.ksplit != 1 || p.Cout % 256 != 0 || p.ps_C % 8 != 0 || p.ldo % 8 != 0 || p.ps_coff % 8 != 0 ||
+           (size_t)p.N * p.ps_H * p.ps_W * p.ldo * 2 >= 0x7FF00000ull);
+}
+bool admit_strided_res(const ConvParams& p, int out_f32) {   // streaming class, 16-bit output
+  return !(p.sp || out_f32 || p.ksplit != 1 || !mega_igemm8_streaming(p.R * p.S, p.K) || p.stride != 1 || p.pad != 0 ||
+           p.Cout % 256 != 0 || p.ldo % 8 != 0 || p.ldr % 8 != 0 || p.ldr < p.Cout ||
+           (long)(p.Ho - 1) * p.rs_stride >= p.rs_H || (long)(p.Wo - 1) * p.rs_stride >= p.rs_W ||
+           ((size_t)(p.M - 1) * p.ldo + p.Cout) * 2 >= 0x7FF00000ull ||
+           (((size_t)p.N * p.rs_H * p.rs_W - 1) * p.ldr + p.Cout) * 2 >= 0x7FF00000ull);
+}
+
+// The instantiation table of one (operand type, mode): these kernels exist and no others.  The plain and split-precision modes
+// come in both launch classes and both output widths; the sub-pixel kernels are CLS 0 and the strided-residual kernels CLS 1
+// (what admission leaves them), with 16-bit output only.  Every mode has both tile heights: bm = 256 or 192 rows.
+template <typename HT, int EPI, int SP>
+int launch8_mode(const ConvParams& p, int bm, int out_f32, hipStream_t st) {
+  auto rows = [&](auto ot, auto cls) -> int {
+    using OT = decltype(ot);
+    constexpr int CLS = decltype(cls)::value;
+    if (bm == 256) return launch8<OT, 2, CLS, EPI, SP, HT>(p, st);
+    if (bm == 192) return launch8<OT, 1, CLS, EPI, SP, HT>(p, st);
+    return MEGA_ERR_ARG;
+  };
+  using C0 = std::integral_constant<int, 0>;
+  using C1 = std::integral_constant<int, 1>;
+  if constexpr (EPI == EPI_SUBPIXEL) {
+    return rows(HT{}, C0{});
+  } else if constexpr (EPI == EPI_STRIDED_RES) {
+    return rows(HT{}, C1{});
+  } else {
+    if (mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1) return out_f32 ? rows(float{}, C1{}) : rows(HT{}, C1{});
+    return out_f32 ? rows(float{}, C0{}) : rows(HT{}, C0{});
+  }
 }
 
 }  // namespace
@@ -793,130 +754,18 @@ int mega_igemm8_streaming(int taps, int K) { return taps == 1 && K <= 512; }
 
 int mega_igemm8_supports(const ConvParams& p) {
   // capability (a single K-tile works: the ring's second tile is then all zeros); which shapes are SENT here by default
-  // is choose_tile's policy (igemm.hip)
+  // is plan_conv's policy (igemm.hip)
   return p.Cin % 64 == 0 && p.in_bytes < 0x7FF00000u && p.w_bytes < 0x7FF00000u && (p.K >> 6) >= 1;
 }
 
+// The mode is what the launch's ConvParams say (no entry point sets sp together with ps or a strided residual: both are refused,
+// by the other mode's admission); a half_dtype that is not a 16-bit type is refused by dispatch_half.
 int mega_igemm8_launch(const ConvParams& p, int bm, int out_f32, int half_dtype, hipStream_t st) {
-  if (half_dtype == MEGA_F16 && p.sp) {  // fp16 [hi | lo] planes (conv_mode "h2"): the SP kernels on IEEE-half pairs
-    const size_t oplanes = p.split_out ? 2 : 1, osz = out_f32 ? 4 : 2;
-    const bool ok = p.ldi >= (p.kwrap > 0 ? p.kwrap : p.Cin) && p.ldi % 64 == 0 && (p.kwrap == 0 || (p.kwrap % 64 == 0 && p.kwrap < p.Cin && p.Cin - p.kwrap <= p.kwrap)) &&
-                    p.Cout % 8 == 0 && !(p.split_out && out_f32) && p.ldo % (out_f32 ? 4 : 8) == 0 && p.ldo >= (int)oplanes * p.Cout &&
-                    (!p.res || (p.ldr % 8 == 0 && p.ldr >= 2 * p.Cout)) &&
-                    ((size_t)(p.M - 1) * p.ldo + oplanes * p.Cout) * osz < 0x7FF00000ull &&
-                    (!p.res || ((size_t)(p.M - 1) * p.ldr + 2 * (size_t)p.Cout) * 2 < 0x7FF00000ull) &&
-                    (p.ksplit == 1 || (!p.split_out && !p.res));
-    if (!ok) return MEGA_ERR_ARG;
-    const bool streamf = mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1;
-    if (bm == 256 && streamf) return out_f32 ? launch8<float, 2, 1, 0, 1, f16_t>(p, st) : launch8<f16_t, 2, 1, 0, 1, f16_t>(p, st);
-    if (bm == 192 && streamf) return out_f32 ? launch8<float, 1, 1, 0, 1, f16_t>(p, st) : launch8<f16_t, 1, 1, 0, 1, f16_t>(p, st);
-    if (bm == 256) return out_f32 ? launch8<float, 2, 0, 0, 1, f16_t>(p, st) : launch8<f16_t, 2, 0, 0, 1, f16_t>(p, st);
-    if (bm == 192) return out_f32 ? launch8<float, 1, 0, 0, 1, f16_t>(p, st) : launch8<f16_t, 1, 0, 0, 1, f16_t>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (p.ps) {                          // sub-pixel read-out (mega_conv2d_nhwc_subpixel): 16-bit in / out, no residual, no split-K
-    if (p.sp || out_f32 || p.res || p.ksplit != 1 || p.Cout % 256 != 0 || p.ps_C % 8 != 0 || p.ldo % 8 != 0 || p.ps_coff % 8 != 0 ||
-        (size_t)p.N * p.ps_H * p.ps_W * p.ldo * 2 >= 0x7FF00000ull)
-      return MEGA_ERR_ARG;
-    if (half_dtype == MEGA_F16) return bm == 192 ? launch8<f16_t, 1, 0, 6, 0, f16_t>(p, st) : launch8<f16_t, 2, 0, 6, 0, f16_t>(p, st);
-    if (half_dtype == MEGA_BF16) return bm == 192 ? launch8<bf16_t, 1, 0, 6>(p, st) : launch8<bf16_t, 2, 0, 6>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (conv_res_strided(p)) {           // residual read at a pixel stride: streaming class, 16-bit output, the buffer-addressed epilogue only
-    if (p.sp || out_f32 || p.ksplit != 1 || !mega_igemm8_streaming(p.R * p.S, p.K) || p.stride != 1 || p.pad != 0 ||
-        p.Cout % 256 != 0 || p.ldo % 8 != 0 || p.ldr % 8 != 0 || p.ldr < p.Cout ||
-        (long)(p.Ho - 1) * conv_rs_stride(p) >= conv_rs_H(p) || (long)(p.Wo - 1) * conv_rs_stride(p) >= conv_rs_W(p) ||
-        ((size_t)(p.M - 1) * p.ldo + p.Cout) * 2 >= 0x7FF00000ull ||
-        (((size_t)p.N * conv_rs_H(p) * conv_rs_W(p) - 1) * p.ldr + p.Cout) * 2 >= 0x7FF00000ull)
-      return MEGA_ERR_ARG;
-    if (half_dtype == MEGA_F16) return bm == 192 ? launch8<f16_t, 1, 1, 7, 0, f16_t>(p, st) : bm == 256 ? launch8<f16_t, 2, 1, 7, 0, f16_t>(p, st) : MEGA_ERR_ARG;
-    if (half_dtype == MEGA_BF16) return bm == 192 ? launch8<bf16_t, 1, 1, 7>(p, st) : bm == 256 ? launch8<bf16_t, 2, 1, 7>(p, st) : MEGA_ERR_ARG;
-    return MEGA_ERR_ARG;
-  }
-  if (half_dtype == MEGA_F16) {        // IEEE half operands (same tiles, same launch classes)
-    const bool streamf = mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1;
-    if (bm == 256 && streamf) return out_f32 ? launch8<float, 2, 1, 0, 0, f16_t>(p, st) : launch8<f16_t, 2, 1, 0, 0, f16_t>(p, st);
-    if (bm == 192 && streamf) return out_f32 ? launch8<float, 1, 1, 0, 0, f16_t>(p, st) : launch8<f16_t, 1, 1, 0, 0, f16_t>(p, st);
-    if (bm == 256) return out_f32 ? launch8<float, 2, 0, 0, 0, f16_t>(p, st) : launch8<f16_t, 2, 0, 0, 0, f16_t>(p, st);
-    if (bm == 192) return out_f32 ? launch8<float, 1, 0, 0, 0, f16_t>(p, st) : launch8<f16_t, 1, 0, 0, 0, f16_t>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (half_dtype != MEGA_BF16) return MEGA_ERR_ARG;
-#ifdef MEGA_EXPERIMENTS
-  // Timing ablations / s_memtime timeline (tools/gpu/ablate8.py).  NOT part of the product library: this block
-  // allocates, synchronises and prints, and its kernels return garbage by construction -- it only exists in a library
-  // built with MEGA_BUILD_EXPERIMENTS=1 (mega/pytorch_amd/build.py adds -DMEGA_EXPERIMENTS).
-  static const int abl = getenv("MEGA_IGEMM8_ABLATE") ? atoi(getenv("MEGA_IGEMM8_ABLATE")) : 0;
-  if (abl && bm == 256 && !out_f32) {
-    if (abl == 1) return launch8<bf16_t, 2, 0, 1>(p, st);
-    if (abl == 2) return launch8<bf16_t, 2, 0, 2>(p, st);
-    if (abl == 3) return launch8<bf16_t, 2, 0, 3>(p, st);
-    if (abl == 5) {          // whole-tile timeline of every block -> MEGA_IGEMM8_TIMELINE_OUT (raw u64 [grid][2][16])
-      static unsigned long long* d_tr = nullptr;
-      static size_t cap = 0;
-      const size_t nblk = (size_t)cdiv(p.M, 256) * cdiv(p.Cout, 256), bytes = nblk * 2 * 16 * sizeof(unsigned long long);
-      if (bytes > cap) { if (d_tr) (void)hipFree(d_tr); (void)hipMalloc(&d_tr, bytes); cap = bytes; }
-      (void)hipMemsetAsync(d_tr, 0, bytes, st);
-      ConvParams q = p;
-      q.partial = reinterpret_cast<float*>(d_tr);
-      const int rc = launch8<bf16_t, 2, 0, 5>(q, st);
-      (void)hipStreamSynchronize(st);
-      const char* path = getenv("MEGA_IGEMM8_TIMELINE_OUT");
-      if (path) {
-        unsigned long long* h = (unsigned long long*)malloc(bytes);
-        (void)hipMemcpy(h, d_tr, bytes, hipMemcpyDeviceToHost);
-        FILE* f = fopen(path, "wb");
-        if (f) { fwrite(h, 1, bytes, f); fclose(f); }
-        free(h);
-      }
-      return rc;
-    }
-    if (abl == 4) {          // timeline of block 0: 12 stamps per K-tile per wave, first 8 K-tiles
-      static unsigned long long* d_tr = nullptr;
-      if (!d_tr) (void)hipMalloc(&d_tr, 8 * 96 * sizeof(unsigned long long));
-      ConvParams q = p;
-      q.partial = reinterpret_cast<float*>(d_tr);
-      const int rc = launch8<bf16_t, 2, 0, 4>(q, st);
-      (void)hipStreamSynchronize(st);
-      static unsigned long long h[8 * 96];
-      (void)hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost);
-      static int printed = 0;
-      if (printed++ == 2) {    // third launch: warm
-        const char* names[12] = {"a:reads", "a:vmcnt", "a:bar", "a:lgkm", "a:mfma", "a:bar2", "b:reads", "b:vmcnt", "b:bar", "b:lgkm", "b:mfma", "b:bar2"};
-        for (int w = 0; w < 8; w += 4) {
-          printf("wave %d (group %d): stamp deltas (100 MHz ticks x? -> raw s_memtime units) over K-tiles 2..5\n", w, w >> 2);
-          for (int t = 2; t < 6; ++t) {
-            printf("  tile %d:", t);
-            for (int e = 0; e < 12; ++e) printf(" %s %llu", names[e], h[w * 96 + t * 12 + e] - h[w * 96 + t * 12 + e - 1]);
-            printf("  | tile total %llu\n", h[w * 96 + t * 12 + 11] - h[w * 96 + (t - 1) * 12 + 11]);
-          }
-        }
-        fflush(stdout);
-      }
-      return rc;
-    }
-  }
-#endif
-  const bool stream = mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1;
-  if (p.sp) {
-    // split-precision planes: the SP kernels have the buffer-addressed epilogue only (+ raw split-K partial sums)
-    const size_t oplanes = p.split_out ? 2 : 1, osz = out_f32 ? 4 : 2;
-    const bool ok = p.ldi >= (p.kwrap > 0 ? p.kwrap : p.Cin) && p.ldi % 64 == 0 && (p.kwrap == 0 || (p.kwrap % 64 == 0 && p.kwrap < p.Cin && p.Cin - p.kwrap <= p.kwrap)) &&
-                    p.Cout % 8 == 0 && !(p.split_out && out_f32) && p.ldo % (out_f32 ? 4 : 8) == 0 && p.ldo >= (int)oplanes * p.Cout &&
-                    (!p.res || (p.ldr % 8 == 0 && p.ldr >= 2 * p.Cout)) &&
-                    ((size_t)(p.M - 1) * p.ldo + oplanes * p.Cout) * osz < 0x7FF00000ull &&
-                    (!p.res || ((size_t)(p.M - 1) * p.ldr + 2 * (size_t)p.Cout) * 2 < 0x7FF00000ull) &&
-                    (p.ksplit == 1 || (!p.split_out && !p.res));
-    if (!ok) return MEGA_ERR_ARG;
-    if (bm == 256 && stream) return out_f32 ? launch8<float, 2, 1, 0, 1>(p, st) : launch8<bf16_t, 2, 1, 0, 1>(p, st);
-    if (bm == 192 && stream) return out_f32 ? launch8<float, 1, 1, 0, 1>(p, st) : launch8<bf16_t, 1, 1, 0, 1>(p, st);
-    if (bm == 256) return out_f32 ? launch8<float, 2, 0, 0, 1>(p, st) : launch8<bf16_t, 2, 0, 0, 1>(p, st);
-    if (bm == 192) return out_f32 ? launch8<float, 1, 0, 0, 1>(p, st) : launch8<bf16_t, 1, 0, 0, 1>(p, st);
-    return MEGA_ERR_ARG;
-  }
-  if (bm == 256 && stream) return out_f32 ? launch8<float, 2, 1>(p, st) : launch8<bf16_t, 2, 1>(p, st);
-  if (bm == 192 && stream) return out_f32 ? launch8<float, 1, 1>(p, st) : launch8<bf16_t, 1, 1>(p, st);
-  if (bm == 256) return out_f32 ? launch8<float, 2>(p, st) : launch8<bf16_t, 2>(p, st);
-  if (bm == 192) return out_f32 ? launch8<float, 1>(p, st) : launch8<bf16_t, 1>(p, st);
-  return MEGA_ERR_ARG;
+  return dispatch_half(half_dtype, [&](auto tag) -> int {
+    using HT = decltype(tag);
+    if (p.ps) return admit_subpixel(p, out_f32) ? launch8_mode<HT, EPI_SUBPIXEL, 0>(p, bm, out_f32, st) : MEGA_ERR_ARG;
+    if (conv_res_strided(p)) return admit_strided_res(p, out_f32) ? launch8_mode<HT, EPI_STRIDED_RES, 0>(p, bm, out_f32, st) : MEGA_ERR_ARG;
+    if (p.sp) return admit_sp(p, out_f32) ? launch8_mode<HT, EPI_PLAIN, 1>(p, bm, out_f32, st) : MEGA_ERR_ARG;
+    return launch8_mode<HT, EPI_PLAIN, 0>(p, bm, out_f32, st);
+  });
 }

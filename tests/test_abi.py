@@ -49,8 +49,6 @@ def test_bad_arguments_are_rejected_without_a_gpu():
 # in a shell silently changes which kernel runs, so a new one has to be added here on purpose.
 ALLOWED_GETENV = {
     "MEGA_IGEMM_TILE",            # igemm.hip: forces the conv GEMM tile (tests/test_conv_dispatch.py and the conv tests set it)
-    "MEGA_IGEMM8_ABLATE",         # igemm8.hip, inside #ifdef MEGA_EXPERIMENTS: not in the product build
-    "MEGA_IGEMM8_TIMELINE_OUT",   # igemm8.hip, inside #ifdef MEGA_EXPERIMENTS
 }
 
 
