@@ -16,7 +16,7 @@ Layout contract at the seams: feature maps are logical NCHW tensors in channels-
 There is no CPU path: modules raise if the kernels are unavailable.
 """
 import os
-from collections import OrderedDict, deque
+from collections import OrderedDict, deque, namedtuple
 
 import torch
 from torch import nn
@@ -67,29 +67,61 @@ def head_dtype(cfg):
     return d
 
 
+class ConvMode(namedtuple("ConvMode", "name compute planes operands plane_dtype plain stem_dtype")):
+    """How the frame stage's convolutions / first FC run -- one row of CONV_MODES:
+      compute      torch dtype of plain activations and weights (cfg.DTYPE)
+      planes       which activations live as [hi | lo] planes (ops.Planes): None; "all" -- every conv reads and writes them
+                   (three per bottleneck), fc0 too; "trunk" -- the residual trunk only
+      operands, plane_dtype   the operand form handed to ops.conv2d_sp / linear_sp and the planes' dtype (None: no planes)
+      plain        ops.conv2d_sp's out_mode for a plain output, the map ROIAlign / the RPN's 1x1 convs read (None: no planes)
+      stem_dtype   dtype the stem runs in (float32: the exact-f32 direct conv, which cannot read the uint8 frames itself)
+    A module built in a plain mode (planes None) takes the dtype from its input."""
+    def split(self, w_ohwi):      # f32 [Cout,R,S,C] -> the operand of an "all" mode: [Wh | Wh | Wl] ("x3") or [W | W] ("h2") per tap
+        return {"x3": ops.split_conv_weight_x3, "h2": ops.split_conv_weight_h2}[self.operands](w_ohwi)
+
+    def pack(self, conv):
+        """OIHW parameter -> the OHWI kernel operand of this mode's convs"""
+        if self.planes != "all":
+            return _pack_conv(conv, self.compute)
+        return self.split(conv.weight.detach().float().permute(0, 2, 3, 1).contiguous())
+
+
+_F32, _BF16, _F16 = torch.float32, torch.bfloat16, torch.float16
+#   "f32"   cfg.DTYPE float32: exact-f32 MFMA (the parity mode, 157 TF/s roof)
+#   "x3"    cfg.DTYPE float32 + cfg.F32_CONV "bf16x3": split-precision -- activations live as [hi | lo] bf16 planes, every conv
+#           contracts [hi | lo | hi] against [Wh | Wh | Wl] on the bf16 matrix cores with f32 accumulation (x.W to ~2^-16);
+#           the stem, the narrow RPN outputs and ROIAlign stay exact f32.  The parity mode at matrix-core rates.
+#   "bf16"  cfg.DTYPE bfloat16 (what bench.py times)
+#   "wide"  cfg.DTYPE bfloat16 + cfg.RESIDUAL_STREAM "planes": bf16 convolutions, but the residual trunk of layer1-3 / res5
+#           (resnet.py:324-344 `out += identity`, 33 + 3 times in R-101-C4) is carried as planes: a conv reads the hi plane
+#           (= the bf16 tensor it always read), conv3 adds hi + lo in f32 and writes both planes: no 8-bit rounding of the trunk
+#   "f16"   cfg.DTYPE float16 (round 6): the same kernels instantiated for IEEE half operands -- identical MFMA rate and
+#           bytes, 11 significant bits instead of 8 (1/8 of the rounding noise); activations are bounded by 65 504
+#   "h2"    cfg.DTYPE float16 + cfg.F16_CONV "x2" (round 6): the two-pass form -- activations as float16 [hi | lo] planes
+#           (x to ~2^-22), every conv / fc0 ONE fp16 GEMM over K x 2 against weights [W | W] rounded to fp16 once: exact
+#           activations x single-rounded weights at twice the fp16 mode's matrix-core work; stem, the narrow RPN outputs and
+#           ROIAlign exact f32 as in "x3"; the head is the bf16 head
+CONV_MODES = {m.name: m for m in (
+    #        name    compute planes   operands plane_dtype plain   stem_dtype
+    ConvMode("f32",  _F32,   None,    None,    None,       None,   _F32),
+    ConvMode("x3",   _F32,   "all",   "x3",    _BF16,      "f32",  _F32),
+    ConvMode("bf16", _BF16,  None,    None,    None,       None,   _BF16),
+    ConvMode("wide", _BF16,  "trunk", "hi",    _BF16,      "bf16", _BF16),
+    ConvMode("f16",  _F16,   None,    None,    None,       None,   _F16),
+    ConvMode("h2",   _F16,   "all",   "h2",    _F16,       "f32",  _F32))}
+
+
 def conv_mode(cfg):
-    """How the frame stage's convolutions / first FC run:
-      "f32"   cfg.DTYPE float32: exact-f32 MFMA (the parity mode, 157 TF/s roof)
-      "x3"    cfg.DTYPE float32 + cfg.F32_CONV "bf16x3": split-precision -- activations live as [hi | lo] bf16 planes
-              (ops.Planes), every conv contracts [hi | lo | hi] against [Wh | Wh | Wl] on the bf16 matrix cores with f32
-              accumulation (x.W to ~2^-16); the stem, the narrow RPN outputs and ROIAlign stay exact f32.  The parity mode
-              at matrix-core rates.
-      "bf16"  cfg.DTYPE bfloat16 (what bench.py times)
-      "h2"    cfg.DTYPE float16 + cfg.F16_CONV "x2" (round 6): the two-pass form -- activations as float16 [hi | lo] planes
-              (x to ~2^-22), every conv / fc0 ONE fp16 GEMM over K x 2 against weights [W | W] rounded to fp16 once:
-              exact activations x single-rounded weights at twice the fp16 mode's matrix-core work; stem, the narrow RPN
-              outputs and ROIAlign exact f32 as in "x3"; the head is the bf16 head
-      "f16"   cfg.DTYPE float16 (round 6): the same kernels instantiated for IEEE half operands -- identical MFMA rate and
-              bytes, 11 significant bits instead of 8 (1/8 of the rounding noise); activations are bounded by 65 504
-      "wide"  cfg.DTYPE bfloat16 + cfg.RESIDUAL_STREAM "planes": bf16 convolutions, but the residual trunk of layer1-3 /
-              res5 (resnet.py:324-344 `out += identity`, 33 + 3 times in R-101-C4) is carried as planes: a conv reads the
-              hi plane (= the bf16 tensor it always read), conv3 adds hi + lo in f32 and writes both planes, so the trunk is
-              never rounded to 8 bits."""
+    """name of the cfg's row of CONV_MODES"""
     if compute_dtype(cfg) == torch.float32:
         return "x3" if str(getattr(cfg, "F32_CONV", "exact")) == "bf16x3" else "f32"
     if compute_dtype(cfg) == torch.float16:
         return "h2" if str(getattr(cfg, "F16_CONV", "single")) == "x2" else "f16"
     return "wide" if str(getattr(cfg, "RESIDUAL_STREAM", "bfloat16")) == "planes" else "bf16"
+
+
+def conv_mode_of(cfg):
+    return CONV_MODES[conv_mode(cfg)]      # the cfg's ConvMode
 
 
 def _nhwc(x):
@@ -149,29 +181,6 @@ def _pack_conv(conv, dtype):
     return conv.weight.detach().permute(0, 2, 3, 1).contiguous().to(dtype)
 
 
-_PLANES3 = ("x3", "h2")          # conv modes whose EVERY conv reads / writes planes (three per bottleneck)
-
-
-def _spk(mode):
-    """conv_mode -> the x3 argument of ops.conv2d_sp: True ([hi | lo | hi] . [Wh | Wh | Wl], bf16), "h2" ([hi | lo] . [W | W],
-    float16), False (the hi plane against plain bf16 weights: mode "wide")"""
-    return {"x3": True, "h2": "h2"}.get(mode, False)
-
-
-def _plane_dtype(mode):
-    return torch.float16 if mode == "h2" else torch.bfloat16
-
-
-def _pack_conv_h2(conv, dtype=None):
-    """OIHW parameter -> the two-pass fp16 operand [Cout,R,S,2C] = [W | W] per tap (ops.conv2d_sp(x3="h2"))."""
-    return ops.split_conv_weight_h2(conv.weight.detach().float().permute(0, 2, 3, 1).contiguous())
-
-
-def _pack_conv_x3(conv, dtype=None):
-    """OIHW parameter -> split-precision operand [Cout,R,S,3C] = [Wh | Wh | Wl] per tap (ops.conv2d_sp(x3=True))."""
-    return ops.split_conv_weight_x3(conv.weight.detach().float().permute(0, 2, 3, 1).contiguous())
-
-
 class _Packed(nn.Module):
     """Modules that cache kernel-ready operands; invalidated on load_state_dict / dtype change."""
 
@@ -203,8 +212,9 @@ class Bottleneck(_Packed):
     """backbone/resnet.py:239-344 with FrozenBN, stride_in_1x1=True: three fused conv+BN(+ReLU) launches,
     the residual add + final ReLU live in conv3's epilogue."""
 
-    def __init__(self, in_channels, bottleneck_channels, out_channels, stride, dilation=1):
+    def __init__(self, in_channels, bottleneck_channels, out_channels, stride, dilation=1, mode=CONV_MODES["f32"]):
         super().__init__()
+        self.mode = mode
         self.downsample = None
         if in_channels != out_channels:
             self.down_stride = stride if dilation == 1 else 1
@@ -222,36 +232,34 @@ class Bottleneck(_Packed):
 
     def _pack(self, dtype, device):
         pk = {}
-        pack = {"x3": _pack_conv_x3, "h2": _pack_conv_h2}.get(dtype, _pack_conv)
+        pack = self.mode.pack if self.mode.planes else (lambda conv: _pack_conv(conv, dtype))
         for i in (1, 2, 3):
             s, b = getattr(self, "bn%d" % i).folded()
-            pk["w%d" % i] = pack(getattr(self, "conv%d" % i), dtype).to(device)
+            pk["w%d" % i] = pack(getattr(self, "conv%d" % i)).to(device)
             pk["s%d" % i], pk["b%d" % i] = s.to(device), b.to(device)
         if self.downsample is not None:
             s, b = self.downsample[1].folded()
-            pk["wd"] = pack(self.downsample[0], dtype).to(device)
+            pk["wd"] = pack(self.downsample[0]).to(device)
             pk["sd"], pk["bd"] = s.to(device), b.to(device)
         return pk
 
-    sp_mode = None     # "x3" / "wide" (conv_mode): set on every block by the module that owns the stage
-
     def run_sp(self, x, out_mode="planes"):
-        """The block on split-precision planes (conv_mode "x3" / "wide").  x: ops.Planes, or -- wide mode, the stem's
-        output -- a plain bf16 tensor.  -> Planes, or out_mode "f32" / "bf16": a plain tensor (the last block of res5)."""
-        x3 = _spk(self.sp_mode)
-        pk = self._packed(self.sp_mode if x3 else torch.bfloat16, x.device)
+        """The block of a planes mode (self.mode.planes).  x: ops.Planes, or -- "trunk", the stem's output -- a plain
+        tensor.  -> Planes, or out_mode = self.mode.plain: a plain tensor (the last block of res5)."""
+        m, op = self.mode, self.mode.operands
+        pk = self._packed(m.compute, x.device)
         identity = x
         if self.downsample is not None:
-            identity = ops.conv2d_sp(x, pk["wd"], pk["sd"], pk["bd"], stride=self.down_stride, out_mode="planes", x3=x3)
+            identity = ops.conv2d_sp(x, pk["wd"], pk["sd"], pk["bd"], stride=self.down_stride, out_mode="planes", operands=op)
         elif not isinstance(x, ops.Planes):
             raise ValueError("an identity block needs its input as planes")
-        if x3:
-            t = ops.conv2d_sp(x, pk["w1"], pk["s1"], pk["b1"], stride=self.stride, relu=True, x3=x3)
-            t = ops.conv2d_sp(t, pk["w2"], pk["s2"], pk["b2"], pad=self.dilation, dil=self.dilation, relu=True, x3=x3)
-        else:       # bf16 inside the block: conv1 reads the hi plane, conv2 is the plain launch
-            t = ops.conv2d_sp(x, pk["w1"], pk["s1"], pk["b1"], stride=self.stride, relu=True, out_mode="bf16", x3=False)
+        if m.planes == "all":
+            t = ops.conv2d_sp(x, pk["w1"], pk["s1"], pk["b1"], stride=self.stride, relu=True, operands=op)
+            t = ops.conv2d_sp(t, pk["w2"], pk["s2"], pk["b2"], pad=self.dilation, dil=self.dilation, relu=True, operands=op)
+        else:       # plain inside the block: conv1 reads the hi plane, conv2 is the plain launch
+            t = ops.conv2d_sp(x, pk["w1"], pk["s1"], pk["b1"], stride=self.stride, relu=True, out_mode=m.plain, operands=op)
             t = ops.conv2d_nhwc(t, pk["w2"], pk["s2"], pk["b2"], pad=self.dilation, dil=self.dilation, relu=True)
-        return ops.conv2d_sp(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out_mode=out_mode, x3=x3)
+        return ops.conv2d_sp(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out_mode=out_mode, operands=op)
 
     fuse = True        # layer1's identity blocks as ONE kernel (ops.bottleneck64); False / MEGA_FUSE_BOTTLENECK=0: three launches
 
@@ -276,7 +284,7 @@ class Bottleneck(_Packed):
     def can_subsample(self, x):
         """the block can write its output's even pixels alone (run(subsample=True)): an identity block on plain 16-bit device
         tensors whose conv3 + strided residual igemm8's streaming class serves"""
-        return (not isinstance(x, ops.Planes) and self.sp_mode is None and x.dtype in _HALF and x.is_cuda
+        return (self.mode.planes is None and x.dtype in _HALF and x.is_cuda
                 and self.downsample is None and self.stride == 1 and self.dilation == 1
                 and self.conv3.in_channels <= 512 and self.conv3.out_channels % 256 == 0)
 
@@ -286,7 +294,7 @@ class Bottleneck(_Packed):
         reads_even_pixels_only: conv1 on every pixel (the 3x3 windows around the even pixels cover the map), conv2 as a
         stride-2 conv, conv3 on its output with the identity read at a pixel stride of 2; same bits at those pixels.
         compact_in (reads_even_pixels_only): x is such a tensor -- conv1 and the downsample run on it with stride 1."""
-        if isinstance(x, ops.Planes) or self.sp_mode is not None:
+        if self.mode.planes:
             assert out is None and not subsample and not compact_in
             return self.run_sp(x)
         pk = self._packed(x.dtype, x.device)
@@ -311,10 +319,10 @@ class Bottleneck(_Packed):
         return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out=out)
 
 
-def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride, dilation=1):
+def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride, dilation=1, mode=CONV_MODES["f32"]):
     blocks, stride = [], first_stride
     for _ in range(block_count):
-        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride, dilation))
+        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride, dilation, mode))
         stride, in_channels = 1, out_channels
     return nn.Sequential(*blocks)
 
@@ -367,7 +375,7 @@ class ResNet(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.dtype = compute_dtype(cfg)
-        self.mode = conv_mode(cfg)
+        self.mode = conv_mode_of(cfg)
         blocks = _STAGE_BLOCKS[cfg.MODEL.BACKBONE.CONV_BODY]
         self.stem = BaseStem(cfg.MODEL.RESNETS.STEM_OUT_CHANNELS)
         in_ch = cfg.MODEL.RESNETS.STEM_OUT_CHANNELS
@@ -375,13 +383,9 @@ class ResNet(nn.Module):
         for i, n in enumerate(blocks):
             mid, out = 64 * 2 ** i, cfg.MODEL.RESNETS.RES2_OUT_CHANNELS * 2 ** i
             name = "layer%d" % (i + 1)
-            self.add_module(name, _make_stage(in_ch, mid, out, n, first_stride=int(i > 0) + 1))
+            self.add_module(name, _make_stage(in_ch, mid, out, n, first_stride=int(i > 0) + 1, mode=self.mode))
             self.stages.append(name)
             in_ch = out
-        if self.mode in ("x3", "wide", "h2"):
-            for m in self.modules():
-                if isinstance(m, Bottleneck):
-                    m.sp_mode = self.mode
 
     # layer1's and layer2's last blocks write only the pixels layer2.block0 / layer3.block0 read (the even ones; plain 16-bit
     # modes).  False: every stage output dense, as before -- same C4 bits (tests)
@@ -390,23 +394,23 @@ class ResNet(nn.Module):
     def forward(self, x, u8_norm=None):
         """x [N,3,H,W] f32 image batch -> [C4] (logical NCHW, channels-last memory, compute dtype).
         u8_norm = (mean, to_bgr) with x the uint8 frames [N,H,W,3] (bf16 mode): preprocessing fused into the stem.
-        conv_mode "x3" / "wide": C4 as an f32 tensor (hi + lo of the planes run_nhwc returns)."""
+        The planes modes: C4 as a tensor too (of the planes run_nhwc returns)."""
         y = self.run_nhwc(x, u8_norm)
-        if isinstance(y, ops.Planes):      # (the seam's tensor: f32 = hi + lo in mode "x3", the bf16 hi plane in mode "wide")
-            y = y.float() if self.mode in _PLANES3 else y.hi().contiguous()
+        if isinstance(y, ops.Planes):      # (the seam's tensor: f32 = hi + lo, or the trunk's hi plane: what its convs read)
+            y = y.float() if self.mode.planes == "all" else y.hi().contiguous()
         return [_nchw_view(y)]
 
     def run_nhwc(self, x, u8_norm=None):
-        """forward() without the NCHW view: -> C4 as a contiguous NHWC tensor, or as ops.Planes (conv_mode "x3" / "wide")"""
-        if u8_norm is not None and self.mode == "h2":       # (the two-pass mode's stem is the exact-f32 one: preprocess first)
+        """forward() without the NCHW view: -> C4 as a contiguous NHWC tensor, or as ops.Planes (the planes modes)"""
+        if u8_norm is not None and self.mode.stem_dtype != self.dtype:       # (an exact-f32 stem under 16-bit convs: preprocess first)
             x, u8_norm = ops.preprocess_frames(x.contiguous(), u8_norm[0], u8_norm[1]), None
         if u8_norm is not None:
             assert self.dtype in _HALF and x.dtype == torch.uint8
             y = self.stem.run_u8(x.contiguous(), u8_norm[0], u8_norm[1], self.dtype)
         else:
-            y = self.stem.run(x.float().contiguous(), torch.float32 if self.mode == "h2" else self.dtype)
-        if self.mode in _PLANES3:
-            y = ops.split_planes(y, _plane_dtype(self.mode))   # the stem (exact f32 direct conv + max-pool) hands over its f32 map as planes
+            y = self.stem.run(x.float().contiguous(), self.mode.stem_dtype)
+        if self.mode.planes == "all":
+            y = ops.split_planes(y, self.mode.plane_dtype)   # the stem (exact f32 direct conv + max-pool) hands over its f32 map as planes
         compact = False        # y holds the even pixels of the previous stage's output only
         for si, name in enumerate(self.stages):
             blocks = list(getattr(self, name))
@@ -459,18 +463,19 @@ class ResNetHead(nn.Module):
     """backbone/resnet.py:155-204 as built by roi_box_feature_extractors.py:462-472: res5, stride_init=1,
     dilation=RES5_DILATION, run on the whole C4 map."""
 
-    def __init__(self, dilation=2):
+    def __init__(self, dilation=2, mode=CONV_MODES["f32"]):
         super().__init__()
-        self.layer4 = _make_stage(1024, 512, 2048, 3, first_stride=1, dilation=dilation)
+        self.mode = mode
+        self.layer4 = _make_stage(1024, 512, 2048, 3, first_stride=1, dilation=dilation, mode=mode)
         self.out_channels = 2048
 
-    def run(self, x, out_mode=None):
-        """out_mode (conv_mode "x3" / "wide": x is ops.Planes): what the LAST block writes -- "f32" / "bf16" (a plain map for
-        ROIAlign) or "planes" (a 1x1 reduce conv follows)"""
+    def run(self, x, out_mode="planes"):
+        """out_mode (the planes modes): what the LAST block writes -- self.mode.plain (a plain map for ROIAlign) or "planes"
+        (a 1x1 reduce conv follows)"""
         blocks = list(self.layer4)
         for bi, blk in enumerate(blocks):
-            if isinstance(x, ops.Planes):
-                x = blk.run_sp(x, out_mode if bi + 1 == len(blocks) and out_mode else "planes")
+            if self.mode.planes:
+                x = blk.run_sp(x, out_mode if bi + 1 == len(blocks) else "planes")
             else:
                 x = blk.run(x)
         return x
@@ -516,6 +521,7 @@ class RPNHead(_Packed):
         self.conv = nn.Conv2d(in_channels, in_channels, 3, padding=1)
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, 1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, 1)
+        self.mode = conv_mode_of(cfg)
         for l in (self.conv, self.cls_logits, self.bbox_pred):
             nn.init.normal_(l.weight, std=0.01)
             nn.init.constant_(l.bias, 0)
@@ -523,28 +529,25 @@ class RPNHead(_Packed):
     def _pack(self, dtype, device):
         w2 = torch.cat([self.cls_logits.weight.detach(), self.bbox_pred.weight.detach()], dim=0)
         b2 = torch.cat([self.cls_logits.bias.detach(), self.bbox_pred.bias.detach()], dim=0)
-        if dtype in _PLANES3:   # split-precision 3x3 conv -> f32; the narrow 1x1 outputs stay exact f32
-            return {"w1": (_pack_conv_x3 if dtype == "x3" else _pack_conv_h2)(self.conv).to(device), "b1": self.conv.bias.detach().float().to(device).contiguous(),
-                    "w2": w2.permute(0, 2, 3, 1).contiguous().float().to(device), "b2": b2.float().to(device).contiguous()}
-        return {"w1": _pack_conv(self.conv, dtype).to(device), "b1": self.conv.bias.detach().float().to(device).contiguous(),
-                "w2": w2.permute(0, 2, 3, 1).contiguous().to(dtype).to(device), "b2": b2.float().to(device).contiguous()}
+        # dtype: the input's.  The planes of an "all" mode: split-precision 3x3 conv -> f32; the narrow 1x1 outputs stay exact f32
+        sp = self.mode.planes == "all" and dtype == self.mode.plane_dtype
+        w1 = self.mode.pack(self.conv) if sp else _pack_conv(self.conv, dtype)
+        return {"w1": w1.to(device), "b1": self.conv.bias.detach().float().to(device).contiguous(),
+                "w2": w2.permute(0, 2, 3, 1).contiguous().to(torch.float32 if sp else dtype).to(device),
+                "b2": b2.float().to(device).contiguous()}
 
-    sp_mode = None     # "x3" / "wide" when the backbone hands over C4 as ops.Planes (set by RPNWithRefModule)
     conv_ksplit = None  # the 3x3 conv's caller-chosen split-K (ops.conv2d_nhwc): set by the ONE-frame detectors (FGFA / DFF /
                         # base: 2394 rows x K = 9216 on 64 x 64 tiles, 94 -> 63 us with 4 K ranges); MEGA's batched frame
                         # stage never sets it (a frame's bits must not depend on the batch it is computed in)
 
     def run(self, feat_nhwc):
         """-> [B, H*W, 5A] f32 (channel a = objectness of anchor a, A + 4a + j = delta j)."""
-        if isinstance(feat_nhwc, ops.Planes):
-            x3 = _spk(self.sp_mode)
-            pk = self._packed(self.sp_mode if x3 else torch.bfloat16, feat_nhwc.device)
-            t = ops.conv2d_sp(feat_nhwc, pk["w1"], None, pk["b1"], pad=1, relu=True, out_mode="f32" if x3 else "bf16", x3=x3)
-            o = ops.conv2d_nhwc(t, pk["w2"], None, pk["b2"], out_dtype=torch.float32)
-            B, H, W, C = o.shape
-            return o.view(B, H * W, C)
         pk = self._packed(feat_nhwc.dtype, feat_nhwc.device)
-        t = ops.conv2d_nhwc(feat_nhwc, pk["w1"], None, pk["b1"], pad=1, relu=True, ksplit=self.conv_ksplit)
+        if isinstance(feat_nhwc, ops.Planes):
+            t = ops.conv2d_sp(feat_nhwc, pk["w1"], None, pk["b1"], pad=1, relu=True, out_mode=self.mode.plain,
+                              operands=self.mode.operands)
+        else:
+            t = ops.conv2d_nhwc(feat_nhwc, pk["w1"], None, pk["b1"], pad=1, relu=True, ksplit=self.conv_ksplit)
         o = ops.conv2d_nhwc(t, pk["w2"], None, pk["b2"], out_dtype=torch.float32)
         B, H, W, C = o.shape
         return o.view(B, H * W, C)
@@ -574,8 +577,6 @@ class RPNWithRefModule(nn.Module):
         self.post_nms_top_n = {"key": c.POST_NMS_TOP_N_TEST, "ref": cfg.MODEL.VID.RPN.REF_POST_NMS_TOP_N}
         self.nms_thresh, self.min_size = c.NMS_THRESH, c.MIN_SIZE
         self.strict_gt = bool(getattr(cfg, "NMS_STRICT_GT", True))
-        if conv_mode(cfg) in ("x3", "wide", "h2"):
-            self.head.sp_mode = conv_mode(cfg)
         self.keep_index = False       # tests: frame records also carry the kept proposals' flat anchor indices
 
     def propose(self, feat_nhwc, im_w, im_h, version="key", want_index=False, select_stream=None, hold=None):
@@ -649,7 +650,8 @@ class MEGAFeatureExtractor(_Packed):
         super().__init__()
         rb = cfg.MODEL.ROI_BOX_HEAD
         vid = cfg.MODEL.VID
-        self.head = ResNetHead(cfg.MODEL.RESNETS.RES5_DILATION)
+        self.mode = conv_mode_of(cfg)
+        self.head = ResNetHead(cfg.MODEL.RESNETS.RES5_DILATION, self.mode)
         pooled_c = 2048
         self.conv = None
         if vid.ROI_BOX_HEAD.REDUCE_CHANNEL:
@@ -691,14 +693,9 @@ class MEGAFeatureExtractor(_Packed):
         self.dtype = compute_dtype(cfg)      # frame stage: res5, ROIAlign, fc0
         self.hdtype = head_dtype(cfg)        # the head's matrix-core operands (= self.dtype except in float16 mode, see head_dtype)
         self.stream = stream_dtype(cfg)
-        self.mode = conv_mode(cfg)
         # cfg.F32_HEAD_LINEAR: "auto" (with F32_CONV "bf16x3": the head's Wq / Wk / Wv projections and stage FCs run in
         # split precision like the frame stage; the attention core, position logits and predictor stay exact f32) | "exact"
-        self.head_x3 = self.mode == "x3" and str(getattr(cfg, "F32_HEAD_LINEAR", "auto")) != "exact"
-        if self.mode in ("x3", "wide", "h2"):
-            for m_ in self.head.modules():
-                if isinstance(m_, Bottleneck):
-                    m_.sp_mode = self.mode
+        self.head_x3 = self.mode.operands == "x3" and str(getattr(cfg, "F32_HEAD_LINEAR", "auto")) != "exact"
         self.mem = None
         self.global_cache = None
         self.cache_memory_kv = True      # keep the Wk / Wv projections of memory rows (False: re-project every step)
@@ -718,8 +715,9 @@ class MEGAFeatureExtractor(_Packed):
         w0 = self.l_fcs[0].weight.detach()
         r2 = self.resolution ** 2
         w0 = w0.view(w0.shape[0], self.pooled_c, r2).permute(0, 2, 1).reshape(w0.shape[0], -1)
-        # (conv_mode "x3" reads fc0 as pk["fc0_x3"] only: no resident f32 copy of the 411 MB matrix beside it -- ADVICE r05)
-        pk["fc_w"] = [None if self.mode in _PLANES3 else w0.contiguous().to(dtype).to(device)] + [
+        # (an "all" mode reads fc0 as pk["fc0_sp"] only: no resident f32 copy of the 411 MB matrix beside it -- ADVICE r05)
+        sp = self.mode.planes == "all"
+        pk["fc_w"] = [None if sp else w0.contiguous().to(dtype).to(device)] + [
             self.l_fcs[i].weight.detach().to(dtype).to(device).contiguous() for i in range(1, self.stage)]
         pk["fc_b"] = [self.l_fcs[i].bias.detach().float().to(device).contiguous() for i in range(self.stage)]
         if self.stream != dtype:      # f32 activation stream in bf16 mode: the stage FCs read and write it at ~2^-16 --
@@ -731,11 +729,10 @@ class MEGAFeatureExtractor(_Packed):
         if hx3:
             for i in range(1, self.stage):
                 pk["fc_w"][i] = ops.X3Weight(self.l_fcs[i].weight, device)
-        if self.mode in _PLANES3:  # split-precision fc0 (and reduce conv) operands
-            splitw = ops.split_conv_weight_x3 if self.mode == "x3" else ops.split_conv_weight_h2
-            pk["fc0_x3"] = splitw(w0.float().contiguous().view(w0.shape[0], 1, 1, -1)).view(w0.shape[0], -1).to(device)
+        if sp:  # fc0 (as a 1x1 conv over its input row) and the reduce conv in the mode's operand form
+            pk["fc0_sp"] = self.mode.split(w0.float().contiguous().view(w0.shape[0], 1, 1, -1)).view(w0.shape[0], -1).to(device)
             if self.conv is not None:
-                pk["rc_w_x3"] = (_pack_conv_x3 if self.mode == "x3" else _pack_conv_h2)(self.conv).to(device)
+                pk["rc_w_sp"] = self.mode.pack(self.conv).to(device)
         return pk
 
     # ---- per-frame stage (independent per frame; the multi-GPU sharding unit)
@@ -747,19 +744,19 @@ class MEGAFeatureExtractor(_Packed):
     def res5_features(self, feat_nhwc):
         """the proposal-independent half of box_features: res5 (+1x1 reduce) on the full C4 maps"""
         pk = self._packed(self.dtype, feat_nhwc.device)
-        if self.mode in ("x3", "wide", "h2") and not isinstance(feat_nhwc, ops.Planes):
-            # the reference call signature (forward(x, proposals): x = the backbone's C4 TENSOR, f32 = hi + lo in mode "x3",
-            # the bf16 hi plane in mode "wide"): back to planes, so that res5's blocks -- which run on planes in these modes --
-            # end in a plain map for ROIAlign (ADVICE r05: the tensor branch handed a Planes object to the reduce conv)
-            feat_nhwc = (ops.split_planes(feat_nhwc.float().contiguous(), _plane_dtype(self.mode)) if self.mode in _PLANES3
+        m = self.mode
+        if m.planes and not isinstance(feat_nhwc, ops.Planes):
+            # the reference call signature (forward(x, proposals): x = the backbone's C4 TENSOR, ResNet.forward's f32 = hi + lo
+            # or hi plane): back to planes, so that res5's blocks -- which run on planes in these modes -- end in a plain map
+            # for ROIAlign (ADVICE r05: the tensor branch handed a Planes object to the reduce conv)
+            feat_nhwc = (ops.split_planes(feat_nhwc.float().contiguous(), m.plane_dtype) if m.planes == "all"
                          else feat_nhwc.contiguous())
-        if isinstance(feat_nhwc, ops.Planes) or (self.mode == "wide" and self.head.layer4[0].sp_mode is not None):
-            plain = "f32" if self.mode in _PLANES3 else "bf16"
+        if m.planes:
             if self.conv is None:
-                return self.head.run(feat_nhwc, out_mode=plain)
+                return self.head.run(feat_nhwc, out_mode=m.plain)
             x = self.head.run(feat_nhwc, out_mode="planes")
-            return ops.conv2d_sp(x, pk["rc_w_x3"] if self.mode in _PLANES3 else pk["rc_w"], None, pk["rc_b"], relu=True,
-                                 out_mode=plain, x3=_spk(self.mode))
+            return ops.conv2d_sp(x, pk["rc_w_sp"] if m.planes == "all" else pk["rc_w"], None, pk["rc_b"], relu=True,
+                                 out_mode=m.plain, operands=m.operands)
         x = self.head.run(feat_nhwc)
         if self.conv is not None:
             x = ops.conv2d_nhwc(x, pk["rc_w"], None, pk["rc_b"], relu=True)
@@ -768,7 +765,7 @@ class MEGAFeatureExtractor(_Packed):
     def pooled_fc(self, x5, rois5):
         """ROIAlign on the res5 maps -> fc0 + ReLU"""
         pk = self._packed(self.dtype, x5.device)
-        if self.mode in _PLANES3:
+        if self.mode.planes == "all":
             # f32 ROIAlign (exact term order) writing planes -> split-precision fc0, in row chunks: a chunk's planes tensor
             # ([rows, 2 x 49 C] bf16) stays below the kernels' 2 GiB operand limit.  Rows are independent (split-K depends
             # on K alone), so the chunking does not change a row's bits.
@@ -777,8 +774,8 @@ class MEGAFeatureExtractor(_Packed):
             out = torch.empty((K, self.feat_dim), dtype=torch.float32, device=x5.device)
             for o in range(0, K, per):
                 pooled = ops.roi_align_planes(x5, rois5[o:o + per].contiguous(), self.scale, (self.resolution, self.resolution),
-                                              self.sampling_ratio, _plane_dtype(self.mode))
-                out[o:o + per] = ops.linear_sp(pooled, pk["fc0_x3"], pk["fc_b"][0], relu=True)
+                                              self.sampling_ratio, self.mode.plane_dtype)
+                out[o:o + per] = ops.linear_sp(pooled, pk["fc0_sp"], pk["fc_b"][0], relu=True, operands=self.mode.operands)
             return out
         pooled = ops.roi_align(x5, rois5, self.scale, (self.resolution, self.resolution), self.sampling_ratio)
         return ops.linear(pooled.view(pooled.shape[0], -1), pk["fc_w"][0], pk["fc_b"][0], relu=True,

@@ -1168,13 +1168,13 @@ def split_planes(x, dtype=torch.bfloat16):
 
 def split_conv_weight_h2(w_ohwi):
     """f32 conv weight [Cout,R,S,C] (OHWI) -> float16 [Cout,R,S,2C] = [W | W] per tap, W rounded to fp16 once: the operand of
-    conv2d_sp(x3="h2") -- against fp16 [hi | lo] planes the K = 2C contraction is x_hi.W + x_lo.W (the two-pass fp16 mode)."""
+    conv2d_sp(operands="h2") -- against fp16 [hi | lo] planes the K = 2C contraction is x_hi.W + x_lo.W (the two-pass fp16 mode)."""
     w = w_ohwi.float().to(torch.float16)
     return torch.cat([w, w], dim=-1).contiguous()
 
 
 def split_conv_weight_x3(w_ohwi):
-    """f32 conv weight [Cout,R,S,C] (OHWI) -> bf16 [Cout,R,S,3C] = [Wh | Wh | Wl] per tap: the operand of conv2d_sp(x3=True)
+    """f32 conv weight [Cout,R,S,C] (OHWI) -> bf16 [Cout,R,S,3C] = [Wh | Wh | Wl] per tap: the operand of conv2d_sp(operands="x3")
     (host-side packing, once per model)."""
     w32 = w_ohwi.float()
     wh = w32.to(torch.bfloat16)
@@ -1182,20 +1182,28 @@ def split_conv_weight_x3(w_ohwi):
     return torch.cat([wh, wh, wl], dim=-1).contiguous()
 
 
-def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_mode="planes", x3=True,
-              out=None):
+# operand form of conv2d_sp / linear_sp -> (K multiple of the weight, dtype of planes and weight, K wraps back to the hi plane):
+#   "x3"  planes read as [hi | lo | hi] against w = split_conv_weight_x3(W) [Cout,R,S,3C]: x.W to ~2^-16, f32 accumulation
+#   "h2"  the two-pass fp16 form: float16 planes read as [hi | lo] (no wrap) against w = split_conv_weight_h2(W) [Cout,R,S,2C]
+#   "hi"  only the hi plane is read, against plain bf16 w [Cout,R,S,C] (bf16 compute over a wide residual stream)
+_SP_OPERANDS = {"x3": (3, torch.bfloat16, True), "h2": (2, torch.float16, False), "hi": (1, torch.bfloat16, False)}
+
+
+def _sp_operands(operands):
+    if operands not in _SP_OPERANDS:
+        raise ValueError("operands must be one of %s, not %r" % (sorted(_SP_OPERANDS), operands))
+    return _SP_OPERANDS[operands]
+
+
+def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_mode="planes",
+              operands="x3", out=None):
     """conv + FrozenBN (+ residual) + activation on split-precision planes (mega_conv2d_nhwc_sp_dt, igemm8 SP kernels).
-    x: Planes [N,H,W,C].  x3=True: w = split_conv_weight_x3(W) [Cout,R,S,3C]; the contraction reads the planes as
-    [hi | lo | hi] -- x.W to ~2^-16 with f32 accumulation.  x3=False: w plain bf16 [Cout,R,S,C], only the hi plane is read
-    (bf16 compute over a wide residual stream).  residual: Planes [N,Ho,Wo,Cout] (hi + lo added in f32).
-    out_mode: "planes" -> Planes, "f32" -> f32 tensor, "bf16" -> bf16 tensor  [N,Ho,Wo,Cout]."""
+    x: Planes [N,H,W,C]; w: the weight in the form `operands` names (_SP_OPERANDS).  residual: Planes [N,Ho,Wo,Cout]
+    (hi + lo added in f32).  out_mode: "planes" -> Planes, "f32" -> f32 tensor, "bf16" -> bf16 tensor  [N,Ho,Wo,Cout]."""
+    kmul, pdt, kwrap = _sp_operands(operands)
     assert residual is None or isinstance(residual, Planes)
-    # x3 == "h2": the two-pass fp16 form -- float16 planes read as [hi | lo] (K = 2C, no wrap) against w = split_conv_weight_h2(W)
-    h2 = isinstance(x3, str) and x3 == "h2"
-    kmul = 2 if h2 else (3 if x3 else 1)
-    pdt = torch.float16 if h2 else torch.bfloat16
-    if not isinstance(x, Planes):      # a plain bf16 tensor as the input (pixel stride C): x3=False only
-        assert x.dtype == torch.bfloat16 and x.is_contiguous() and not x3
+    if not isinstance(x, Planes):      # a plain bf16 tensor as the input (pixel stride C): operands "hi" only
+        assert x.dtype == torch.bfloat16 and x.is_contiguous() and operands == "hi"
         xt, ldi = x, x.shape[-1]
     else:
         xt, ldi = x.t, 2 * x.C
@@ -1228,12 +1236,12 @@ def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1
     M = N * Ho * Wo
     _tok = None
     if _PROF is not None:
-        _tok = _pb("igemm8_sp_" + ("h2" if h2 else ("x3" if x3 else "hi")), 2.0 * M * Cout * K,
-                   xt.numel() * (2.0 if x3 or xt is x else 1.0) + w.numel() * 2.0 + out.numel() * out.element_size()
+        _tok = _pb("igemm8_sp_" + operands, 2.0 * M * Cout * K,
+                   xt.numel() * (2.0 if operands != "hi" or xt is x else 1.0) + w.numel() * 2.0 + out.numel() * out.element_size()
                    + (0 if residual is None else residual.t.numel() * 2.0), detail="%dx%dx%d (%dx%d)" % (M, Cout, K, R, S))
     nb = lib.mega_conv2d_nhwc_workspace_bytes(M, Cout, K) if mode == 2 and residual is None else 0
     ws = _ws(nb, x.device) if nb else None
-    rc = lib.mega_conv2d_nhwc_sp_dt(_ptr(xt), ldi, 2 * C if kmul == 3 else 0, _ptr(w), _ptr(scale), _ptr(bias),
+    rc = lib.mega_conv2d_nhwc_sp_dt(_ptr(xt), ldi, 2 * C if kwrap else 0, _ptr(w), _ptr(scale), _ptr(bias),
                                     None if residual is None else _ptr(residual.t), 0, _ptr(out), ldo, mode, N, H, W, Cw, Cout,
                                     R, S, stride, pad, dil, int(relu), _DT[pdt], _ptr(ws), nb, _stream())
     _pe(_tok)
@@ -1273,17 +1281,16 @@ def linear_transposed_x3(w, x, ld):
     out = torch.empty((Nout, ld), dtype=torch.float32, device=x.device)
     if ld > M8:
         out[:, M8:].zero_()
-    conv2d_sp(w.w3.view(Nout, 1, 1, 3 * K), xs.view(M8, 1, 1, 3 * K), out_mode="f32", x3=False, out=out)
+    conv2d_sp(w.w3.view(Nout, 1, 1, 3 * K), xs.view(M8, 1, 1, 3 * K), out_mode="f32", operands="hi", out=out)
     return out
 
 
-def linear_sp(x, w3, bias=None, relu=False):
-    """x: Planes [M,K]; w3 = split_conv_weight_x3 of [Nout,K] viewed [Nout,1,1,K] -> f32 [M,Nout] (x.W to ~2^-16); or, for
-    float16 planes, w3 = split_conv_weight_h2 of it ([Nout, 2K]: the two-pass fp16 form)."""
+def linear_sp(x, w3, bias=None, relu=False, operands="x3"):
+    """x: Planes [M,K]; w3 = split_conv_weight_x3 ("x3": x.W to ~2^-16) or split_conv_weight_h2 ("h2": float16 planes, the
+    two-pass fp16 form) of [Nout,K] viewed [Nout,1,1,K] -> f32 [M,Nout]."""
     M, K = x.shape
-    h2 = x.t.dtype == torch.float16
-    y = conv2d_sp(Planes(x.t.view(M, 1, 1, 2 * K), K), w3.view(w3.shape[0], 1, 1, (2 if h2 else 3) * K), None, bias, relu=relu,
-                  out_mode="f32", x3="h2" if h2 else True)
+    y = conv2d_sp(Planes(x.t.view(M, 1, 1, 2 * K), K), w3.view(w3.shape[0], 1, 1, _sp_operands(operands)[0] * K), None, bias,
+                  relu=relu, out_mode="f32", operands=operands)
     return y.view(M, w3.shape[0])
 
 

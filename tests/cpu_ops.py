@@ -288,22 +288,17 @@ def split_conv_weight_h2(w_ohwi):
     return torch.cat([w, w], dim=-1).contiguous()
 
 
-def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_mode="planes", x3=True,
-              out=None):
+def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1, relu=False, out_mode="planes",
+              operands="x3", out=None):
     from mega.pytorch_amd import ops
+    kmul, pdt, _ = ops._sp_operands(operands)
     if isinstance(x, ops.Planes):
         C = x.C
-        xin = x.float() if x3 else x.hi().float()
+        xin = x.hi().float() if operands == "hi" else x.float()
     else:
         C, xin = x.shape[-1], x.float()
-    h2 = isinstance(x3, str) and x3 == "h2"
-    pdt = torch.float16 if h2 else torch.bfloat16
-    if h2:
-        w32 = w[..., :C].float()                                                    # [W | W] -> W (rounded to fp16 once)
-        assert w.shape[-1] == 2 * C
-    else:
-        w32 = (w[..., :C].float() + w[..., 2 * C:].float()) if x3 else w.float()    # [Wh | Wh | Wl] -> Wh + Wl
-    assert w32.shape[-1] == C
+    assert w.shape[-1] == kmul * C
+    w32 = w[..., :C].float() + (w[..., 2 * C:].float() if operands == "x3" else 0)      # [Wh | Wh | Wl] -> Wh + Wl; [W | W] -> W
     y = conv2d_nhwc(xin, w32, scale, bias, None if residual is None else residual.float(), stride, pad, dil, relu,
                     out_dtype=torch.float32)
     if out is not None:
@@ -312,9 +307,10 @@ def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1
     return _planes(y, pdt) if out_mode == "planes" else y.to(torch.float32 if out_mode == "f32" else pdt)
 
 
-def linear_sp(x, w3, bias=None, relu=False):
+def linear_sp(x, w3, bias=None, relu=False, operands="x3"):
     M, K = x.shape
-    w32 = w3[:, :K].float() + w3[:, 2 * K:].float() if w3.shape[1] == 3 * K else w3[:, :K].float()
+    assert w3.shape[1] == {"x3": 3, "h2": 2}[operands] * K
+    w32 = w3[:, :K].float() + w3[:, 2 * K:].float() if operands == "x3" else w3[:, :K].float()
     y = x.float() @ w32.t()
     if bias is not None:
         y = y + bias

@@ -322,7 +322,7 @@ def split_hi_lo(v, dtype=torch.bfloat16):
 
 
 def make_sp_case(shape, wide_w, relu, use_res, seed):
-    """conv2d_sp(x3=True) on integers.  x: mostly small, one element in eight (wide_w: in 32) up to +-4096 (13 bits: the lo plane is needed and
+    """conv2d_sp(operands="x3") on integers.  x: mostly small, one element in eight (wide_w: in 32) up to +-4096 (13 bits: the lo plane is needed and
     x = hi + lo holds exactly); w: |w| <= 4, or (wide_w) one element in 32 from +-{257, 259, 515}, whose bf16 hi part is
     256 / 260 / 516 and whose lo part is +-1; scale in {1/2, 1}, integer bias, integer residual up to +-1024."""
     N, H, W, Cin, Cout, R, stride, pad, dil = shape

@@ -213,7 +213,7 @@ def test_stem_entry_points_exact(dev, hw):
 @pytest.mark.parametrize("out_mode", ["f32", "planes"])
 @pytest.mark.parametrize("spec", ec.SP_CASES, ids=["3x3-small-w", "1x1-wide-w"])
 def test_conv2d_sp_x3_exact(dev, spec, out_mode):
-    """conv2d_sp(x3=True): the documented contraction x_hi.Wh + x_lo.Wh + x_hi.Wl, x up to 4096 (the lo plane is used), weights
+    """conv2d_sp(operands="x3"): the documented contraction x_hi.Wh + x_lo.Wh + x_hi.Wl, x up to 4096 (the lo plane is used), weights
     whose lo part is zero / non-zero; ops.split_planes and the weight packing equal the CPU split bit for bit"""
     ops = _ops()
     shape, wide, relu, use_res = spec
@@ -230,5 +230,5 @@ def test_conv2d_sp_x3_exact(dev, spec, out_mode):
         assert_bits_equal(rp.t, torch.cat(ec.split_hi_lo(case.res), dim=-1), "split_planes(residual) %s" % (shape,))
     want, _ = ec.reference_sp(case, out_mode)
     y = ops.conv2d_sp(xp, w3.to(dev), case.scale.to(dev), case.bias.to(dev), residual=rp, stride=stride, pad=pad, dil=dil,
-                      relu=relu, out_mode=out_mode, x3=True)
+                      relu=relu, out_mode=out_mode, operands="x3")
     assert_bits_equal(y.t if out_mode == "planes" else y, want, "conv2d_sp x3 %s -> %s" % (shape, out_mode), relu=relu)

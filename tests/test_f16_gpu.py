@@ -331,7 +331,7 @@ def test_h2_conv2d_sp_vs_f64(dev, case):
     wh2 = ops.split_conv_weight_h2(w).to(dev)
     assert wh2.dtype == H16 and wh2.shape[-1] == 2 * C
     y = ops.conv2d_sp(xp, wh2, scale.to(dev), bias.to(dev), residual=rp, stride=stride, pad=pad, dil=dil, relu=relu,
-                      out_mode=out_mode, x3="h2")
+                      out_mode=out_mode, operands="h2")
     got = (y.float() if out_mode == "planes" else y).cpu().double()
     err = (got - ref).abs().max().item() / ref.abs().max().item()
     print("conv2d_sp h2 %s: max err / scale = %.3g" % (case, err))
@@ -349,7 +349,7 @@ def test_h2_linear_sp_split_k_and_roi_align_planes(dev):
     b = torch.randn((Nout,), generator=g) * 0.1
     ref = (x.double() @ w.to(H16).double().t() + b.double()).clamp(min=0)
     y = ops.linear_sp(ops.split_planes(x.to(dev), H16), ops.split_conv_weight_h2(w.view(Nout, 1, 1, K)).to(dev).view(Nout, 2 * K),
-                      b.to(dev), relu=True).cpu().double()
+                      b.to(dev), relu=True, operands="h2").cpu().double()
     err = (y - ref).abs().max().item() / ref.abs().max().item()
     print("linear_sp h2 split-K: max err / scale = %.3g" % err)
     assert err < 2e-5

@@ -1101,7 +1101,7 @@ def test_conv2d_sp_x3_vs_f64(dev, case):
     assert (xp.float().cpu() - x).abs().max() <= 2.0 ** -16 * x.abs().max()          # the planes hold x to ~2^-17
     rp = ops.split_planes(res.to(dev).contiguous()) if use_res else None
     y = ops.conv2d_sp(xp, ops.split_conv_weight_x3(w).to(dev), scale.to(dev), bias.to(dev), residual=rp, stride=stride,
-                      pad=pad, dil=dil, relu=relu, out_mode=out_mode, x3=True)
+                      pad=pad, dil=dil, relu=relu, out_mode=out_mode, operands="x3")
     got = (y.float() if out_mode == "planes" else y).cpu().double()
     err = (got - ref).abs().max().item() / ref.abs().max().item()
     print("conv2d_sp x3 %s: max err / scale = %.3g" % (case, err))
@@ -1110,7 +1110,7 @@ def test_conv2d_sp_x3_vs_f64(dev, case):
 
 @pytest.mark.parametrize("case", SP_CASES[:5] + SP_CASES[8:])
 def test_conv2d_sp_hi_plane_bit_equal_to_bf16_kernel(dev, case):
-    """x3=False (the bf16 mode over a wide residual stream): the hi plane is the bf16 kernel's input, so without a
+    """operands="hi" (the bf16 mode over a wide residual stream): the hi plane is the bf16 kernel's input, so without a
     residual the rounded output equals the plain bf16 launch bit for bit (out_mode "bf16"; the planes' hi is that value
     too), and with a split residual the sum is taken against hi + lo in f32."""
     ops = _ops()
@@ -1121,9 +1121,9 @@ def test_conv2d_sp_hi_plane_bit_equal_to_bf16_kernel(dev, case):
     sc, bi = scale.to(dev), bias.to(dev)
     xh = xp.hi().contiguous()
     plain = ops.conv2d_nhwc(xh, wb, sc, bi, stride=stride, pad=pad, dil=dil, relu=relu)
-    y16 = ops.conv2d_sp(xp, wb, sc, bi, stride=stride, pad=pad, dil=dil, relu=relu, out_mode="bf16", x3=False)
+    y16 = ops.conv2d_sp(xp, wb, sc, bi, stride=stride, pad=pad, dil=dil, relu=relu, out_mode="bf16", operands="hi")
     assert torch.equal(y16.view(torch.int16), plain.view(torch.int16))
-    yp = ops.conv2d_sp(xp, wb, sc, bi, stride=stride, pad=pad, dil=dil, relu=relu, out_mode="planes", x3=False)
+    yp = ops.conv2d_sp(xp, wb, sc, bi, stride=stride, pad=pad, dil=dil, relu=relu, out_mode="planes", operands="hi")
     assert torch.equal(yp.hi().contiguous().view(torch.int16), plain.view(torch.int16))
     if use_res:
         rp = ops.split_planes(res.to(dev).contiguous())
@@ -1132,7 +1132,7 @@ def test_conv2d_sp_hi_plane_bit_equal_to_bf16_kernel(dev, case):
         if relu:
             want = want.clamp(min=0)
         got = ops.conv2d_sp(xp, wb, sc, bi, residual=rp, stride=stride, pad=pad, dil=dil, relu=relu, out_mode="planes",
-                            x3=False).float()
+                            operands="hi").float()
         # (fma(acc, scale, bias) + residual in f32, then the planes hold it to 2^-17)
         assert (got - want).abs().max().item() <= 2.0 ** -15 * want.abs().max().item()
 
