@@ -86,7 +86,7 @@ class KeyFrameShard(object):
         per, R, D = (S + W - 1) // W, max(max(nrows), 1), like.shape[1]
         buf = like.new_zeros((per, R, D))
         ops.copy_blocks([(buf[t // W, :x.shape[0]], x) for t, x in own.items() if x.shape[0] > 0])
-        out = like.new_empty((W * per, R, D))
+        out = torch.empty((W * per, R, D), dtype=like.dtype, device=like.device)
         self._count("memory_rows", buf)
         self.dist.all_gather_into_tensor(out, buf, group=self.group)
         return [out[self.owner(t) * per + t // W, :nrows[t]] for t in range(S)]

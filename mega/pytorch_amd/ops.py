@@ -238,7 +238,8 @@ def deconv4x4s2_into(x, w4, bias4, out, coff, relu=0, ksplit=1):
     """crop_like(act(ConvTranspose2d(Cin, C, 4, stride=2)(x))) written to out[..., coff:coff + C] (flownet.py:9-13,:40-52,:94-111):
     x [N,H,W,Cin] NHWC, w4 = pack_deconv4x4s2(weight), bias4 f32 [4 C] (the bias repeated four times) or None, out
     [N,H2,W2,ldo] contiguous (the level's concatenation buffer); crop_like's rule: the full map is (2H+2) x (2W+2); when its
-    size differs from (H2, W2) one row / column is dropped at the top / left."""
+    size differs from (H2, W2) one row / column is dropped at the top / left.  Only the slice is written: every other column
+    of out keeps what it held (flow_level_assemble writes the rest of a level's buffer)."""
     _gpu(x, w4, bias4, out)
     lib = _lib.load()
     N, H, W, Cin = x.shape
@@ -564,6 +565,7 @@ def nms(dets, scores, thr, strict_gt=True):
 def rpn_select(rpn_out, cell_anchors, Hf, Wf, anchor_stride, pre_nms, post_nms, nms_thresh, min_size, im_w, im_h,
                strict_gt=True, want_index=False, hold=None):
     """rpn_out [B,Hf*Wf,5A] f32 -> proposals [B,post_nms,4], scores [B,post_nms], counts [B] (all on device).
+    The rows past counts[b] are written too: zero proposals, zero scores.
     want_index: also the kept proposals' flat anchor indices (y*Wf + x)*A + a, [B,post_nms] i32, -1 past the count.
     hold (a list): the workspace is appended to it -- a caller that launches this on a side stream (launch_on) keeps it
     alive until the streams have joined, so that the allocator cannot hand the block to the current stream's next op."""
@@ -596,7 +598,9 @@ def rpn_select(rpn_out, cell_anchors, Hf, Wf, anchor_stride, pre_nms, post_nms, 
 
 def postprocess(logits, deltas, props, nprop, weights, im_w, im_h, score_thresh, nms_thresh, max_det,
                 strict_gt=True, want_probs=False):
-    """One image: returns (boxes [cap,4], scores [cap], labels [cap] i64, count [1] i32 device[, probs])."""
+    """One image: returns (boxes [cap,4], scores [cap], labels [cap] i64, count [1] i32 device[, probs]), cap = (NC-1) * R.
+    The detections are the first `count` rows; the rows from `count` on are not written (torch.empty: whatever the
+    allocator's block held) and no part of the result."""
     _gpu(logits, deltas, props)
     lib = _lib.load()
     R, NC = logits.shape
@@ -629,7 +633,7 @@ def postprocess_batched(logits, deltas, props, B, weights, im_w, im_h, score_thr
                         strict_gt=True, nprop=None):
     """B images of R = rows / B proposals each (logits [B*R,NC], deltas [B*R,NC*4], props [B*R,4]) in one launch chain.
     Returns (boxes [B,cap,4], scores [B,cap], labels [B,cap] i64, counts [B] i32 device); image b has the bits of
-    postprocess() on its own rows."""
+    postprocess() on its own rows.  Image b's detections are its first counts[b] rows; the rows past them are not written."""
     _gpu(logits, deltas, props)
     lib = _lib.load()
     NC = logits.shape[1]
@@ -666,7 +670,8 @@ def postprocess_batched(logits, deltas, props, B, weights, im_w, im_h, score_thr
 def postprocess_candidates_batched(logits, deltas, props, B, weights, im_w, im_h, score_thresh, nprop=None):
     """The candidates of B images of R = rows / B proposals each (include/mega_hip.h mega_postprocess_candidates_batched):
     (boxes [B,NC-1,R,4], scores [B,NC-1,R]) -- class j + 1, proposal row r; the score is -1 where it is not > score_thresh
-    or r >= nprop[b]."""
+    or r >= nprop[b].  Every slot is written; the box of a slot whose score is -1 is the decode of whatever that row holds
+    (NaN for a padding row) and no part of the result."""
     _gpu(logits, deltas, props)
     lib = _lib.load()
     NC = logits.shape[1]
@@ -731,7 +736,8 @@ def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_th
     cboxes [K,F,NC-1,R,4] / cscores [K,F,NC-1,R] f32 (the candidates of every view, each in its own image), view_sizes
     [(w, h)] x K (view 0 = the identity view, whose image the results are in), view_flips [bool] x K.  Returns
     (boxes [F,cap,4], scores [F,cap], labels [F,cap] i64, counts [F] i32 device), cap = (NC-1) * K * R: frame f's
-    detections are the first counts[f] rows.  Raises ValueError beyond K = 16 views or K * R = 8192 rows per class."""
+    detections are the first counts[f] rows; the rows past them are not written.  Raises ValueError beyond K = 16 views or
+    K * R = 8192 rows per class."""
     _gpu(cboxes, cscores)
     lib = _lib.load()
     F, K, R, NC, (ob, os_, ol, oc), (vw, vh, vf), ws, nb = _merge_setup(
@@ -780,7 +786,10 @@ def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh
 def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False):
     """-> [16, Nq, ldp] f32 with ldp = roundup(Nk, 32).  precise=False: fast sin/cos (bf16 mode).
     tiled=True (bf16 mode only): -> bf16 [16, ceil(Nk/32), Nq, 32] in the attention kernel's tile order (half the
-    bytes; relation_attention recognises it by its dtype)."""
+    bytes; relation_attention recognises it by its dtype).
+    Only the logits of the keys below Nk are written: the pad columns Nk .. ldp-1 of the rows, and the pad-key slots of the
+    last tile, hold whatever the allocator's block held (NaN included).  The attention kernels never let a pad key's logit
+    reach the softmax."""
     _gpu(rois_q, rois_k, wg_t, bg, dim_mat)
     lib = _lib.load()
     Nq, Nk = rois_q.shape[0], rois_k.shape[0]
@@ -946,7 +955,7 @@ class _CopySeg(ctypes.Structure):
 
 def copy_blocks(pairs):
     """[(dst, src)]: 2-D tensors of equal shape / dtype with unit column stride (row / column blocks of wider buffers
-    are fine) -> all copies in ONE launch (mega_copy_segments)."""
+    are fine) -> all copies in ONE launch (mega_copy_segments).  Nothing outside the destination blocks is written."""
     pairs = [(d, s_) for d, s_ in pairs if d.numel() > 0]
     if not pairs:
         return
@@ -1517,7 +1526,8 @@ def _check_video_tensors(box, score, seg_off, tasks, F, C, pos=None):
 def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     """Seq-NMS over T (video, class) tasks (include/mega_hip.h mega_seq_nms).  box [N,4] f32, score [N] f32 sorted class-
     major then frame, seg_off [C*F+1] i64, tasks [T,3] i32 (class, first frame, frame count), longest first.
-    -> keep [N] u8, new_score [N] f32 (valid where keep), stats [T,2] i64 (iterations, DP frame steps), on the device.
+    -> keep [N] u8, new_score [N] f32 (valid where keep; the other elements are the wrapper's zeros), stats [T,2] i64
+    (iterations, DP frame steps), on the device.  Every box belongs to one task, so every element of keep is written.
     Synchronises the stream (the kernel's status word)."""
     _gpu(box, score, seg_off, tasks)
     lib = _lib.load()
@@ -1543,7 +1553,8 @@ def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, m
     score [N] f32, pos [N] i32 sorted class-major, then frame, then descending score (equal scores: ascending position);
     seg_off [C*F+1] i64, tasks [T,3] i32 (class, first frame, frame count), longest first; max_open: a bound on a task's
     open tracks.  -> root [N] i64 (index of the track's first box in this order, -1: no track), and valid at the roots
-    cnt [N] i32, sum [N] f64, mx [N] f32, on the device.  Synchronises the stream (the kernel's status word)."""
+    cnt [N] i32, sum [N] f64, mx [N] f32, on the device (the kernel writes them at the roots only: the other elements are
+    the wrapper's zeros).  Synchronises the stream (the kernel's status word)."""
     _gpu(box, score, pos, seg_off, tasks)
     lib = _lib.load()
     N, T = _check_video_tensors(box, score, seg_off, tasks, F, C, pos)
