@@ -381,6 +381,12 @@ int mega_conv2d_nhwc_sp_dt(const void* in, int ldi, int kwrap, const void* w, co
                            int Cout, int R, int S, int stride, int pad, int dil, int relu, int dtype, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* Which SP kernel a mega_conv2d_nhwc_sp_dt launch of GEMM shape M x Cout x K (K = R S Cin, Cin the wrapped depth of one tap)
+ * with taps = R S runs on: kind * 1000000 + rows * 1000 + 256, encoded as mega_conv2d_nhwc_plan_ex (kind 7 streaming class,
+ * 8 matrix class; rows 192 or 256).  has_ws: the call passes a split-K workspace.  Computed by the function the launch itself
+ * uses; launches nothing.  -1: not a launchable combination (bad sizes, a split-K launch that is not out_mode 2). */
+int mega_conv2d_nhwc_sp_plan(int M, int Cout, int K, int taps, int out_mode, int has_ws);
+
 /* The three plane entry points above take either 16-bit type (dtype = MEGA_BF16 / MEGA_F16: the type of the [hi | lo] pairs and of
  * the weights; the text above describes MEGA_BF16).  MEGA_F16 carries the TWO-PASS form of the fp16 mode (conv_mode "h2"): ldi = 2C, Cin = 2C, kwrap = 0 reads the planes
  * as [hi | lo] against weights packed [W | W] per tap, W rounded to fp16 once -- x_hi.W + x_lo.W: exact activations (to ~2^-22)

@@ -721,6 +721,24 @@ extern "C" int mega_conv2d_nhwc_subpixel(const void* in, const void* w4, const f
   });
 }
 
+// The launch decision of the SP kernels, shared by mega_conv2d_nhwc_sp_dt (which launches it) and mega_conv2d_nhwc_sp_plan
+// (which reports it).  K ranges: the library's rule, only when the caller brought a workspace; class and rows: igemm8's own.
+static int sp_ksplit(int K, bool has_ws) { return has_ws ? choose_ksplit(K) : 1; }
+static ConvPlan plan_sp(int M, int Cout, int K, int taps, int ksplit) {
+  return {mega_igemm8_class(taps, K, ksplit) ? KERNEL_IGEMM8S : KERNEL_IGEMM8, igemm8_rows(M, Cout, ksplit), 256};
+}
+
+// kind * 1e6 + rows * 1e3 + 256 (as mega_conv2d_nhwc_plan_ex; kinds 7 streaming, 8 matrix) of the SP kernel a
+// mega_conv2d_nhwc_sp_dt launch of GEMM shape M x Cout x K (K = R S Cin, the wrapped depth) with `taps` = R S runs on;
+// has_ws: the caller passes a split-K workspace.  -1: not a launchable combination.  Launches nothing.
+extern "C" int mega_conv2d_nhwc_sp_plan(int M, int Cout, int K, int taps, int out_mode, int has_ws) {
+  if (M <= 0 || Cout <= 0 || K <= 0 || taps <= 0 || K % taps != 0 || out_mode < 0 || out_mode > 2) return -1;
+  const int z = sp_ksplit(K, has_ws != 0);
+  if (z > 1 && out_mode != 2) return -1;
+  const ConvPlan pl = plan_sp(M, Cout, K, taps, z);
+  return pl.kernel * 1000000 + pl.bm * 1000 + pl.bn;
+}
+
 // Split-precision activation planes (igemm_params.h, igemm8.hip SP kernels).  An f32 activation x [N,H,W,C] lives in HBM as
 // bf16 [N,H,W,2C] = [hi | lo] (mega_split_f32_to_planes_dt; ~2^-17 relative).  This entry point runs conv + FrozenBN (+ split
 // residual) + activation on such tensors with the bf16 matrix cores:
@@ -750,16 +768,15 @@ extern "C" int mega_conv2d_nhwc_sp_dt(const void* in, int ldi, int kwrap, const 
   p.ldo = ldo > 0 ? ldo : (out_mode == 1 ? 2 * Cout : Cout);
   p.ldr = ldr > 0 ? ldr : 2 * Cout;
   p.relu = relu;
-  if (ws) {
-    const int z = choose_ksplit(p.K);
-    if (z > 1) {
-      if (ws_bytes < (size_t)z * p.M * Cout * sizeof(float) || out_mode != 2 || residual) return MEGA_ERR_ARG;
-      p.ksplit = z;
-      p.partial = (float*)ws;
-    }
+  const int z = sp_ksplit(p.K, ws != nullptr);
+  if (z > 1) {
+    if (ws_bytes < (size_t)z * p.M * Cout * sizeof(float) || out_mode != 2 || residual) return MEGA_ERR_ARG;
+    p.ksplit = z;
+    p.partial = (float*)ws;
   }
   hipStream_t st = (hipStream_t)stream;
-  int rc = mega_igemm8_launch(p, igemm8_rows(p.M, Cout, p.ksplit), out_mode == 2, dtype, st);   // (the SP kernels exist on igemm8 only)
+  // (the SP kernels exist on igemm8 only; its launcher takes the class from mega_igemm8_class, as plan_sp does)
+  int rc = mega_igemm8_launch(p, plan_sp(p.M, Cout, p.K, R * S, p.ksplit).bm, out_mode == 2, dtype, st);
   if (rc == MEGA_OK && p.ksplit > 1) rc = launch_finalize<bf16_t, float>(p, st);      // (no residual in split-K launches: type-free)
   return rc;
 }

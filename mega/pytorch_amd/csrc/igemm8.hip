@@ -742,7 +742,7 @@ int launch8_mode(const ConvParams& p, int bm, int out_f32, hipStream_t st) {
   } else if constexpr (EPI == EPI_STRIDED_RES) {
     return rows(HT{}, C1{});
   } else {
-    if (mega_igemm8_streaming(p.R * p.S, p.K) && p.ksplit == 1) return out_f32 ? rows(float{}, C1{}) : rows(HT{}, C1{});
+    if (mega_igemm8_class(p.R * p.S, p.K, p.ksplit)) return out_f32 ? rows(float{}, C1{}) : rows(HT{}, C1{});
     return out_f32 ? rows(float{}, C0{}) : rows(HT{}, C0{});
   }
 }
@@ -751,6 +751,9 @@ int launch8_mode(const ConvParams& p, int bm, int out_f32, hipStream_t st) {
 
 // the streaming launch class of igemm8_kernel's CLS parameter (see there)
 int mega_igemm8_streaming(int taps, int K) { return taps == 1 && K <= 512; }
+
+// (a split-K launch writes raw partial sums: the matrix class's epilogue)
+int mega_igemm8_class(int taps, int K, int ksplit) { return mega_igemm8_streaming(taps, K) && ksplit == 1; }
 
 int mega_igemm8_supports(const ConvParams& p) {
   // capability (a single K-tile works: the ring's second tile is then all zeros); which shapes are SENT here by default

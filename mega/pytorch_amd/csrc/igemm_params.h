@@ -54,6 +54,9 @@ int mega_igemm8_launch(const ConvParams& p, int bm, int out_f32, int half_dtype,
 int mega_igemm8_supports(const ConvParams& p);
 // 1 when a launch of `taps` = R * S kernel taps and GEMM depth K belongs to igemm8's streaming class (1x1, K <= 512)
 int mega_igemm8_streaming(int taps, int K);
+// 1 when a plain or split-precision launch runs igemm8's streaming (CLS 1) instantiation, 0 the matrix (CLS 0) one: what
+// launch8_mode instantiates and what the plan entry points report
+int mega_igemm8_class(int taps, int K, int ksplit);
 // conv64.hip: persistent 3x3 / 64 -> 64 channel kernel (layer1's conv2); bit-identical to the generic tiles
 int mega_conv64_supports(const ConvParams& p, int out_f32);
 int mega_conv64_launch(const ConvParams& p, int half_dtype, hipStream_t st);

@@ -9,6 +9,10 @@ equals `reference` BIT FOR BIT; one lost or doubled contraction element, a stale
 residual, or another rounding mode shows up as a wrong integer.  `check_exact` asserts the condition, so that "bit-equal" is a
 theorem and not a hope; tests/test_exact_conv_cases.py proves on the CPU that the check bites (planted faults).
 
+The split-precision kernels add the roundings their operand forms document -- the hi / lo splits of activations, weights,
+residual and output, the one fp16 rounding of an h2 weight -- and `reference_sp` / `reference_sp_block` perform exactly those
+(SP_FORMS, SP_TABLE): the same theorem, with the terms of the documented contraction as the products.
+
 Layouts are the kernels' own: activations NHWC, weights OHWI.  A shape is (N, H, W, Cin, Cout, R, stride, pad, dil).
 """
 import math
@@ -313,60 +317,308 @@ def reference_stem(case, out_dtype, to_bgr=True, pool=False):
     return y.permute(0, 2, 3, 1).contiguous(), bound / g
 
 
-# ------------------------------------------------------------------------------------------------ split precision (x3)
-def split_hi_lo(v, dtype=torch.bfloat16):
-    """the two roundings of a split: hi = dtype(v), lo = dtype(v - hi) (v f32)"""
+# ------------------------------------------------------------------------------------------------ split precision
+# operand form of ops.conv2d_sp -> (dtype T of planes and weights, blocks of the K axis per tap).  The documented contractions:
+#   "x3"  x_hi.Wh + x_lo.Wh + x_hi.Wl   (x_lo.Wl is not part of it), planes and weight split by two bf16 roundings each
+#   "h2"  (x_hi + x_lo) . f16(W)        f16 planes, W rounded to fp16 ONCE
+#   "hi"  x_hi . bf16(W)                only the hi plane is read (from planes, or -- plain_x -- from a plain bf16 tensor)
+SP_FORMS = {"x3": (torch.bfloat16, 3), "h2": (torch.float16, 2), "hi": (torch.bfloat16, 1)}
+SP_OUT_MODES = ("planes", "f32", "plain")
+_WIDE_W = {torch.bfloat16: (257.0, 259.0, 515.0),        # bf16: 256 / 260 / 516, lo part -+1
+           torch.float16: (2049.0, 2051.0, 4099.0)}      # not fp16 numbers: 2048 / 2052 / 4100
+
+
+def split_hi_lo(v, dtype=torch.bfloat16, trunc_lo=False):
+    """the two roundings of a split: hi = dtype(v), lo = dtype(v - hi) (v f32; v - hi is an f32 number).  trunc_lo: the
+    second one by truncation (a planted fault)."""
     v = v.float()
     hi = v.to(dtype)
-    return hi, (v - hi.float()).to(dtype)
+    return hi, convert((v - hi.float()).double(), dtype, trunc=trunc_lo)
 
 
-def make_sp_case(shape, wide_w, relu, use_res, seed):
-    """conv2d_sp(operands="x3") on integers.  x: mostly small, one element in eight (wide_w: in 32) up to +-4096 (13 bits: the lo plane is needed and
-    x = hi + lo holds exactly); w: |w| <= 4, or (wide_w) one element in 32 from +-{257, 259, 515}, whose bf16 hi part is
-    256 / 260 / 516 and whose lo part is +-1; scale in {1/2, 1}, integer bias, integer residual up to +-1024."""
+def make_sp_case(shape, wide_w, relu, use_res, seed, form="x3", plain_x=False, xbig=4096, pbig=None, xband=None,
+                 pwide=0.03125, sexp=(-1, 0), ab=16, abig=None, ar=1024):
+    """conv2d_sp on integers.  x: mostly |x| <= 8, a share pbig (default one element in eight; wide_w: in 32) up to +-xbig (4096:
+    13 bits, the lo plane is needed in bf16 and in f16, and x = hi + lo holds exactly); w: |w| <= 4, or (wide_w) one element in 32
+    from +-_WIDE_W, which T does not hold (bf16: hi part 256 / 260 / 516, lo part +-1; f16: one rounding to 2048 / 2052 / 4100);
+    xband = (lo, hi): the wide activations are odd integers of magnitude lo .. hi instead (every one of them needs its lo plane,
+    at the least magnitude: long-K cases).  pwide: the share of wide weights.  scale 2^e, e uniform in sexp; integer bias up to
+    +-ab -- abig = (lo, hi): on about half of the channels of magnitude lo .. hi, which moves those channels' outputs into
+    the binades where the SECOND rounding of an output split is inexact; integer residual up to +-ar.  form "h2": the product
+    of a 13-bit x and a 12-bit w alone would exceed 2^24, so wide weights sit on the input channels c % 8 == 0 and wide
+    activations on the others.  plain_x ("hi" only): x is a bf16 tensor, not planes."""
     N, H, W, Cin, Cout, R, stride, pad, dil = shape
+    T = SP_FORMS[form][0]
+    assert not plain_x or form == "hi"
     g = torch.Generator().manual_seed(seed)
     x = _ints(g, (N, H, W, Cin), 8)
-    big = torch.rand(x.shape, generator=g) < (0.03125 if wide_w else 0.125)
-    x = torch.where(big, _ints(g, x.shape, 4096), x)
+    if pbig is None:
+        pbig = 0.03125 if wide_w else 0.125
+    big = torch.rand(x.shape, generator=g) < pbig
+    wc = (torch.arange(Cin) % 8 == 0) if (form == "h2" and wide_w) else torch.zeros(Cin, dtype=torch.bool)
+    if xband is None:
+        wide_x = _ints(g, x.shape, xbig)
+    else:
+        wide_x = (_ints(g, x.shape, xband[1], lo=xband[0]).long() | 1).double() * (2 * torch.randint(0, 2, x.shape, generator=g) - 1)
+    x = torch.where(big & ~wc, wide_x, x)
     w = _ints(g, (Cout, R, R, Cin), 4)
     if wide_w:
-        pick = torch.rand(w.shape, generator=g) < 0.03125
-        vals = torch.tensor([257.0, 259.0, 515.0, -257.0, -259.0, -515.0], dtype=torch.float64)
+        pick = torch.rand(w.shape, generator=g) < (8 * pwide if form == "h2" else pwide)
+        if form == "h2":
+            pick = pick & wc
+        mags = torch.tensor(_WIDE_W[T], dtype=torch.float64)
+        vals = torch.cat([mags, -mags])
         w = torch.where(pick, vals[torch.randint(0, 6, w.shape, generator=g)], w)
-    scale = torch.pow(2.0, torch.randint(-1, 1, (Cout,), generator=g).double()).float()
-    bias = _ints(g, (Cout,), 16).float()
+    scale = torch.pow(2.0, torch.randint(sexp[0], sexp[1] + 1, (Cout,), generator=g).double()).float()
+    bias = _ints(g, (Cout,), ab).float()
     Ho, Wo = out_hw(shape)
-    res = _ints(g, (N, Ho, Wo, Cout), 1024).float() if use_res else None
-    return SimpleNamespace(shape=tuple(shape), relu=int(relu), x=x.float(), w=w.float(), scale=scale, bias=bias, res=res)
+    res = _ints(g, (N, Ho, Wo, Cout), ar).float() if use_res else None
+    if abig is not None:
+        wide_b = _ints(g, (Cout,), abig[1], lo=abig[0]) * (2 * torch.randint(0, 2, (Cout,), generator=g) - 1)
+        bias = torch.where(torch.rand((Cout,), generator=g) < 0.5, wide_b.float(), bias)
+    if plain_x:
+        x = x.to(T).double()
+    return SimpleNamespace(shape=tuple(shape), form=form, pdt=T, plain_x=plain_x, relu=int(relu), x=x.float(), w=w.float(),
+                           scale=scale, bias=bias, res=res, _sp=None)
 
 
-def reference_sp(case, out_mode):
-    """(y, bound / g): the DOCUMENTED contraction x_hi.Wh + x_lo.Wh + x_hi.Wl in float64 (x_lo.Wl is not part of it), planes and
-    weight split computed here by the same two roundings; the residual enters as hi + lo; out_mode "f32": the f32 value, "planes":
-    [bf16(y) | bf16(y - bf16(y))] along the channel axis."""
-    N, H, W, Cin, Cout, R, stride, pad, dil = case.shape
-    xh, xl = split_hi_lo(case.x)
-    wh, wl = split_hi_lo(case.w)
-    assert torch.equal(xh.double() + xl.double(), case.x.double()) and bool((xl != 0).any())
-    terms = ((xh, wh), (xl, wh), (xh, wl))
-    acc = sum(conv_f64(a, b, stride, pad, dil) for a, b in terms)
-    amax = float(sum(conv_f64(a.double().abs(), b.double().abs(), stride, pad, dil) for a, b in terms).max())
-    res = None
+SP_FAULTS = ("drop_xlo_wh", "drop_xhi_wl", "add_xlo_wl", "drop_res_lo", "trunc_lo", "shift_lo", "w_unrounded", "wrap_early",
+             "hi_reads_lo", "trunc_plain")
+
+
+def sp_fault_applies(case, out_mode, fault):
+    """whether the planted fault is one this case can show (it has that term / operand / output)"""
+    form = getattr(case, "form", "x3")
+    return {"drop_xlo_wh": form in ("x3", "h2"), "drop_xhi_wl": form == "x3" and bool(_sp_setup(case).wl_any),
+            "add_xlo_wl": form == "x3" and bool(_sp_setup(case).wl_any), "drop_res_lo": case.res is not None,
+            "trunc_lo": out_mode == "planes", "shift_lo": out_mode == "planes",
+            "w_unrounded": form == "h2" and not torch.equal(case.w.to(torch.float16).float(), case.w),
+            "wrap_early": form == "x3", "hi_reads_lo": form == "hi" and not case.plain_x,
+            "trunc_plain": out_mode == "plain"}[fault]
+
+
+def _sp_setup(case):
+    """the case's operands as the kernel contracts them, computed once: blocks [(a_i, b_i)] of the K axis per tap (f64), the exact
+    accumulator, max conv(|a|, |b|), the residual as hi + lo"""
+    if getattr(case, "_sp", None) is not None:
+        return case._sp
+    form = getattr(case, "form", "x3")
+    T = SP_FORMS[form][0]
+    geo = case.shape[6:]
+    xh, xl = split_hi_lo(case.x, T)
+    assert torch.equal(xh.double() + xl.double(), case.x.double()) and float(case.x.abs().max()) < MAX_FINITE[T]
+    if form == "x3":
+        wh, wl = split_hi_lo(case.w, T)
+        blocks = [(xh, wh), (xl, wh), (xh, wl)]
+    else:
+        wh, wl = case.w.to(T), None
+        blocks = [(xh, wh), (xl, wh)] if form == "h2" else [(xh, wh)]
+    blocks = [(a.double(), b.double()) for a, b in blocks]
+    A = torch.cat([a for a, _ in blocks], dim=-1)
+    Wk = torch.cat([b for _, b in blocks], dim=-1)
+    s = SimpleNamespace(T=T, geo=geo, xh=xh.double(), xl=xl.double(), wh=wh.double(), wl=None if wl is None else wl.double(),
+                        wl_any=wl is not None and bool((wl != 0).any()), blocks=blocks, A=A, Wk=Wk)
+    s.acc = conv_f64(A, Wk, *geo)
+    s.amax = float(conv_f64(A.abs(), Wk.abs(), *geo).max())
+    s.res = s.res_hi = None
     if case.res is not None:
-        rh, rl = split_hi_lo(case.res)
-        res = rh.double() + rl.double()
-        assert torch.equal(res, case.res.double())
-    bound, g = exactness(amax, 1.0, case.scale, case.bias, 0.0 if res is None else float(res.abs().max()))
+        rh, rl = split_hi_lo(case.res, T)
+        s.res_hi = rh.double()
+        s.res = rh.double() + rl.double()
+        assert torch.equal(s.res, case.res.double())
+    bound, g = exactness(s.amax, 1.0, case.scale, case.bias, 0.0 if s.res is None else float(s.res.abs().max()))
     assert bound / g < LIMIT, "SP case not exact: %g" % (bound / g)
-    v = case.acc_v = activation(acc * case.scale.double() + case.bias.double() + (0 if res is None else res), case.relu)
+    s.ratio = bound / g
+    case._sp = s
+    return s
+
+
+def sp_value(case, fault=None):
+    """the exact f32 value y before the output stage, as float64 (fault: one of the contraction / residual faults of SP_FAULTS)"""
+    s = _sp_setup(case)
+    acc, res = s.acc, s.res
+    if fault == "drop_xlo_wh":
+        acc = acc - conv_f64(s.xl, s.wh, *s.geo)
+    elif fault == "drop_xhi_wl":
+        acc = acc - conv_f64(s.xh, s.wl, *s.geo)
+    elif fault == "add_xlo_wl":
+        acc = acc + conv_f64(s.xl, s.wl, *s.geo)
+    elif fault == "hi_reads_lo":                           # the "hi" form contracting the lo plane as well
+        acc = acc + conv_f64(s.xl, s.wh, *s.geo)
+    elif fault == "w_unrounded":
+        acc = acc + conv_f64(s.xh + s.xl, case.w.double() - s.wh, *s.geo)
+    elif fault == "wrap_early":
+        # the kernel's K index of one tap runs over [hi | lo | hi'] with hi' = source channel k - kwrap, kwrap = 2C.  Wrapped one
+        # 64-element K-tile early (kwrap = 2C - 64) in the centre tap: k in [2C - 64, 3C) reads source channel k - 2C + 64
+        C = case.shape[3]
+        src = torch.cat([s.xh, s.xl], dim=-1)
+        k = torch.arange(3 * C)
+        bad = src[..., torch.where(k >= 2 * C - 64, k - (2 * C - 64), k)]
+        r = case.shape[5] // 2
+        wt = torch.zeros_like(s.Wk)
+        wt[:, r, r] = s.Wk[:, r, r]
+        acc = acc + conv_f64(bad - s.A, wt, *s.geo)
+    elif fault == "drop_res_lo":
+        res = s.res_hi
+    v = activation(acc * case.scale.double() + case.bias.double() + (0 if res is None else res), case.relu)
+    if fault is None:
+        assert torch.equal(v.float().double(), v)
+    return v
+
+
+def sp_output(v, T, out_mode, fault=None):
+    """the output stage: "f32" the value; "planes" [T(y) | T(y - T(y))] along the channel axis; "plain" ONE nearest-even conversion.
+    faults: "trunc_lo" the lo plane by truncation, "shift_lo" the lo plane taken from the neighbouring 8-column vector,
+    "trunc_plain" the plain conversion by truncation."""
     y = v.float()
-    assert torch.equal(y.double(), v)
+    if out_mode == "f32":
+        return y
+    if out_mode == "plain":
+        return convert(v, T, trunc=fault == "trunc_plain")
+    assert out_mode == "planes"
+    hi, lo = split_hi_lo(y, T, trunc_lo=fault == "trunc_lo")
+    if fault == "shift_lo":
+        lo = lo.roll(8, dims=-1)
+    return torch.cat([hi, lo], dim=-1)
+
+
+def reference_sp(case, out_mode, fault=None):
+    """(y, bound / g): the documented contraction of the case's operand form in float64 (SP_FORMS), the residual entering as
+    hi + lo of its own split, FrozenBN, the activation, then the output stage of `out_mode` (sp_output).  The exactness
+    condition (and, for f16, |y| < 65504) is asserted.  The fault-free result is computed once per (case, out_mode)."""
+    s = _sp_setup(case)
+    cache = s.__dict__.setdefault("out", {})
+    if fault is None and out_mode in cache:
+        return cache[out_mode], s.ratio
+    v = sp_value(case, fault if fault not in ("trunc_lo", "shift_lo", "trunc_plain") else None)
+    if fault is None:
+        case.acc_v = v
+    y = sp_output(v, s.T, out_mode, fault)
+    if fault is None:
+        if out_mode != "f32":          # (f16 planes and plain outputs: every value below 65504)
+            assert float(v.abs().max()) < MAX_FINITE[s.T], "the output leaves %s's finite range: %g" % (s.T, float(v.abs().max()))
+        cache[out_mode] = y
+    return y, s.ratio
+
+
+def sp_shares(case, out_mode):
+    """shares of elements that exercise the fault classes: in_lo / res_lo -- input / residual elements with a non-zero lo plane;
+    for a planes output,
+    out_lo -- outputs with a non-zero lo, out_inexact2 -- outputs whose second rounding is inexact (hi + lo != y); for a 16-bit
+    plain output, rounded / ties as rounding_shares"""
+    s = _sp_setup(case)
+    v = sp_value(case)
+    d = {"in_lo": (s.xl != 0).double().mean().item()}
+    if s.res is not None:
+        d["res_lo"] = (s.res != s.res_hi).double().mean().item()
     if out_mode == "planes":
-        hi, lo = split_hi_lo(y)
-        y = torch.cat([hi, lo], dim=-1)
-    return y, bound / g
+        hi, lo = split_hi_lo(v.float(), s.T)
+        d["out_lo"] = (lo != 0).double().mean().item()
+        d["out_inexact2"] = (hi.double() + lo.double() != v).double().mean().item()
+    elif out_mode == "plain":
+        d["rounded"], d["ties"] = rounding_shares(v, s.T)
+    return d
+
+
+# ------------------------------------------------------------------------------------------------ Bottleneck.run_sp
+# mode -> (operand form of the 1x1 convs, dtype of planes, dtype of the plain tensors inside the block or None)
+SP_BLOCK_MODES = {"x3": ("x3", torch.bfloat16, None), "h2": ("h2", torch.float16, None), "wide": ("hi", torch.bfloat16, torch.bfloat16)}
+# kind -> (Cin, mid, Cout, stride, dilation, downsample)
+SP_BLOCK_KINDS = {"identity": (256, 64, 256, 1, 1, False), "down-s2": (128, 64, 256, 2, 1, True),
+                  "down-dil2": (128, 64, 256, 2, 2, True)}
+
+
+def make_sp_block_case(kind, hw, seed, plain_x=False):
+    """a bottleneck on integers for Bottleneck.run_sp: x >= 0 (it follows a ReLU), mostly 0 .. 4, one element in 16 up to 4095
+    (twelve bits: the lo plane of the block's input -- its identity -- is non-zero in bf16 and in f16); sparse weights in
+    {-1, 0, 1} (three in four are zero: the accumulators grow slowly enough for three exact layers on 12-bit inputs);
+    power-of-two scales, integer bias.  plain_x: x is rounded to bf16 (the stem's output in "wide" mode)."""
+    Cin, mid, Cout, stride, dil, ds = SP_BLOCK_KINDS[kind]
+    N, H, W = hw
+    g = torch.Generator().manual_seed(seed)
+    x = _ints(g, (N, H, W, Cin), 4, lo=0)
+    x = torch.where(torch.rand(x.shape, generator=g) < 1.0 / 16, _ints(g, x.shape, 4095, lo=0), x)
+    if plain_x:
+        x = x.to(torch.bfloat16).double()
+    shapes = [(mid, 1, 1, Cin), (mid, 3, 3, mid), (Cout, 1, 1, mid)] + ([(Cout, 1, 1, Cin)] if ds else [])
+    ws = [torch.where(torch.rand(s, generator=g) < 0.25, _ints(g, s, 1), torch.zeros(s, dtype=torch.float64)) for s in shapes]
+    exps = [(-2, -1), (-2, -1), (-2, -1), (-1, 0)]
+    sb = []
+    for i, wt in enumerate(ws):
+        n = wt.shape[0]
+        sb.append((torch.pow(2.0, torch.randint(exps[i][0], exps[i][1] + 1, (n,), generator=g).double()).float(),
+                   _ints(g, (n,), 8).float()))
+    return SimpleNamespace(kind=kind, hw=tuple(hw), plain_x=plain_x, x=x.float(), w=[t.float() for t in ws], sb=sb)
+
+
+def reference_sp_block(case, mode, plain_out, fault=None):
+    """(y, [bound / g per layer], [share of non-zero lo per hand-off]): the block in float64 with the hand-off of `mode` between
+    the layers -- a planes mode ("x3", "h2"): every layer's f32 result is split [T(y) | T(y - T(y))] and the next layer reads
+    exactly hi and lo, through that mode's contraction; "wide": conv1 reads the hi plane of x (or the plain x) and writes ONE
+    bf16 conversion, conv2 is the plain bf16 conv, conv3 reads that tensor, adds the identity's hi + lo and splits.  The weights
+    are integers that T holds, so W = T(W) and the x3 lo part is zero: a block checks where the planes go, the conv table
+    the contraction's terms.  plain_out: the block's result as the mode's plain output (x3 / h2: f32; wide: one bf16 conversion)
+    instead of planes.  The exactness condition is asserted for every layer.
+    fault (tests of the check): "identity_hi" the identity's lo plane dropped, "ds_dense" the downsample taken from the
+    pixel to the right of the one its stride reads."""
+    form, T, plain = SP_BLOCK_MODES[mode]
+    Cin, mid, Cout, stride, dil, ds = SP_BLOCK_KINDS[case.kind]
+    cstride = 1 if dil > 1 else stride                      # (a dilated block runs at stride 1: conv1 and the downsample)
+    ratios, lo_shares = [], []
+
+    def planes(v):                                          # f32 value -> (hi, lo) as float64
+        hi, lo = split_hi_lo(v.float(), T)
+        lo_shares.append((lo != 0).double().mean().item())
+        return hi.double(), lo.double()
+
+    def layer(inp, g_in, i, st, pad, dl, res, g_res, relu):
+        """inp: (hi, lo) planes or a plain tensor; the contraction of the mode's form with integer weights"""
+        w, (sc, bi) = case.w[i].double(), case.sb[i]
+        assert torch.equal(w.to(T).double(), w)
+        if isinstance(inp, tuple):
+            a = inp[0] if form == "hi" else inp[0] + inp[1]
+        else:
+            a = inp
+        acc = conv_f64(a, w, st, pad, dl)
+        amax = float(conv_f64(a.abs() if form == "hi" or not isinstance(inp, tuple) else inp[0].abs() + inp[1].abs(), w.abs(),
+                              st, pad, dl).max())
+        r = None if res is None else res[0] + res[1]
+        bound, g = exactness(amax, g_in, sc, bi, 0.0 if r is None else float(r.abs().max()), g_res)
+        assert bound / g < LIMIT, "layer %d not exact: %g / %g" % (i, bound, g)
+        ratios.append(bound / g)
+        v = acc * sc.double() + bi.double() + (0 if r is None else r)
+        v = v.clamp(min=0) if relu else v
+        assert torch.equal(v.float().double(), v) and float(v.abs().max()) < MAX_FINITE[T]
+        return v, g
+
+    x = case.x.double()
+    xin = x if case.plain_x else planes(x)
+    if case.plain_x:
+        assert mode == "wide" and ds and torch.equal(x.to(T).double(), x)
+    if ds:
+        if fault == "ds_dense":
+            v, g_id = layer(xin, 1.0, 3, 1, 0, 1, None, 1.0, False)
+            v = v.roll(-1, dims=2)[:, ::cstride, ::cstride]
+        else:
+            v, g_id = layer(xin, 1.0, 3, cstride, 0, 1, None, 1.0, False)
+        ident = planes(v)
+    else:
+        ident, g_id = xin, 1.0
+    if fault == "identity_hi":
+        ident = (ident[0], torch.zeros_like(ident[1]))
+    v1, g1 = layer(xin, 1.0, 0, cstride, 0, 1, None, 1.0, True)
+    if plain is None:
+        v2, g2 = layer(planes(v1), g1, 1, 1, dil, dil, None, 1.0, True)
+        t2 = planes(v2)
+    else:
+        v2, g2 = layer(v1.to(plain).double(), g1, 1, 1, dil, dil, None, 1.0, True)
+        t2 = v2.to(plain).double()
+    v3, _ = layer(t2, g2, 2, 1, 0, 1, ident, g_id, True)
+    if plain_out:
+        y = v3.float() if plain is None else v3.to(plain)
+    else:
+        y = torch.cat(split_hi_lo(v3.float(), T), dim=-1)
+    return y, ratios, lo_shares
 
 
 # ------------------------------------------------------------------------------------------------ 4x4 stride-2 deconvolution
@@ -424,6 +676,62 @@ SP_CASES = [
     ((1, 19, 23, 64, 64, 3, 1, 1, 1), False, 1, False),
     ((1, 13, 15, 128, 264, 1, 1, 0, 1), True, 0, True),
 ]
+# The split-precision table: every operand form, launch class x row count, output mode x residual, activation, Cout class and
+# geometry of the SP kernels at least once.  kind 7 streaming / 8 matrix and the rows are what the library's own rule must give
+# (mega_conv2d_nhwc_sp_plan; asserted on the CPU and again before every GPU comparison).  The 256-row instantiation is chosen
+# only where it saves a round of the 256 CUs: Cout 2048 with 6144 < M <= 8192.
+# form "hi-plain": the "hi" form fed a plain bf16 tensor.  pad_cols > 0: the caller's out= buffer, ldo = Cout + pad_cols.
+# knobs: make_sp_case's ranges where the defaults would break a condition (exactness; |y| < 65504 in f16; the 1 % shares).
+_P = dict
+_B18 = (1 << 17, 1 << 18)
+_H2 = _P(sexp=(-9, -8), ab=64, ar=4095, pbig=0.125)                   # g = 2^-9: bound / g < 2^24 keeps every |y| below 32768
+# (id, shape, form, wide_w, relu, use_res, out_mode, pad_cols, kind, rows, knobs)
+SP_TABLE = [
+    # 256 rows, streaming (K = 192): split residual and split output through the MF1 = 2 residual prefetch
+    ("s256-x3-res-planes", (1, 50, 124, 64, 2048, 1, 1, 0, 1), "x3", True, 1, True, "planes", 0, 7, 256, _P(abig=_B18)),
+    # 256 rows, matrix (K = 576): f32 output with a residual (the h4[d] / h4[2 + d] unpack)
+    ("m256-x3-res-f32", (1, 50, 124, 192, 2048, 1, 1, 0, 1), "x3", True, 0, True, "f32", 0, 8, 256, _P()),
+    # 256 rows in f16: [W | W] weights, no wrap, f16 lo plane written
+    ("s256-h2-planes", (1, 50, 124, 64, 2048, 1, 1, 0, 1), "h2", True, 1, False, "planes", 0, 7, 256, _P(_H2, abig=(17000, 24000))),
+    # Cout 64 with a residual: the waves whose columns do not exist are skipped (use_b0 / use_b1); 3x3 at C = 64
+    ("m192-x3-3x3-cout64-res", (1, 19, 23, 64, 64, 3, 1, 1, 1), "x3", False, 1, True, "planes", 0, 8, 192, _P(abig=_B18)),
+    # 3x3 at C = 128: the tap / plane wrap runs over two K-tiles per plane; Cout 128 with a residual; LeakyReLU
+    ("m192-x3-3x3-c128-leaky", (2, 13, 15, 128, 128, 3, 1, 1, 1), "x3", True, 2, True, "f32", 0, 8, 192, _P()),
+    # dilated 3x3, Cout 264 (second N tile of 8 columns), planes without a residual, no activation
+    ("m192-x3-dil2-planes", (1, 13, 15, 64, 264, 3, 1, 2, 2), "x3", True, 0, False, "planes", 0, 8, 192, _P(abig=_B18)),
+    # stride-2 1x1 on odd H and W (the downsample's stride on planes), M tail
+    ("s192-x3-stride2-res", (1, 13, 15, 128, 264, 1, 2, 0, 1), "x3", True, 1, True, "planes", 0, 7, 192, _P(abig=_B18)),
+    # f32 into the caller's buffer, ldo > Cout: nothing is written behind column Cout
+    ("s192-x3-f32-ldo", (1, 7, 9, 64, 136, 1, 1, 0, 1), "x3", True, 0, False, "f32", 8, 7, 192, _P()),
+    # "wide" conv1: the hi plane of planes whose lo plane is NOT zero, one plain bf16 conversion, Cout 8
+    ("s192-hi-plain-cout8", (1, 13, 15, 256, 8, 1, 1, 0, 1), "hi", True, 1, False, "plain", 0, 7, 192, _P(xbig=511, pbig=0.125)),
+    # "wide" conv3: a plain bf16 tensor in (ldi = C), split residual, split output
+    ("s192-hiplain-res-planes", (1, 13, 15, 64, 256, 1, 1, 0, 1), "hi-plain", True, 1, True, "planes", 0, 7, 192, _P(abig=_B18)),
+    # "wide" downsample of a dilated block: hi plane, matrix class (K = 576), planes without a residual, LeakyReLU
+    ("m192-hi-planes-leaky", (1, 9, 11, 576, 72, 1, 1, 0, 1), "hi", True, 2, False, "planes", 0, 8, 192, _P(abig=_B18)),
+    # plain bf16 with a residual into the caller's buffer
+    ("s192-hi-res-plain-ldo", (1, 7, 9, 128, 72, 1, 1, 0, 1), "hi", True, 0, True, "plain", 24, 7, 192, _P(xbig=511, pbig=0.125)),
+    # h2, 3x3 (K = 1152, matrix class): f16 split residual + f16 split output
+    ("m192-h2-3x3-res-planes", (1, 9, 11, 64, 72, 3, 1, 1, 1), "h2", True, 1, True, "planes", 0, 8, 192, _P(_H2, abig=(17000, 22000))),
+    # h2, f32 output with a residual, Cout 520 (third N tile of 8 columns), LeakyReLU
+    ("s192-h2-res-f32-leaky", (1, 13, 15, 128, 520, 1, 1, 0, 1), "h2", True, 2, True, "f32", 0, 7, 192, _P(_H2)),
+    # h2, plain f16 with a residual into the caller's buffer
+    ("s192-h2-res-plain-ldo", (1, 13, 15, 64, 72, 1, 1, 0, 1), "h2", True, 0, True, "plain", 8, 7, 192, _P(sexp=(-3, -2), ar=4095, pbig=0.125)),
+    # h2, plain f16, no residual, ReLU
+    ("s192-h2-plain", (1, 7, 9, 128, 264, 1, 1, 0, 1), "h2", False, 1, False, "plain", 0, 7, 192, _P(sexp=(-3, -2))),
+]
+# linear_sp above the library's split-K threshold (R S Cw >= 32768 -> three K ranges + finalize): (M, K, Nout), M = 37 and
+# Nout = 72 as LINEAR_SPLITK_SHAPE; wide activations are rare so that 10944 / 16384 products stay below 2^24
+SP_SPLITK = {"x3": (37, 10944, 72), "h2": (37, 16384, 72)}
+# (linear_sp has no FrozenBN scale: sexp = (0, 0) makes it 1)
+SP_SPLITK_KNOBS = {"x3": _P(pbig=1.0 / 32, xband=(257, 511), sexp=(0, 0)),
+                   "h2": _P(pbig=1.0 / 48, xband=(2049, 2303), pwide=1.0 / 128, sexp=(0, 0))}
+SP_LINEAR_T = (37, 192, 136, 64)                 # ops.linear / ops.linear_transposed through an X3Weight: (M, K, Nout, ld)
+# Bottleneck.run_sp: (kind, (N, H, W), plain_x) -- the downsample kinds on 13 x 15 (odd: the stride-2 tail); the last row is
+# "wide" only (a downsample block fed the stem's plain bf16 tensor)
+SP_BLOCKS = [("identity", (1, 9, 12), False), ("down-s2", (1, 13, 15), False), ("down-dil2", (1, 13, 15), False),
+             ("down-s2", (1, 13, 15), True)]
+
 # (N, H, W, Cin, C, Cs): the two smallest entries of test_kernels_gpu.DECONV_CASES
 DECONV_SHAPES = [(1, 4, 6, 386, 64, 128), (2, 7, 9, 770, 128, 256)]
 
@@ -469,6 +777,52 @@ def stem_case(hw):
 def sp_case(spec):
     shape, wide_w, relu, use_res = spec
     return make_sp_case(shape, wide_w, relu, use_res, seed=sum(shape))
+
+
+_SP_BUILT = {}
+
+
+def sp_table_case(row):
+    """the case of one SP_TABLE row, built once per process and never modified"""
+    name, shape, form, wide_w, relu, use_res, out_mode, pad_cols, kind, rows, knobs = row
+    if name not in _SP_BUILT:
+        _SP_BUILT[name] = make_sp_case(shape, wide_w, relu, use_res, seed=sum(shape) + len(name), form=form.split("-")[0],
+                                       plain_x=form == "hi-plain", **knobs)
+    return _SP_BUILT[name]
+
+
+def sp_gemm_shape(shape, form):
+    """(M, Cout, K, taps) of the launch: K = R S (blocks of the form) Cin, what mega_conv2d_nhwc_sp_plan takes"""
+    N, H, W, Cin, Cout, R, stride, pad, dil = shape
+    Ho, Wo = out_hw(shape)
+    return N * Ho * Wo, Cout, R * R * SP_FORMS[form.split("-")[0]][1] * Cin, R * R
+
+
+def sp_splitk_case(form):
+    M, K, Nout = SP_SPLITK[form]
+    key = "splitk-" + form
+    if key not in _SP_BUILT:
+        _SP_BUILT[key] = make_sp_case((M, 1, 1, K, Nout, 1, 1, 0, 1), True, 1, False, seed=K % 1009, form=form,
+                                      **SP_SPLITK_KNOBS[form])
+    return _SP_BUILT[key]
+
+
+def sp_linear_case(with_bias):
+    """the X3Weight case: scale 1; with_bias False (ops.linear_transposed takes none): bias 0"""
+    M, K, Nout, ld = SP_LINEAR_T
+    key = "linear-bias" if with_bias else "linear-t"
+    if key not in _SP_BUILT:
+        _SP_BUILT[key] = make_sp_case((M, 1, 1, K, Nout, 1, 1, 0, 1), True, 0, False, seed=M + K + int(with_bias), form="x3",
+                                      sexp=(0, 0), ab=16 if with_bias else 0)
+    return _SP_BUILT[key]
+
+
+def sp_block_case(spec):
+    kind, hw, plain_x = spec
+    key = ("block", kind, hw, plain_x)
+    if key not in _SP_BUILT:
+        _SP_BUILT[key] = make_sp_block_case(kind, hw, seed=sum(hw) + len(kind) + int(plain_x), plain_x=plain_x)
+    return _SP_BUILT[key]
 
 
 def deconv_case(shape, dtype):

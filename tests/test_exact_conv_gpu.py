@@ -5,9 +5,12 @@ the f32 accumulation is exact in any order and the only rounding is the one near
 kernel equals the float64 reference BIT FOR BIT (tests/test_exact_conv_cases.py checks those conditions, and that the comparison
 catches planted faults, on the CPU).  Every assertion here is assert_bits_equal against that reference: the register-staged tiles,
 igemm8 (matrix and streaming class, 256 and 192 rows), conv64, the two fused bottlenecks, split-K + finalize, the sub-pixel
-deconvolution, the four stem entry points and the split-precision (x3) kernels.  No number in this file is a tolerance.
+deconvolution, the four stem entry points and two small x3 cases of the split-precision kernels.  No number in this file is a
+tolerance.
 
-A new conv-family kernel or dispatch class adds its shapes here (testing)."""
+A new conv-family kernel or dispatch class adds its shapes here (testing).  The split-precision family -- every
+operand form (x3, h2, hi), launch class and row count, output mode, split-K, the X3Weight wrappers and Bottleneck.run_sp -- has
+its own table in tests/test_exact_sp_gpu.py, which grew out of section h below."""
 import pytest
 import torch
 
