@@ -14,6 +14,15 @@
  *     values bounded by 65 504; accumulation is f32 in every mode).  Wherever an entry point takes a dtype code, MEGA_F16
  *     is accepted where MEGA_BF16 is, unless its comment says otherwise (the split-precision plane kernels are bf16 only).
  *   - activations are NHWC; GEMM weights are OHWI ([Cout][R][S][Cin]) so both operands are K-contiguous.
+ *   - this header is the ONE declaration of the ABI.  The kernels' sources include it, so the compiler checks every
+ *     definition against its prototype, and the Python binding parses it (comments stripped) into its ctypes signatures
+ *     and structures.  The parser's grammar is deliberately tiny; keep every declaration inside it:
+ *       prototype   `RET mega_name(PARAMS);` -- RET is int, size_t, void or const char*; PARAMS is `void` or a comma list
+ *                   of named parameters, each int, float, long long, size_t or a pointer (anything with a `*`).
+ *       descriptor  `typedef struct { FIELDS } mega_name;` -- semicolon-ended fields of the parameter types, several
+ *                   names of one type separated by commas (`int ldq, ldk;`).
+ *     Anything else (a double or unsigned parameter, an array field, a struct by value) makes the binding raise, naming
+ *     the line.
  *
  * Each prototype cites the reference interface it replaces (paths relative to the reference tree
  * Scalsol/mega.pytorch).
@@ -316,10 +325,11 @@ int mega_dff_warp_scale(const void* feats, const float* flow, const void* scale,
 
 /* Pool / key-set assembly of the batched relation aggregation: n block copies (rows x row_bytes bytes, independent
  * source / destination row strides) in one launch -- replaces the reference's per-key-frame torch.cat of its pools
- * (roi_box_feature_extractors.py:676,:687-688,:812-814; generalized_rcnn_mega.py:213-216).  segs = array of
- *   struct { const void* src; void* dst; long long src_stride, dst_stride; int rows, row_bytes; }
- * Destinations must not overlap; addresses / strides / row lengths 2-byte aligned at least.  Bit-exact data movement. */
-int mega_copy_segments(const void* segs, int n, void* stream);
+ * (roi_box_feature_extractors.py:676,:687-688,:812-814; generalized_rcnn_mega.py:213-216).  segs = mega_copy_seg[n], host
+ * memory; strides in bytes.  Destinations must not overlap; addresses / strides / row lengths 2-byte aligned at least.
+ * Bit-exact data movement. */
+typedef struct { const void* src; void* dst; long long src_stride, dst_stride; int rows, row_bytes; } mega_copy_seg;
+int mega_copy_segments(const mega_copy_seg* segs, int n, void* stream);
 
 /* The identity bottleneck of the backbone's full-resolution stage -- layer1 blocks 1, 2 of ResNet-50/101-C4
  * (backbone/resnet.py:324-344: 256 -> 64 (1x1) -> 64 (3x3, pad 1) -> 256 (1x1) channels, stride 1, FrozenBN as f32
@@ -396,7 +406,7 @@ int mega_conv2d_nhwc_sp_plan(int M, int Cout, int K, int taps, int out_mode, int
  * MEGA_F16; row_bytes =
  * SOURCE bytes per row, a multiple of 32; 16-byte aligned on both sides): a concatenation of f32 row blocks delivered as the
  * rounded copy the bf16 projections read (roi_box_feature_extractors.py:812-814 pools with an f32 activation stream). */
-int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, void* stream);
+int mega_copy_cast_segments_dt(const mega_copy_seg* segs, int n, int dtype, void* stream);
 
 /* dst[i] = half(src[i]) (round to nearest even; dtype = MEGA_BF16 / MEGA_F16), n contiguous elements, both pointers 16-byte
  * aligned: the rounded copy of the head's f32 activation stream that the 16-bit Wq / Wk / Wv projections read
@@ -425,12 +435,12 @@ typedef struct {
   int ldv2;
   int reserved;
 } mega_attn_desc;
-int mega_relation_attention_batched(const void* descs /* mega_attn_desc[n], host memory */, int n, int groups,
+int mega_relation_attention_batched(const mega_attn_desc* descs /* [n], host memory */, int n, int groups,
                                     float scale, int dtype, void* stream);
 
 /* mega_position_logits_tiled_dt for n <= 20 (query boxes, key boxes) problems in one launch (mega_position_logits_tiled_batched_dt);
  * the single entry point launches a batch of one. */
-typedef struct { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; } mega_pos_desc;
+typedef struct { const float* rois_q; const float* rois_k; void* out; int Nq, Nk; } mega_pos_desc;
 
 /* Round 6: the head on IEEE-half operands (cfg.HEAD_DTYPE "float16": Q K^T, P V and the position term on
  * v_mfma_f32_32x32x16_f16 / 16x16x32_f16 -- the bf16 rate and bytes, 11 significant bits instead of 8).  The three
@@ -440,7 +450,7 @@ typedef struct { const float* rois_q; const float* rois_k; void* out_bf16; int N
  * roi_box_feature_extractors.py:126-176 (position embedding), :567-646 (attention_module_multi_head). */
 int mega_position_logits_tiled_dt(const float* rois_q, const float* rois_k, const float* wg_t, const float* bg,
                                   const float* dim_mat, void* out16, int Nq, int Nk, int dtype, void* stream);
-int mega_position_logits_tiled_batched_dt(const void* descs /* mega_pos_desc[n], host memory */, int n, const float* wg_t,
+int mega_position_logits_tiled_batched_dt(const mega_pos_desc* descs /* [n], host memory */, int n, const float* wg_t,
                                           const float* bg, const float* dim_mat, int dtype, void* stream);
 int mega_relation_attention_tiled_pos_dt(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv,
                                          const void* pos_tiled16, const void* resid, int ldr, const float* bias_v,

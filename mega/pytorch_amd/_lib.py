@@ -1,120 +1,100 @@
-"""ctypes binding of libmega_hip.so (include/mega_hip.h).
+"""ctypes binding of libmega_hip.so, derived from include/mega_hip.h.
 
-The product path has NO fallback: if the library is missing or a call fails, this raises.
+The header is the one declaration of the C ABI: the kernels' sources include it (the compiler checks every definition
+against its prototype) and this module parses it into SIGNATURES, PARAMS and STRUCTS.  Nothing here is typed by hand, so a
+new entry point needs its prototype in the header, its definition under csrc/ and a wrapper in ops.py.  The grammar the
+parser accepts is stated in the header's "Boundary rules"; a declaration outside it raises, naming the line.
+
+The product path has NO fallback: if the library or the header is missing or a call fails, this raises.
 """
 import ctypes
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmega_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(HERE, "..", "..", "include", "mega_hip.h"))
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_longlong = ctypes.c_longlong
 
 _ERR = {1: "bad argument", 2: "kernel launch failure", 3: "workspace too small", 4: "kernel loop bound exceeded"}
 
-# name -> (restype, argtypes).  Must list every symbol declared in include/mega_hip.h.
-SIGNATURES = {
-    "mega_conv2d_nhwc": (c_int, [c_void_p] * 6 + [c_int] * 15 + [c_void_p]),
-    "mega_conv2d_nhwc_ws": (c_int, [c_void_p] * 6 + [c_int] * 15 + [c_void_p, c_size_t, c_void_p]),
-    "mega_conv2d_nhwc_workspace_bytes": (c_size_t, [c_int] * 3),
-    "mega_conv2d_nhwc_rs": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
-    "mega_stem_conv_bn_relu": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
-    "mega_stem_conv_bn_relu_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
-    "mega_stem_conv_bn_relu_bf16_u8": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float] * 3 + [c_int, c_void_p]),
-    "mega_stem_pool_dt": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_float] * 3 + [c_int, c_int, c_void_p]),
-    "mega_stem_pool_tile": (None, [c_void_p, c_void_p]),
-    "mega_maxpool3x3s2_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
-    "mega_avgpool2x2_ceil_nhwc": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
-    "mega_roi_align_fwd": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_int] * 7 + [c_void_p]),
-    "mega_nms_full_workspace_bytes": (c_size_t, [c_int]),
-    "mega_nms": (c_int, [c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mega_nms_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_nms_sorted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_int, c_int] + [c_void_p] * 4 +
-                        [c_size_t, c_void_p]),
-    "mega_rpn_select_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_rpn_select_idx": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_int, c_float, c_float, c_float] +
-                            [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "mega_postprocess_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_postprocess": (c_int, [c_void_p] * 4 + [c_int, c_int] + [c_float] * 8 + [c_int, c_int] + [c_void_p] * 6 +
-                         [c_size_t, c_void_p]),
-    "mega_postprocess_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "mega_postprocess_batched": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int] + [c_float] * 8 + [c_int, c_int] +
-                                 [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "mega_postprocess_candidates_batched": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_float] * 7 + [c_void_p] * 3),
-    "mega_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 4),
-    "mega_bbox_aug_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_float, c_float, c_int, c_int] +
-                            [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "mega_soft_merge_workspace_bytes": (c_size_t, [c_int] * 4),
-    "mega_soft_merge": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 +
-                        [c_float, c_float, c_int, c_int, c_float, c_int, c_float, c_int, c_int] + [c_void_p] * 5 +
-                        [c_size_t, c_void_p]),
-    "mega_position_logits": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
-    "mega_relation_attention_splits": (c_int, [c_int, c_int, c_int]),
-    "mega_relation_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "mega_relation_attention": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                        c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                                        c_int, c_void_p, c_size_t, c_void_p]),
-    "mega_relation_attention_batched": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
-    "mega_position_logits_tiled_dt": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
-    "mega_position_logits_tiled_batched_dt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "mega_relation_attention_tiled_pos_dt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                                     c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                                     c_float, c_int, c_void_p, c_size_t, c_void_p]),
-    "mega_conv2d_nhwc_tile": (c_int, [c_int] * 3),
-    "mega_conv2d_nhwc_plan": (c_int, [c_int] * 4),
-    "mega_conv2d_nhwc_plan_ex": (c_int, [c_int] * 14),
-    "mega_preprocess_frames": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 3 + [c_int, c_void_p]),
-    "mega_dff_warp_scale": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
-    "mega_fgfa_pair_taps": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
-    "mega_resize_bilinear_u8": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                                                      c_int, c_void_p]),
-    "mega_resize_bilinear_u8_flip": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p,
-                                                                           c_void_p, c_int, c_int, c_void_p]),
-    "mega_fgfa_warp_aggregate": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
-    "mega_fgfa_warp_aggregate_ring": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
-    "mega_copy_segments": (c_int, [c_void_p, c_int, c_void_p]),
-    "mega_bottleneck64_fwd_dt": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
-    "mega_bottleneck64_even_fwd_dt": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
-    "mega_bottleneck64_ds_fwd_dt": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_void_p]),
-    "mega_cast_f32_to_half": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "mega_copy_cast_segments_dt": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "mega_split_f32_to_bf16x3": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "mega_split_f32_to_planes_dt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "mega_roi_align_fwd_planes_dt": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] + [c_int] * 4 + [c_void_p]),
-    "mega_conv2d_nhwc_sp_dt": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                       c_int] + [c_int] * 12 + [c_void_p, c_size_t, c_void_p]),
-    "mega_conv2d_nhwc_sp_plan": (c_int, [c_int] * 6),
-    "mega_conv2d_nhwc_ks_workspace_bytes": (c_size_t, [c_int] * 5),
-    "mega_conv2d_nhwc_ks": (c_int, [c_void_p] * 6 + [c_int] * 16 + [c_void_p, c_size_t, c_void_p]),
-    "mega_conv2d_nhwc_subpixel": (c_int, [c_void_p] * 4 + [c_int] * 13 + [c_void_p, c_size_t, c_void_p]),
-    "mega_flow_level_assemble": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
-    "mega_flow_pred_finish": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
-    "mega_flow_conv1_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong, c_int, c_int, c_void_p]),
-    "mega_fgfa_warp_aggregate_ring_pos": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_int, c_void_p]),
-    "mega_fgfa_warp_aggregate_ring_pos_batched": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_int, c_int, c_int, c_void_p]),
-    "mega_vid_eval_match": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_longlong, c_int] + [c_void_p] * 4),
-    "mega_vid_eval_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
-    "mega_vid_eval_ap": (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong] + [c_void_p] * 2 + [c_size_t, c_void_p]),
-    "mega_proposal_recall_match": (c_int, [c_void_p] * 7 + [c_int, c_int, c_longlong, c_longlong, c_int, c_int] +
-                                   [c_void_p] * 3),
-    "mega_seq_nms_workspace_bytes": (c_size_t, [c_longlong, c_longlong]),
-    "mega_seq_nms": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int] + [c_void_p] * 4 +
-                     [c_size_t, c_void_p]),
-    "mega_link_tracks_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_link_tracks": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_longlong, c_float, c_float, c_int, c_int] +
-                         [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "mega_tubelet_match_workspace_bytes": (c_size_t, [c_longlong]),
-    "mega_tubelet_match": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_longlong] * 7 + [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "mega_tubelet_scores": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_void_p]),
-    "mega_motion_iou_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
-    "mega_motion_iou": (c_int, [c_void_p] * 5 + [c_int, c_longlong, c_int, c_int] + [c_void_p] * 3 + [c_size_t, c_void_p]),
-    "mega_overlay_detections_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "mega_overlay_detections": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                        c_float, c_float, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "mega_last_error_string": (ctypes.c_char_p, []),
-}
+_SCALARS = {"int": c_int, "float": c_float, "long long": c_longlong, "size_t": c_size_t}
+_RETURNS = {"int": c_int, "size_t": c_size_t, "void": None, "const char*": ctypes.c_char_p}
+
+
+def _declarator(decl):
+    """`TYPE name` -> (name, ctype); any pointer is a c_void_p.  None outside the grammar."""
+    m = re.match(r"^(.*?)\s*(\w+)$", decl.strip())
+    if not m:
+        return None
+    if "*" in m.group(1):
+        return m.group(2), c_void_p
+    typ = _SCALARS.get(" ".join(m.group(1).split()))
+    return None if typ is None else (m.group(2), typ)
+
+
+def parse_header(text, path="mega_hip.h"):
+    """The declarations of a header in the grammar of mega_hip.h's "Boundary rules" ->
+    ({name: (restype, argtypes)}, {name: parameter names}, {typedef name: ctypes.Structure subclass})."""
+    # comments become their own newlines, so that a position still tells its line
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: "\n" * m.group(0).count("\n"), text, flags=re.S)
+    text = re.sub(r'^[ \t]*#[^\n]*|^extern "C" \{$|^\}$', "", text, flags=re.M)      # preprocessor lines, the extern "C" block
+    signatures, params, structs = {}, {}, {}
+    end = 0
+    for st in re.finditer(r"((?:[^;{]|\{[^}]*\})*);", text):
+        end = st.end()
+        decl = " ".join(st.group(1).split())
+        if not decl:
+            continue
+
+        def bad(why):
+            return ValueError("%s:%d: %s -- outside the binding's grammar (see the header's Boundary rules): %r"
+                              % (path, text.count("\n", 0, st.end(1) - len(st.group(1).lstrip())) + 1, why, decl))
+
+        m = re.match(r"^typedef struct \{(.*)\} (mega_\w+)$", decl)
+        if m:
+            fields = []
+            for field in filter(None, (f.strip() for f in m.group(1).split(";"))):
+                names = [n.strip() for n in field.split(",")]
+                first = _declarator(names[0])
+                if first is None or not all(re.match(r"^\w+$", n) for n in names[1:]):
+                    raise bad("field `%s`" % field)
+                fields += [first] + [(n, first[1]) for n in names[1:]]
+            structs[m.group(2)] = type(m.group(2), (ctypes.Structure,), {"_fields_": fields})
+            continue
+        m = re.match(r"^(.*?)\s*\b(mega_\w+)\s*\((.*)\)$", decl)
+        if not m:
+            raise bad("neither a prototype nor a typedef struct")
+        ret = re.sub(r"\s*\*\s*", "*", m.group(1))
+        if ret not in _RETURNS:
+            raise bad("return type `%s`" % m.group(1))
+        args = [] if m.group(3).strip() == "void" else [(p, _declarator(p)) for p in m.group(3).split(",")]
+        for p, d in args:
+            if d is None:
+                raise bad("parameter `%s`" % p.strip())
+        signatures[m.group(2)] = (_RETURNS[ret], [d[1] for _, d in args])
+        params[m.group(2)] = tuple(d[0] for _, d in args)
+    rest = text[end:].lstrip()
+    if rest:
+        raise ValueError("%s:%d: unterminated declaration: %r" % (path, text.count("\n", 0, len(text) - len(rest)) + 1,
+                                                                   rest.strip()))
+    return signatures, params, structs
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(
+            "include/mega_hip.h not found at %s -- the ctypes binding of libmega_hip.so is derived from it; "
+            "mega.pytorch_amd runs from the repository tree (there is no hand-written signature table to fall back on)"
+            % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read(), HEADER_PATH)
+
+
+# name -> (restype, argtypes) / parameter names of every entry point; typedef name -> ctypes.Structure of every descriptor
+SIGNATURES, PARAMS, STRUCTS = _read_header()
 
 _lib = None
 

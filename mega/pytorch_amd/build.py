@@ -11,6 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+HEADER = os.path.join(HERE, "..", "..", "include", "mega_hip.h")
 LIB = os.path.join(HERE, "libmega_hip.so")
 STAMP = os.path.join(HERE, "csrc", ".build_stamp")
 SOURCES = {
@@ -65,6 +66,7 @@ def _digest():
         if fn.endswith((".hip", ".h")):
             h.update(fn.encode())
             h.update(open(os.path.join(CSRC, fn), "rb").read())
+    h.update(open(HEADER, "rb").read())      # csrc/common.h includes it
     h.update(" ".join(BASE_FLAGS).encode())
     h.update(repr(sorted(SOURCES.items())).encode())
     h.update(open(os.path.abspath(__file__), "rb").read())      # (the flag probe lives here)

@@ -173,20 +173,17 @@ extern "C" int mega_cast_f32_to_half(const float* src, void* dst, size_t n, int 
   });
 }
 
-struct MegaCopySegC {
-  const void* src; void* dst; long long src_stride, dst_stride; int rows, row_bytes;
-};
+static_assert(sizeof(mega_copy_seg) == 40 && offsetof(mega_copy_seg, row_bytes) == 36, "mega_copy_seg: layout is ABI");
 
 // segs[n] as for mega_copy_segments, but the source blocks are f32 and the destination blocks bf16: row_bytes counts the
 // SOURCE bytes of a row (a multiple of 32: 8 elements per thread), strides are bytes of the respective tensor, both sides
 // 16-byte aligned.  dst = bf16(src), round to nearest even.
-extern "C" int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, void* stream) {
+extern "C" int mega_copy_cast_segments_dt(const mega_copy_seg* segs, int n, int dtype, void* stream) {
   mega_clear_error();
   if (n == 0) return MEGA_OK;
   if (!segs || n < 0 || (dtype != MEGA_BF16 && dtype != MEGA_F16)) return MEGA_ERR_ARG;
-  const MegaCopySegC* d = (const MegaCopySegC*)segs;
   for (int i = 0; i < n; ++i) {
-    const MegaCopySegC& g = d[i];
+    const mega_copy_seg& g = segs[i];
     if (g.rows < 0 || g.row_bytes < 0 || (g.row_bytes & 31)) return MEGA_ERR_ARG;
     if (g.rows > 0 && g.row_bytes > 0) {
       if (!g.src || !g.dst || ((size_t)g.src & 15) || ((size_t)g.dst & 15)) return MEGA_ERR_ARG;
@@ -207,7 +204,7 @@ extern "C" int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, vo
     units = 0;
   };
   for (int i = 0; i < n; ++i) {
-    const MegaCopySegC& g = d[i];
+    const mega_copy_seg& g = segs[i];
     if (g.rows == 0 || g.row_bytes == 0) continue;
     const unsigned long long u = (unsigned long long)g.rows * (unsigned long long)(g.row_bytes / 32);
     if (u >= 0xFFFFFFFFull) return MEGA_ERR_ARG;
@@ -226,14 +223,13 @@ extern "C" int mega_copy_cast_segments_dt(const void* segs, int n, int dtype, vo
 
 // segs[n]: copy rows x row_bytes bytes from src (+ r * src_stride) to dst (+ r * dst_stride).  Segments must not
 // overlap each other's destinations.  Any n (launched in groups of 56 segments).
-extern "C" int mega_copy_segments(const void* segs, int n, void* stream) {
+extern "C" int mega_copy_segments(const mega_copy_seg* segs, int n, void* stream) {
   mega_clear_error();
   if (n == 0) return MEGA_OK;
   if (!segs || n < 0) return MEGA_ERR_ARG;
-  const MegaCopySegC* d = (const MegaCopySegC*)segs;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n; ++i) {
-    const MegaCopySegC& g = d[i];
+    const mega_copy_seg& g = segs[i];
     if (g.rows < 0 || g.row_bytes < 0 || (g.rows > 0 && g.row_bytes > 0 && (!g.src || !g.dst))) return MEGA_ERR_ARG;
   }
   // all segments in one launch (groups of COPY_MAXSEG), 16-byte units at whatever alignment the segment has
@@ -249,7 +245,7 @@ extern "C" int mega_copy_segments(const void* segs, int n, void* stream) {
     units = 0;
   };
   for (int i = 0; i < n; ++i) {
-    const MegaCopySegC& g = d[i];
+    const mega_copy_seg& g = segs[i];
     if (g.rows == 0 || g.row_bytes == 0) continue;
     const unsigned long long upr = (unsigned long long)(g.row_bytes + 15) / 16;
     const unsigned long long u = (unsigned long long)g.rows * upr;

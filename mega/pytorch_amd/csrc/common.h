@@ -4,15 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MEGA_F32 0
-#define MEGA_BF16 1
-#define MEGA_F16 2
-
-#define MEGA_OK 0
-#define MEGA_ERR_ARG 1
-#define MEGA_ERR_LAUNCH 2
-#define MEGA_ERR_WS 3
-#define MEGA_ERR_LIMIT 4
+// The C ABI: dtype / error codes, descriptor structs and the prototype every extern "C" definition is checked against.
+#include "../../../include/mega_hip.h"
 
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;

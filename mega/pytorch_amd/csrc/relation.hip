@@ -815,19 +815,19 @@ extern "C" int mega_position_logits(const float* rois_q, const float* rois_k, co
   return mega_check_launch();
 }
 
-struct MegaPosDescC { const float* rois_q; const float* rois_k; void* out_bf16; int Nq, Nk; };
+static_assert(sizeof(mega_pos_desc) == 32 && offsetof(mega_pos_desc, Nk) == 28, "mega_pos_desc: layout is ABI");
 
 // the one launcher of pos_logits_tiled_batched_kernel: n <= POS_MAXB problems
-static int pos_tiled_launch(const MegaPosDescC* d, int n, const float* wg_t, const float* bg, const float* dim_mat,
+static int pos_tiled_launch(const mega_pos_desc* d, int n, const float* wg_t, const float* bg, const float* dim_mat,
                             int dtype, void* stream) {
   if (!d || n < 0 || n > POS_MAXB || !wg_t || !bg || !dim_mat) return MEGA_ERR_ARG;
   PosBatch b;
   int max_q = 0, max_k = 0;
   for (int i = 0; i < n; ++i) {
-    if (!d[i].rois_q || !d[i].rois_k || !d[i].out_bf16 || d[i].Nq <= 0 || d[i].Nk <= 0 ||
-        (reinterpret_cast<size_t>(d[i].out_bf16) & 15))
+    if (!d[i].rois_q || !d[i].rois_k || !d[i].out || d[i].Nq <= 0 || d[i].Nk <= 0 ||
+        (reinterpret_cast<size_t>(d[i].out) & 15))
       return MEGA_ERR_ARG;
-    b.p[i].rq = (const float4*)d[i].rois_q; b.p[i].rk = (const float4*)d[i].rois_k; b.p[i].out = (unsigned short*)d[i].out_bf16;
+    b.p[i].rq = (const float4*)d[i].rois_q; b.p[i].rk = (const float4*)d[i].rois_k; b.p[i].out = (unsigned short*)d[i].out;
     b.p[i].Nq = d[i].Nq; b.p[i].Nk = d[i].Nk;
     max_q = d[i].Nq > max_q ? d[i].Nq : max_q;
     max_k = d[i].Nk > max_k ? d[i].Nk : max_k;
@@ -846,16 +846,16 @@ extern "C" int mega_position_logits_tiled_dt(const float* rois_q, const float* r
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (Nq == 0 || Nk == 0) return MEGA_OK;
-  const MegaPosDescC d = {rois_q, rois_k, out16, Nq, Nk};
+  const mega_pos_desc d = {rois_q, rois_k, out16, Nq, Nk};
   return pos_tiled_launch(&d, 1, wg_t, bg, dim_mat, dtype, stream);
 }
 
-extern "C" int mega_position_logits_tiled_batched_dt(const void* descs, int n, const float* wg_t, const float* bg,
+extern "C" int mega_position_logits_tiled_batched_dt(const mega_pos_desc* descs, int n, const float* wg_t, const float* bg,
                                                      const float* dim_mat, int dtype, void* stream) {
   mega_clear_error();
   if (dtype != MEGA_BF16 && dtype != MEGA_F16) return MEGA_ERR_ARG;
   if (n == 0) return MEGA_OK;
-  return pos_tiled_launch((const MegaPosDescC*)descs, n, wg_t, bg, dim_mat, dtype, stream);
+  return pos_tiled_launch(descs, n, wg_t, bg, dim_mat, dtype, stream);
 }
 
 // Number of key-range splits the attention core uses for (Nq, Nk) -- a function of the problem alone, so a problem
@@ -917,16 +917,10 @@ static int attn_fill(AttnParams& p, const void* q, int ldq, const void* k, int l
 
 // n <= ATTN_MAXB independent problems in one launch (+ one combine launch when any of them splits its key range).  All
 // problems share groups / scale / dtype and the kind of position term (none, f32 rows, or tile-ordered 16-bit).
-struct MegaAttnDescC {
-  const void* q; const void* k; const void* vt; const float* pos; const void* pos_tiled; const void* resid;
-  const float* bias_v; void* out; void* ws; size_t ws_bytes;
-  int ldq, ldk, ldv, ldp, ldr, ldo, Nq, Nk;
-  int io_f32, nk1;
-  const void* k2; const void* vt2; int ldv2, reserved;
-};
+static_assert(sizeof(mega_attn_desc) == 144 && offsetof(mega_attn_desc, k2) == 120, "mega_attn_desc: layout is ABI");
 
 // the one launcher of attn_batched_kernel / attn_combine_batched_kernel: fill, z table, SEG choice, dtype dispatch, combine
-static int attn_launch(const MegaAttnDescC* d, int n, int groups, float scale, int dtype, void* stream) {
+static int attn_launch(const mega_attn_desc* d, int n, int groups, float scale, int dtype, void* stream) {
   if (!d || n < 0 || n > ATTN_MAXB) return MEGA_ERR_ARG;
   AttnBatch b;                 // by-value kernel argument (~2.5 KB)
   b.n = n;
@@ -970,11 +964,11 @@ static int attn_launch(const MegaAttnDescC* d, int n, int groups, float scale, i
   });
 }
 
-extern "C" int mega_relation_attention_batched(const void* descs, int n, int groups, float scale, int dtype,
+extern "C" int mega_relation_attention_batched(const mega_attn_desc* descs, int n, int groups, float scale, int dtype,
                                                void* stream) {
   mega_clear_error();
   if (n == 0) return MEGA_OK;
-  return attn_launch((const MegaAttnDescC*)descs, n, groups, scale, dtype, stream);
+  return attn_launch(descs, n, groups, scale, dtype, stream);
 }
 
 // the single-problem entry points: a batch of one (one key segment, resid / out in the operand type)
@@ -984,7 +978,7 @@ static int relation_attention_impl(const void* q, int ldq, const void* k, int ld
                                    int dtype, void* ws, size_t ws_bytes, void* stream) {
   mega_clear_error();
   if (Nq == 0) return MEGA_OK;
-  MegaAttnDescC d = {};
+  mega_attn_desc d = {};
   d.q = q; d.k = k; d.vt = vt; d.pos = pos; d.pos_tiled = pos_tiled; d.resid = resid; d.bias_v = bias_v; d.out = out;
   d.ws = ws; d.ws_bytes = ws_bytes;
   d.ldq = ldq; d.ldk = ldk; d.ldv = ldv; d.ldp = ldp; d.ldr = ldr; d.ldo = ldo; d.Nq = Nq; d.Nk = Nk;

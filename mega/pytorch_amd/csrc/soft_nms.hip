@@ -186,11 +186,6 @@ extern "C" size_t mega_soft_merge_workspace_bytes(int F, int K, int R, int NC) {
   return soft_ws_carve(nullptr, (size_t)F * (NC - 1) * K * R, (size_t)F * (NC - 1)).bytes;
 }
 
-extern "C" int mega_bbox_aug_merge(const float* cboxes, const float* cscores, int F, int K, int R, int NC,
-                                   const int* view_w, const int* view_h, const int* view_flip, float score_thresh,
-                                   float nms_thresh, int strict_gt, int max_det, float* out_boxes, float* out_scores,
-                                   long long* out_labels, int* out_cnt, void* ws, size_t ws_bytes, void* stream);
-
 extern "C" int mega_soft_merge(const float* cboxes, const float* cscores, int F, int K, int R, int NC, const int* view_w,
                                const int* view_h, const int* view_flip, float score_thresh, float nms_thresh,
                                int strict_gt, int soft_method, float sigma, int vote, float vote_thresh,

@@ -51,10 +51,14 @@ def profiling():
     return _PROF is not None
 
 
+_NO_CPU = "mega.pytorch_amd ops need HIP device tensors (no CPU path)"
+
+
 def _gpu(*ts):
+    """the device check for tensors that reach a kernel inside a descriptor (_call checks its own arguments)"""
     for t in ts:
         if t is not None and not t.is_cuda:
-            raise RuntimeError("mega.pytorch_amd ops need HIP device tensors (no CPU path)")
+            raise RuntimeError(_NO_CPU)
 
 
 def _ptr(t):
@@ -106,32 +110,60 @@ def set_profiler(p):
     _PROF = p
 
 
-def _pb(family, flops=0.0, nbytes=0.0, detail=None):
-    return None if _PROF is None else _PROF.begin(family, flops, nbytes, detail)
+_ENTRY = {}      # entry point -> (its ctypes function, the positions of its pointer parameters, whether it ends in `stream`)
 
 
-def _pe(tok):
-    if tok is not None:
+def _entry(name):
+    fn = getattr(_lib.load(), name)
+    takes_stream = _lib.PARAMS[name][-1:] == ("stream",)
+    argtypes = _lib.SIGNATURES[name][1]
+    ptrs = tuple(i for i, t in enumerate(argtypes[:len(argtypes) - takes_stream]) if t is ctypes.c_void_p)
+    _ENTRY[name] = fn, ptrs, takes_stream
+    return _ENTRY[name]
+
+
+def _call(name, *args, prof=None, what=None):
+    """One launch through the C ABI, as include/mega_hip.h declares `name`.  args: the prototype's parameters in order,
+    without a trailing `stream` (the launch stream is appended).  Where the prototype takes a pointer, a tensor stands for
+    its data_ptr() (a tensor that is not on a HIP device raises) and None for NULL; ctypes arrays and addresses pass as
+    they are.  prof = (family, flops, bytes[, detail]): with a profiler set, its event pair brackets the C call itself.
+    A non-zero return code raises through _lib.check under `what` (the entry point's name unless given)."""
+    fn, ptrs, takes_stream = _ENTRY.get(name) or _entry(name)
+    args = list(args)
+    for i in ptrs:
+        a = args[i]
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise RuntimeError(_NO_CPU)
+            args[i] = a.data_ptr()
+    if takes_stream:
+        args.append(_stream())
+    if prof is None or _PROF is None:
+        rc = fn(*args)
+    else:
+        tok = _PROF.begin(*prof)
+        rc = fn(*args)
         _PROF.end(tok)
+    _lib.check(rc, what or name)
 
 
 # ------------------------------------------------------------------------------------------------ conv / linear
-def _igemm_family(lib, M, Cout, K, dtype, shape=None):
+def _igemm_family(M, Cout, K, dtype, shape=None):
     """name of the kernel instantiation a conv / linear is dispatched to (profiler families).  shape = (N, H, W, Cin, R,
     S, stride, pad, dil, ldo, has_residual, out dtype): the layer itself, asked through the launch path's own predicates;
     without it the (M, Cout, K) GEMM shape of a 1x1 layer / linear."""
     if shape is not None:
         N, H, W, Cin, R, S, stride, pad, dil, ldo, has_res, odt = shape
-        t = lib.mega_conv2d_nhwc_plan_ex(N, H, W, Cin, Cout, R, S, stride, pad, dil, ldo, int(has_res), _DT[dtype], _DT[odt])
+        t = _lib.load().mega_conv2d_nhwc_plan_ex(N, H, W, Cin, Cout, R, S, stride, pad, dil, ldo, int(has_res), _DT[dtype], _DT[odt])
     else:
-        t = lib.mega_conv2d_nhwc_plan(M, Cout, K, _DT[dtype])
+        t = _lib.load().mega_conv2d_nhwc_plan(M, Cout, K, _DT[dtype])
     kind, t = t // 1000000, t % 1000000
     if kind == 6:
         return "conv64_bf16_3x3"
     # one family = one rocprofv3 symbol: igemm8_kernel<OT, ...> is instantiated per OUTPUT type, so a bf16 launch that writes
     # f32 (fc0's split-K partial sums, the RPN head's f32 logits) is a different symbol from the bf16-output launches of the
     # same tile ("_f32out")
-    f32out = shape is not None and dtype in _HALF and (shape[-1] == torch.float32 or (kind in (7, 8) and lib.mega_conv2d_nhwc_workspace_bytes(M, Cout, K) > 0))
+    f32out = shape is not None and dtype in _HALF and (shape[-1] == torch.float32 or (kind in (7, 8) and _lib.load().mega_conv2d_nhwc_workspace_bytes(M, Cout, K) > 0))
     return "igemm%s_%s_%dx%d%s" % ({8: "8", 7: "8s"}.get(kind, ""), {torch.bfloat16: "bf16", torch.float16: "f16"}.get(dtype, "f32"),
                                    t // 1000, t % 1000, "_f32out" if f32out else "")
 
@@ -143,10 +175,8 @@ def conv2d_nhwc(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil
     (mega_conv2d_nhwc_ks: small-M / long-K layers of FlowNetS and the FGFA box head); None: the library's K-only rule.
     residual_stride s > 1 (a 1x1 / stride 1 conv on 16-bit tensors): residual is [N,Hr,Wr,Cout] with ceil(Hr / s) == Ho,
     ceil(Wr / s) == Wo and residual[:, ::s, ::s, :] is what is added, read in place (mega_conv2d_nhwc_rs)."""
-    _gpu(x, w, scale, bias, residual)
     if residual_stride != 1:
         return _conv1x1_strided_residual(x, w, scale, bias, residual, int(residual_stride), relu, out_dtype, out, stride, pad, dil, ksplit)
-    lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout, R, S, Cin2 = w.shape
     assert Cin == Cin2 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype
@@ -161,39 +191,32 @@ def conv2d_nhwc(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil
         assert residual.shape == out.shape and residual.dtype == x.dtype and residual.is_contiguous()
     for v in (scale, bias):
         assert v is None or (v.dtype == torch.float32 and v.numel() == Cout and v.is_contiguous())
-    _tok = None
+    prof = None
     if _PROF is not None:      # family = the kernel symbol rocprofv3 would report for this launch
-        _tok = _pb(_igemm_family(lib, N * Ho * Wo, Cout, R * S * Cin, x.dtype,
-                                 (N, H, W, Cin, R, S, stride, pad, dil, Cout, residual is not None, odt)),
-                   2.0 * N * Ho * Wo * Cout * R * S * Cin,
-                   x.numel() * x.element_size() + w.numel() * w.element_size() + out.numel() * out.element_size()
-                   + (0 if residual is None else residual.numel() * residual.element_size()),
-                   detail="%dx%dx%d (%dx%d)" % (N * Ho * Wo, Cout, R * S * Cin, R, S))
+        prof = (_igemm_family(N * Ho * Wo, Cout, R * S * Cin, x.dtype,
+                              (N, H, W, Cin, R, S, stride, pad, dil, Cout, residual is not None, odt)),
+                2.0 * N * Ho * Wo * Cout * R * S * Cin,
+                x.numel() * x.element_size() + w.numel() * w.element_size() + out.numel() * out.element_size()
+                + (0 if residual is None else residual.numel() * residual.element_size()),
+                "%dx%dx%d (%dx%d)" % (N * Ho * Wo, Cout, R * S * Cin, R, S))
     if x.numel() * x.element_size() >= 0x7FF00000 or w.numel() * w.element_size() >= 0x7FF00000:
         raise ValueError("conv2d_nhwc: operand of %.2f GiB; the kernels use 32-bit buffer offsets (< 2 GiB per operand): "
                          "lower the frame-stage batch (ClipEngine steps_per_batch) or split the call over M"
                          % (max(x.numel() * x.element_size(), w.numel() * w.element_size()) / 2.0 ** 30))
     if ksplit is not None:
-        nb = lib.mega_conv2d_nhwc_ks_workspace_bytes(N * Ho * Wo, Cout, R * S * Cin, _dt(x), int(ksplit))
+        nb = _lib.load().mega_conv2d_nhwc_ks_workspace_bytes(N * Ho * Wo, Cout, R * S * Cin, _dt(x), int(ksplit))
         ws = _ws(nb, x.device) if nb else None
-        rc = lib.mega_conv2d_nhwc_ks(_ptr(x), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin,
-                                     Cout, R, S, stride, pad, dil, int(relu), Cout, Cout, _dt(x), _DT[odt], int(ksplit),
-                                     _ptr(ws), nb, _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_conv2d_nhwc_ks")
+        _call("mega_conv2d_nhwc_ks", x, w, scale, bias, residual, out, N, H, W, Cin, Cout, R, S, stride, pad, dil, int(relu),
+              Cout, Cout, _dt(x), _DT[odt], int(ksplit), ws, nb, prof=prof)
         return out
-    nb = lib.mega_conv2d_nhwc_workspace_bytes(N * Ho * Wo, Cout, R * S * Cin)     # > 0: long-K layer, split-K
+    nb = _lib.load().mega_conv2d_nhwc_workspace_bytes(N * Ho * Wo, Cout, R * S * Cin)     # > 0: long-K layer, split-K
     ws = _ws(nb, x.device) if nb else None
-    rc = lib.mega_conv2d_nhwc_ws(_ptr(x), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin,
-                                 Cout, R, S, stride, pad, dil, int(relu), Cout, Cout, _dt(x), _DT[odt], _ptr(ws), nb,
-                                 _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_conv2d_nhwc")
+    _call("mega_conv2d_nhwc_ws", x, w, scale, bias, residual, out, N, H, W, Cin, Cout, R, S, stride, pad, dil, int(relu),
+          Cout, Cout, _dt(x), _DT[odt], ws, nb, prof=prof, what="mega_conv2d_nhwc")
     return out
 
 
 def _conv1x1_strided_residual(x, w, scale, bias, residual, rs, relu, out_dtype, out, stride, pad, dil, ksplit):
-    lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout, R, S, Cin2 = w.shape
     assert rs > 1 and residual is not None and (R, S, stride, pad, dil) == (1, 1, 1, 0, 1) and ksplit is None
@@ -210,12 +233,10 @@ def _conv1x1_strided_residual(x, w, scale, bias, residual, rs, relu, out_dtype, 
         assert v is None or (v.dtype == torch.float32 and v.numel() == Cout and v.is_contiguous())
     if max(t.numel() * 2 for t in (x, w, out, residual)) >= 0x7FF00000:
         raise ValueError("conv2d_nhwc: operand of 2 GiB or more; the kernels use 32-bit buffer offsets")
-    _tok = _pb("igemm8s_%s_rs" % {torch.bfloat16: "bf16", torch.float16: "f16"}[x.dtype], 2.0 * N * H * W * Cout * Cin,
-               (x.numel() + w.numel() + 2 * out.numel()) * 2.0, detail="%dx%dx%d (1x1, residual stride %d)" % (N * H * W, Cout, Cin, rs))
-    rc = lib.mega_conv2d_nhwc_rs(_ptr(x), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin, Cout,
-                                 int(relu), Cout, Cout, Hr, Wr, rs, _dt(x), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_conv2d_nhwc_rs")
+    _call("mega_conv2d_nhwc_rs", x, w, scale, bias, residual, out, N, H, W, Cin, Cout, int(relu), Cout, Cout, Hr, Wr, rs,
+          _dt(x), prof=("igemm8s_%s_rs" % {torch.bfloat16: "bf16", torch.float16: "f16"}[x.dtype], 2.0 * N * H * W * Cout * Cin,
+                        (x.numel() + w.numel() + 2 * out.numel()) * 2.0,
+                        "%dx%dx%d (1x1, residual stride %d)" % (N * H * W, Cout, Cin, rs)))
     return out
 
 
@@ -240,8 +261,6 @@ def deconv4x4s2_into(x, w4, bias4, out, coff, relu=0, ksplit=1):
     [N,H2,W2,ldo] contiguous (the level's concatenation buffer); crop_like's rule: the full map is (2H+2) x (2W+2); when its
     size differs from (H2, W2) one row / column is dropped at the top / left.  Only the slice is written: every other column
     of out keeps what it held (flow_level_assemble writes the rest of a level's buffer)."""
-    _gpu(x, w4, bias4, out)
-    lib = _lib.load()
     N, H, W, Cin = x.shape
     C = w4.shape[0] // 4
     assert tuple(w4.shape) == (4 * C, 2, 2, Cin) and x.is_contiguous() and w4.is_contiguous() and out.is_contiguous()
@@ -250,14 +269,12 @@ def deconv4x4s2_into(x, w4, bias4, out, coff, relu=0, ksplit=1):
     crop = 0 if (2 * H + 2, 2 * W + 2) == (H2, W2) else 1
     assert H2 + crop <= 2 * H + 2 and W2 + crop <= 2 * W + 2
     M = N * (H + 1) * (W + 1)
-    _tok = _pb("deconv_subpixel", 2.0 * M * 4 * C * 4 * Cin, (x.numel() + w4.numel() + N * H2 * W2 * C) * x.element_size(),
-               detail="%dx%dx%d (2x2 sub-pixel)" % (M, 4 * C, 4 * Cin))
-    nb = lib.mega_conv2d_nhwc_ks_workspace_bytes(M, 4 * C, 4 * Cin, _dt(x), int(ksplit))
+    nb = _lib.load().mega_conv2d_nhwc_ks_workspace_bytes(M, 4 * C, 4 * Cin, _dt(x), int(ksplit))
     ws = _ws(nb, x.device) if nb else None
-    rc = lib.mega_conv2d_nhwc_subpixel(_ptr(x), _ptr(w4), _ptr(bias4), _ptr(out), N, H, W, Cin, C, int(relu), H2, W2, crop, ldo,
-                                       coff, _dt(x), int(ksplit), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_conv2d_nhwc_subpixel")
+    _call("mega_conv2d_nhwc_subpixel", x, w4, bias4, out, N, H, W, Cin, C, int(relu), H2, W2, crop, ldo, coff, _dt(x),
+          int(ksplit), ws, nb,
+          prof=("deconv_subpixel", 2.0 * M * 4 * C * 4 * Cin, (x.numel() + w4.numel() + N * H2 * W2 * C) * x.element_size(),
+                "%dx%dx%d (2x2 sub-pixel)" % (M, 4 * C, 4 * Cin)))
     return out
 
 
@@ -267,8 +284,6 @@ def flow_conv1_combine(ab, bias, dtype, key=None, order=None, T=None, out=None, 
     default).  The key frame's slot is `key` (host int) or order[0] (device i32: the engine's ring).
     nwin > 0: order i32 [G, 1 + nwin] = rows [key slot, slot of window position 0 .. nwin-1]: -> [G * nwin,h,w,64], pair
     g * nwin + t = (key frame of row g, the frame at window position t) -- exactly the pairs of G key frames, in window order."""
-    _gpu(ab, bias, order)
-    lib = _lib.load()
     S, h, w, c = ab.shape
     if nwin > 0:
         assert order is not None and order.dim() == 2 and order.shape[1] == nwin + 1
@@ -282,26 +297,19 @@ def flow_conv1_combine(ab, bias, dtype, key=None, order=None, T=None, out=None, 
     if out is None:
         out = torch.empty((T, h, w, 64), dtype=dtype, device=ab.device)
     assert out.dtype == dtype and tuple(out.shape) == (T, h, w, 64) and out.is_contiguous()
-    _tok = _pb("flow_conv1_combine", 0.0, T * h * w * 64 * 6.0)
-    rc = lib.mega_flow_conv1_combine(_ptr(ab), _ptr(bias), _ptr(order), -1 if key is None else int(key), _ptr(out), T, h * w,
-                                     int(nwin), _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_flow_conv1_combine")
+    _call("mega_flow_conv1_combine", ab, bias, order, -1 if key is None else int(key), out, T, h * w, int(nwin), _DT[dtype],
+          prof=("flow_conv1_combine", 0.0, T * h * w * 64 * 6.0))
     return out
 
 
 def flow_pred_finish(z, bias, scale, out_dtype):
     """second half of a FlowNetS flow prediction (mega_flow_pred_finish): z f32 [N,H,W,ldz] = the 1 x 1 conv of the level's map
     with the 18 (tap, channel) columns of Conv2d(Cin, 2, 3, padding=1) -> [N,H,W,2] = (sum of the shifted taps) * scale + bias."""
-    _gpu(z, bias)
-    lib = _lib.load()
     N, H, W, ldz = z.shape
     assert z.dtype == torch.float32 and z.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == 2
     out = torch.empty((N, H, W, 2), dtype=out_dtype, device=z.device)
-    _tok = _pb("flow_pred_finish", 0.0, N * H * W * (18 * 4.0 + 2 * out.element_size()))
-    rc = lib.mega_flow_pred_finish(_ptr(z), ldz, _ptr(bias), float(scale), _ptr(out), N, H, W, _DT[out_dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_flow_pred_finish")
+    _call("mega_flow_pred_finish", z, ldz, bias, float(scale), out, N, H, W, _DT[out_dtype],
+          prof=("flow_pred_finish", 0.0, N * H * W * (18 * 4.0 + 2 * out.element_size())))
     return out
 
 
@@ -309,19 +317,14 @@ def flow_level_assemble(skip, flow, w_up, b_up, out, C):
     """the rest of a FlowNetS refinement level's concatenation (mega_flow_level_assemble): out[..., :Cs] = skip,
     out[..., Cs+C:Cs+C+2] = crop_like(ConvTranspose2d(2, 2, 4, stride=2)(flow)) from the f32 weights w_up [2,2,4,4] / b_up [2],
     zeros up to out's channel stride; out[..., Cs:Cs+C] (the deconvolution's slice) is left alone."""
-    _gpu(skip, flow, w_up, b_up, out)
-    lib = _lib.load()
     N, H2, W2, Cs = skip.shape
     _, h, w, two = flow.shape
     assert two == 2 and out.shape[:3] == skip.shape[:3] and flow.shape[0] == N
     assert skip.is_contiguous() and flow.is_contiguous() and out.is_contiguous() and skip.dtype == flow.dtype == out.dtype
     assert w_up.dtype == torch.float32 and tuple(w_up.shape) == (2, 2, 4, 4) and w_up.is_contiguous() and b_up.dtype == torch.float32
     crop = 0 if (2 * h + 2, 2 * w + 2) == (H2, W2) else 1
-    _tok = _pb("flow_level_assemble", 0.0, (skip.numel() + N * H2 * W2 * (out.shape[3] - C)) * skip.element_size())
-    rc = lib.mega_flow_level_assemble(_ptr(skip), _ptr(flow), _ptr(w_up), _ptr(b_up), _ptr(out), N, H2, W2, Cs, C, out.shape[3],
-                                      h, w, crop, _dt(skip), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_flow_level_assemble")
+    _call("mega_flow_level_assemble", skip, flow, w_up, b_up, out, N, H2, W2, Cs, C, out.shape[3], h, w, crop, _dt(skip),
+          prof=("flow_level_assemble", 0.0, (skip.numel() + N * H2 * W2 * (out.shape[3] - C)) * skip.element_size()))
     return out
 
 
@@ -331,8 +334,6 @@ def bottleneck64(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, subsample=False):
     launches.  w1 [64,1,1,256], w2 [64,3,3,64], w3 [256,1,1,64] (OHWI bf16), s / b f32 FrozenBN scale / bias.
     subsample: the even pixels only -- y[:, ::2, ::2, :] as a contiguous [N,ceil(H/2),ceil(W/2),256] tensor, same bits (for a
     block whose only reader is a stride-2 1x1 conv: conv2 / conv3 / the residual / the stores run on a quarter of the pixels)."""
-    _gpu(x, w1, s1, b1, w2, s2, b2, w3, s3, b3)
-    lib = _lib.load()
     N, H, W, C = x.shape
     assert C == 256 and x.dtype in _HALF and x.is_contiguous()
     assert tuple(w1.shape) == (64, 1, 1, 256) and tuple(w2.shape) == (64, 3, 3, 64) and tuple(w3.shape) == (256, 1, 1, 64)
@@ -345,18 +346,12 @@ def bottleneck64(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, subsample=False):
     px = float(N * H * W)
     if subsample:
         out = torch.empty((N, (H + 1) // 2, (W + 1) // 2, 256), dtype=x.dtype, device=x.device)
-        _tok = _pb("bneck64_fused_even", 2.0 * px * (256 * 64 + (576 * 64 + 64 * 256) / 4.0), px * 512.0 + out.numel() * 2.0)
-        rc = lib.mega_bottleneck64_even_fwd_dt(_ptr(x), _ptr(w1), _ptr(s1), _ptr(b1), _ptr(w2), _ptr(s2), _ptr(b2), _ptr(w3),
-                                               _ptr(s3), _ptr(b3), _ptr(out), N, H, W, _dt(x), _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_bottleneck64_even_fwd_dt")
+        _call("mega_bottleneck64_even_fwd_dt", x, w1, s1, b1, w2, s2, b2, w3, s3, b3, out, N, H, W, _dt(x),
+              prof=("bneck64_fused_even", 2.0 * px * (256 * 64 + (576 * 64 + 64 * 256) / 4.0), px * 512.0 + out.numel() * 2.0))
         return out
     out = torch.empty_like(x)
-    _tok = _pb("bneck64_fused", 2.0 * px * (256 * 64 + 576 * 64 + 64 * 256), px * 1024.0)
-    rc = lib.mega_bottleneck64_fwd_dt(_ptr(x), _ptr(w1), _ptr(s1), _ptr(b1), _ptr(w2), _ptr(s2), _ptr(b2), _ptr(w3), _ptr(s3),
-                                      _ptr(b3), _ptr(out), N, H, W, _dt(x), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_bottleneck64_fwd_dt")
+    _call("mega_bottleneck64_fwd_dt", x, w1, s1, b1, w2, s2, b2, w3, s3, b3, out, N, H, W, _dt(x),
+          prof=("bneck64_fused", 2.0 * px * (256 * 64 + 576 * 64 + 64 * 256), px * 1024.0))
     return out
 
 
@@ -364,8 +359,6 @@ def bottleneck64_ds(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, bd):
     """The fused FIRST block of layer1 (64 -> 64 -> 64 (3x3) -> 256 with the 1x1 downsample branch): x NHWC bf16 [N,H,W,64] ->
     relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + bnd(convd(x))) [N,H,W,256]; same bits as the four conv2d_nhwc
     launches.  w1 [64,1,1,64], w2 [64,3,3,64], w3 / wd [256,1,1,64]."""
-    _gpu(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, bd)
-    lib = _lib.load()
     N, H, W, C = x.shape
     assert C == 64 and x.dtype in _HALF and x.is_contiguous()
     assert tuple(w1.shape) == (64, 1, 1, 64) and tuple(w2.shape) == (64, 3, 3, 64)
@@ -378,11 +371,8 @@ def bottleneck64_ds(x, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, bd):
     if out.numel() * 2 >= 0x7FF00000:
         raise ValueError("bottleneck64_ds: output of %.2f GiB; 32-bit buffer offsets (< 2 GiB)" % (out.numel() * 2 / 2.0 ** 30))
     px = float(N * H * W)
-    _tok = _pb("bneck64_fused", 2.0 * px * (64 * 64 + 576 * 64 + 2 * 64 * 256), px * 640.0)
-    rc = lib.mega_bottleneck64_ds_fwd_dt(_ptr(x), _ptr(w1), _ptr(s1), _ptr(b1), _ptr(w2), _ptr(s2), _ptr(b2), _ptr(w3), _ptr(s3),
-                                         _ptr(b3), _ptr(wd), _ptr(sd), _ptr(bd), _ptr(out), N, H, W, _dt(x), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_bottleneck64_ds_fwd_dt")
+    _call("mega_bottleneck64_ds_fwd_dt", x, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, bd, out, N, H, W, _dt(x),
+          prof=("bneck64_fused", 2.0 * px * (64 * 64 + 576 * 64 + 2 * 64 * 256), px * 640.0))
     return out
 
 
@@ -401,23 +391,16 @@ def linear(x, w, bias=None, relu=False, residual=None, out_dtype=None, scale=Non
 def stem(x_nchw, w_tap64, scale, bias, out_dtype, w_n160=None):
     """x [N,3,H,W] f32 -> conv7x7 s2 + BN + ReLU -> NHWC [N,Ho,Wo,64].  f32: direct conv with w_tap64 [147,64] f32;
     bf16: matrix-core kernel with w_n160 = bf16 [64,176] (see pack_stem_weight_bf16)."""
-    _gpu(x_nchw, w_tap64, scale, bias)
-    lib = _lib.load()
     N, C, H, W = x_nchw.shape
     assert C == 3 and x_nchw.dtype == torch.float32 and x_nchw.is_contiguous()
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((N, Ho, Wo, 64), dtype=out_dtype, device=x_nchw.device)
-    _tok = _pb("stem", 2.0 * N * Ho * Wo * 64 * 147, x_nchw.numel() * 4 + out.numel() * out.element_size())
+    prof = ("stem", 2.0 * N * Ho * Wo * 64 * 147, x_nchw.numel() * 4 + out.numel() * out.element_size())
     if out_dtype == torch.bfloat16 and w_n160 is not None:
-        _gpu(w_n160)
         assert w_n160.dtype == torch.bfloat16 and tuple(w_n160.shape) == (64, 176) and w_n160.is_contiguous()
-        rc = lib.mega_stem_conv_bn_relu_bf16(_ptr(x_nchw), _ptr(w_n160), _ptr(scale), _ptr(bias), _ptr(out), N, H, W,
-                                             _stream())
+        _call("mega_stem_conv_bn_relu_bf16", x_nchw, w_n160, scale, bias, out, N, H, W, prof=prof, what="mega_stem_conv_bn_relu")
     else:
-        rc = lib.mega_stem_conv_bn_relu(_ptr(x_nchw), _ptr(w_tap64), _ptr(scale), _ptr(bias), _ptr(out), N, H, W,
-                                        _DT[out_dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_stem_conv_bn_relu")
+        _call("mega_stem_conv_bn_relu", x_nchw, w_tap64, scale, bias, out, N, H, W, _DT[out_dtype], prof=prof)
     return out
 
 
@@ -425,18 +408,13 @@ def stem_u8(frames_u8, w_n160, scale, bias, mean, to_bgr=True):
     """uint8 frames [N,H,W,3] RGB -> preprocess (BGR*255 - mean) + conv7x7 s2 + BN + ReLU -> NHWC bf16 [N,Ho,Wo,64] in ONE
     kernel (the bf16 matrix-core stem with the preprocessing on its patch load): same bits as
     stem(preprocess_frames(frames_u8), ...)."""
-    _gpu(frames_u8, w_n160, scale, bias)
-    lib = _lib.load()
     N, H, W, C = frames_u8.shape
     assert C == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     assert w_n160.dtype == torch.bfloat16 and tuple(w_n160.shape) == (64, 176) and w_n160.is_contiguous()
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((N, Ho, Wo, 64), dtype=torch.bfloat16, device=frames_u8.device)
-    _tok = _pb("stem", 2.0 * N * Ho * Wo * 64 * 147, frames_u8.numel() + out.numel() * 2)
-    rc = lib.mega_stem_conv_bn_relu_bf16_u8(_ptr(frames_u8), _ptr(w_n160), _ptr(scale), _ptr(bias), _ptr(out), N, H, W,
-                                            float(mean[0]), float(mean[1]), float(mean[2]), int(to_bgr), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_stem_conv_bn_relu_bf16_u8")
+    _call("mega_stem_conv_bn_relu_bf16_u8", frames_u8, w_n160, scale, bias, out, N, H, W, float(mean[0]), float(mean[1]),
+          float(mean[2]), int(to_bgr), prof=("stem", 2.0 * N * Ho * Wo * 64 * 147, frames_u8.numel() + out.numel() * 2))
     return out
 
 
@@ -444,8 +422,6 @@ def stem_pool(x, w_n160, scale, bias, mean=None, to_bgr=True):
     """resnet.py:355-366 in ONE kernel (bf16): conv7x7 s2 + BN + ReLU + max_pool2d(3, 2, 1) -> NHWC bf16 [N,Hp,Wp,64].  x =
     uint8 frames [N,H,W,3] RGB (preprocessing on the patch load, `mean` required) or the preprocessed f32 NCHW image.  Same
     bits as maxpool3x3s2(stem[_u8](...)); the stem's own map never reaches HBM."""
-    _gpu(x, w_n160, scale, bias)
-    lib = _lib.load()
     u8 = x.dtype == torch.uint8
     if u8:
         N, H, W, C = x.shape
@@ -459,11 +435,9 @@ def stem_pool(x, w_n160, scale, bias, mean=None, to_bgr=True):
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
     out = torch.empty((N, Hp, Wp, 64), dtype=w_n160.dtype, device=x.device)      # (the weights' 16-bit type is the output's)
-    _tok = _pb("stem", 2.0 * N * Ho * Wo * 64 * 147, x.numel() * x.element_size() + out.numel() * 2)
-    rc = lib.mega_stem_pool_dt(_ptr(x), int(u8), _ptr(w_n160), _ptr(scale), _ptr(bias), _ptr(out), N, H, W,
-                               float(mean[0]), float(mean[1]), float(mean[2]), int(to_bgr), _dt(w_n160), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_stem_pool_dt")
+    _call("mega_stem_pool_dt", x, int(u8), w_n160, scale, bias, out, N, H, W, float(mean[0]), float(mean[1]),
+          float(mean[2]), int(to_bgr), _dt(w_n160),
+          prof=("stem", 2.0 * N * Ho * Wo * 64 * 147, x.numel() * x.element_size() + out.numel() * 2))
     return out
 
 
@@ -484,24 +458,18 @@ def pack_stem_weight_bf16(w_oihw, dtype=torch.bfloat16):
 
 
 def maxpool3x3s2(x):
-    _gpu(x)
-    lib = _lib.load()
     N, H, W, C = x.shape
     assert x.is_contiguous()
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
-    _tok = _pb("maxpool", 0.0, (x.numel() + out.numel()) * x.element_size())
-    rc = lib.mega_maxpool3x3s2_nhwc(_ptr(x), _ptr(out), N, H, W, C, _dt(x), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_maxpool3x3s2_nhwc")
+    _call("mega_maxpool3x3s2_nhwc", x, out, N, H, W, C, _dt(x),
+          prof=("maxpool", 0.0, (x.numel() + out.numel()) * x.element_size()))
     return out
 
 
 # ------------------------------------------------------------------------------------------------ ROIAlign
 def roi_align(feat, rois, spatial_scale, pooled, sampling_ratio, in_nhwc=True, out_nhwc=True):
     """feat NHWC [B,H,W,C] (or NCHW when in_nhwc=False); rois [K,5] f32 -> [K,ph*pw,C] (or [K,C,ph,pw])."""
-    _gpu(feat, rois)
-    lib = _lib.load()
     if in_nhwc:
         B, H, W, C = feat.shape
     else:
@@ -511,11 +479,9 @@ def roi_align(feat, rois, spatial_scale, pooled, sampling_ratio, in_nhwc=True, o
     assert feat.is_contiguous() and rois.dtype == torch.float32 and rois.is_contiguous() and rois.shape[1] == 5
     shape = (K, ph * pw, C) if out_nhwc else (K, C, ph, pw)
     out = torch.empty(shape, dtype=feat.dtype, device=feat.device)
-    _tok = _pb("roi_align", 0.0, out.numel() * out.element_size() + feat.numel() * feat.element_size())
-    rc = lib.mega_roi_align_fwd(_ptr(feat), _ptr(rois), _ptr(out), K, C, H, W, float(spatial_scale), ph, pw,
-                                int(sampling_ratio), int(in_nhwc), int(out_nhwc), _dt(feat), _dt(feat), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_roi_align_fwd")
+    _call("mega_roi_align_fwd", feat, rois, out, K, C, H, W, float(spatial_scale), ph, pw, int(sampling_ratio),
+          int(in_nhwc), int(out_nhwc), _dt(feat), _dt(feat),
+          prof=("roi_align", 0.0, out.numel() * out.element_size() + feat.numel() * feat.element_size()))
     return out
 
 
@@ -524,27 +490,20 @@ def roi_align_planes(feat, rois, spatial_scale, pooled, sampling_ratio, dtype=to
     [K, 2*ph*pw*C]), without the f32 tensor in between.  Large launches (C / 4 a multiple of 8 channel vectors, adaptive grid) run
     the separable per-ROI form of the 16-bit kernels: split_planes(roi_align(...)) to f32 round-off; small ones the
     exact-term-order kernel: bit for bit."""
-    _gpu(feat, rois)
-    lib = _lib.load()
     B, H, W, C = feat.shape
     ph, pw = pooled
     K = rois.shape[0]
     assert feat.dtype == torch.float32 and feat.is_contiguous() and rois.dtype == torch.float32 and rois.is_contiguous()
     assert rois.shape[1] == 5 and C % 4 == 0
     out = torch.empty((K, 2 * ph * pw * C), dtype=dtype, device=feat.device)
-    _tok = _pb("roi_align", 0.0, out.numel() * 2 + feat.numel() * 4)
-    rc = lib.mega_roi_align_fwd_planes_dt(_ptr(feat), _ptr(rois), _ptr(out), K, C, H, W, float(spatial_scale), ph, pw,
-                                          int(sampling_ratio), _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_roi_align_fwd_planes_dt")
+    _call("mega_roi_align_fwd_planes_dt", feat, rois, out, K, C, H, W, float(spatial_scale), ph, pw, int(sampling_ratio),
+          _DT[dtype], prof=("roi_align", 0.0, out.numel() * 2 + feat.numel() * 4))
     return Planes(out, ph * pw * C)
 
 
 # ------------------------------------------------------------------------------------------------ NMS
 def nms(dets, scores, thr, strict_gt=True):
     """Kept ORIGINAL indices ascending (int64), reference mega_core._C.nms semantics.  One host sync (size)."""
-    _gpu(dets, scores)
-    lib = _lib.load()
     n = dets.shape[0]
     if n == 0:
         return torch.empty((0,), dtype=torch.int64, device=dets.device)
@@ -554,11 +513,9 @@ def nms(dets, scores, thr, strict_gt=True):
     scores = scores.contiguous().float()
     keep = torch.empty((n,), dtype=torch.int64, device=dets.device)
     cnt = torch.zeros((1,), dtype=torch.int32, device=dets.device)
-    nb = lib.mega_nms_full_workspace_bytes(n)
+    nb = _lib.load().mega_nms_full_workspace_bytes(n)
     ws = _ws(nb, dets.device)
-    rc = lib.mega_nms(_ptr(dets), _ptr(scores), n, float(thr), int(strict_gt), _ptr(keep), _ptr(cnt), _ptr(ws), nb,
-                      _stream())
-    _lib.check(rc, "mega_nms")
+    _call("mega_nms", dets, scores, n, float(thr), int(strict_gt), keep, cnt, ws, nb)
     return keep[: int(cnt.item())]
 
 
@@ -569,8 +526,6 @@ def rpn_select(rpn_out, cell_anchors, Hf, Wf, anchor_stride, pre_nms, post_nms, 
     want_index: also the kept proposals' flat anchor indices (y*Wf + x)*A + a, [B,post_nms] i32, -1 past the count.
     hold (a list): the workspace is appended to it -- a caller that launches this on a side stream (launch_on) keeps it
     alive until the streams have joined, so that the allocator cannot hand the block to the current stream's next op."""
-    _gpu(rpn_out, cell_anchors)
-    lib = _lib.load()
     B = rpn_out.shape[0]
     A = cell_anchors.shape[0]
     ldc = rpn_out.shape[-1]
@@ -582,15 +537,12 @@ def rpn_select(rpn_out, cell_anchors, Hf, Wf, anchor_stride, pre_nms, post_nms, 
     props = torch.empty((B, post_nms, 4), dtype=torch.float32, device=rpn_out.device)
     scores = torch.empty((B, post_nms), dtype=torch.float32, device=rpn_out.device)
     cnt = torch.empty((B,), dtype=torch.int32, device=rpn_out.device)
-    nb = lib.mega_rpn_select_workspace_bytes(B, k)
+    nb = _lib.load().mega_rpn_select_workspace_bytes(B, k)
     ws = _ws(nb, rpn_out.device)
-    _tok = _pb("rpn_select", 0.0, rpn_out.numel() * 4)
     index = torch.empty((B, post_nms), dtype=torch.int32, device=rpn_out.device) if want_index else None
-    rc = lib.mega_rpn_select_idx(_ptr(rpn_out), _ptr(cell_anchors), B, Hf, Wf, A, ldc, anchor_stride, pre_nms, post_nms,
-                                 float(nms_thresh), int(strict_gt), float(min_size), float(im_w), float(im_h),
-                                 _ptr(props), _ptr(scores), _ptr(cnt), _ptr(index), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_rpn_select_idx")
+    _call("mega_rpn_select_idx", rpn_out, cell_anchors, B, Hf, Wf, A, ldc, anchor_stride, pre_nms, post_nms, float(nms_thresh),
+          int(strict_gt), float(min_size), float(im_w), float(im_h), props, scores, cnt, index, ws, nb,
+          prof=("rpn_select", 0.0, rpn_out.numel() * 4))
     if hold is not None:
         hold.append(ws)
     return (props, scores, cnt, index) if want_index else (props, scores, cnt)
@@ -601,8 +553,6 @@ def postprocess(logits, deltas, props, nprop, weights, im_w, im_h, score_thresh,
     """One image: returns (boxes [cap,4], scores [cap], labels [cap] i64, count [1] i32 device[, probs]), cap = (NC-1) * R.
     The detections are the first `count` rows; the rows from `count` on are not written (torch.empty: whatever the
     allocator's block held) and no part of the result."""
-    _gpu(logits, deltas, props)
-    lib = _lib.load()
     R, NC = logits.shape
     if R > 1024:
         raise ValueError("postprocess: %d proposals; the per-class sort takes at most 1024 per image "
@@ -614,18 +564,14 @@ def postprocess(logits, deltas, props, nprop, weights, im_w, im_h, score_thresh,
     ol = torch.empty((cap,), dtype=torch.int64, device=dev)
     oc = torch.zeros((1,), dtype=torch.int32, device=dev)
     probs = torch.empty((R, NC), dtype=torch.float32, device=dev) if want_probs else None
-    nb = lib.mega_postprocess_workspace_bytes(R, NC)
+    nb = _lib.load().mega_postprocess_workspace_bytes(R, NC)
     ws = _ws(nb, dev)
     assert logits.dtype == torch.float32 and deltas.dtype == torch.float32 and props.dtype == torch.float32
     assert logits.is_contiguous() and deltas.is_contiguous() and props.is_contiguous()
     wx, wy, ww, wh = weights
-    _tok = _pb("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4)
-    rc = lib.mega_postprocess(_ptr(logits), _ptr(deltas), _ptr(props), _ptr(nprop), R, NC, wx, wy, ww, wh,
-                              float(im_w), float(im_h), float(score_thresh), float(nms_thresh), int(strict_gt),
-                              int(max_det), _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc), _ptr(probs), _ptr(ws), nb,
-                              _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_postprocess")
+    _call("mega_postprocess", logits, deltas, props, nprop, R, NC, wx, wy, ww, wh, float(im_w), float(im_h),
+          float(score_thresh), float(nms_thresh), int(strict_gt), int(max_det), ob, os_, ol, oc, probs, ws, nb,
+          prof=("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4))
     return (ob, os_, ol, oc, probs) if want_probs else (ob, os_, ol, oc)
 
 
@@ -634,8 +580,6 @@ def postprocess_batched(logits, deltas, props, B, weights, im_w, im_h, score_thr
     """B images of R = rows / B proposals each (logits [B*R,NC], deltas [B*R,NC*4], props [B*R,4]) in one launch chain.
     Returns (boxes [B,cap,4], scores [B,cap], labels [B,cap] i64, counts [B] i32 device); image b has the bits of
     postprocess() on its own rows.  Image b's detections are its first counts[b] rows; the rows past them are not written."""
-    _gpu(logits, deltas, props)
-    lib = _lib.load()
     NC = logits.shape[1]
     assert logits.shape[0] % B == 0
     R = logits.shape[0] // B
@@ -648,22 +592,17 @@ def postprocess_batched(logits, deltas, props, B, weights, im_w, im_h, score_thr
     os_ = torch.empty((B, cap), dtype=torch.float32, device=dev)
     ol = torch.empty((B, cap), dtype=torch.int64, device=dev)
     oc = torch.zeros((B,), dtype=torch.int32, device=dev)
-    nb = lib.mega_postprocess_batched_workspace_bytes(B, R, NC)
+    nb = _lib.load().mega_postprocess_batched_workspace_bytes(B, R, NC)
     ws = _ws(nb, dev)
     assert logits.dtype == torch.float32 and deltas.dtype == torch.float32 and props.dtype == torch.float32
     assert logits.is_contiguous() and deltas.is_contiguous() and props.is_contiguous()
     assert deltas.shape == (B * R, NC * 4) and props.shape == (B * R, 4)
     wx, wy, ww, wh = weights
-    _tok = _pb("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4)
     if nprop is not None:      # device i32 [B]: the valid proposal rows of each image (rows past it are ignored)
-        _gpu(nprop)
         assert nprop.dtype == torch.int32 and nprop.numel() == B and nprop.is_contiguous()
-    rc = lib.mega_postprocess_batched(_ptr(logits), _ptr(deltas), _ptr(props), _ptr(nprop), B, R, NC, wx, wy, ww, wh,
-                                      float(im_w), float(im_h), float(score_thresh), float(nms_thresh), int(strict_gt),
-                                      int(max_det), _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc), None, _ptr(ws), nb,
-                                      _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_postprocess_batched")
+    _call("mega_postprocess_batched", logits, deltas, props, nprop, B, R, NC, wx, wy, ww, wh, float(im_w), float(im_h),
+          float(score_thresh), float(nms_thresh), int(strict_gt), int(max_det), ob, os_, ol, oc, None, ws, nb,
+          prof=("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4))
     return ob, os_, ol, oc
 
 
@@ -672,8 +611,6 @@ def postprocess_candidates_batched(logits, deltas, props, B, weights, im_w, im_h
     (boxes [B,NC-1,R,4], scores [B,NC-1,R]) -- class j + 1, proposal row r; the score is -1 where it is not > score_thresh
     or r >= nprop[b].  Every slot is written; the box of a slot whose score is -1 is the decode of whatever that row holds
     (NaN for a padding row) and no part of the result."""
-    _gpu(logits, deltas, props)
-    lib = _lib.load()
     NC = logits.shape[1]
     assert logits.shape[0] % B == 0
     R = logits.shape[0] // B
@@ -681,18 +618,13 @@ def postprocess_candidates_batched(logits, deltas, props, B, weights, im_w, im_h
     assert logits.is_contiguous() and deltas.is_contiguous() and props.is_contiguous()
     assert deltas.shape == (B * R, NC * 4) and props.shape == (B * R, 4)
     if nprop is not None:
-        _gpu(nprop)
         assert nprop.dtype == torch.int32 and nprop.numel() == B and nprop.is_contiguous()
     dev = logits.device
     cb = torch.empty((B, NC - 1, R, 4), dtype=torch.float32, device=dev)
     cs = torch.empty((B, NC - 1, R), dtype=torch.float32, device=dev)
     wx, wy, ww, wh = weights
-    _tok = _pb("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4)
-    rc = lib.mega_postprocess_candidates_batched(_ptr(logits), _ptr(deltas), _ptr(props), _ptr(nprop), B, R, NC, wx, wy,
-                                                 ww, wh, float(im_w), float(im_h), float(score_thresh), _ptr(cb), _ptr(cs),
-                                                 _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_postprocess_candidates_batched")
+    _call("mega_postprocess_candidates_batched", logits, deltas, props, nprop, B, R, NC, wx, wy, ww, wh, float(im_w),
+          float(im_h), float(score_thresh), cb, cs, prof=("postprocess", 0.0, (logits.numel() + deltas.numel()) * 4))
     return cb, cs
 
 
@@ -738,16 +670,11 @@ def bbox_aug_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_th
     (boxes [F,cap,4], scores [F,cap], labels [F,cap] i64, counts [F] i32 device), cap = (NC-1) * K * R: frame f's
     detections are the first counts[f] rows; the rows past them are not written.  Raises ValueError beyond K = 16 views or
     K * R = 8192 rows per class."""
-    _gpu(cboxes, cscores)
-    lib = _lib.load()
     F, K, R, NC, (ob, os_, ol, oc), (vw, vh, vf), ws, nb = _merge_setup(
-        "bbox_aug_merge", lib.mega_bbox_aug_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
-    _tok = _pb("bbox_aug_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
-    rc = lib.mega_bbox_aug_merge(_ptr(cboxes), _ptr(cscores), F, K, R, NC, vw, vh, vf, float(score_thresh),
-                                 float(nms_thresh), int(strict_gt), int(max_det), _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc),
-                                 _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_bbox_aug_merge")
+        "bbox_aug_merge", _lib.load().mega_bbox_aug_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
+    _call("mega_bbox_aug_merge", cboxes, cscores, F, K, R, NC, vw, vh, vf, float(score_thresh), float(nms_thresh),
+          int(strict_gt), int(max_det), ob, os_, ol, oc, ws, nb,
+          prof=("bbox_aug_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4))
     return ob, os_, ol, oc
 
 
@@ -760,8 +687,6 @@ def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh
     """bbox_aug_merge with soft-NMS and / or box voting as the final filter (include/mega_hip.h mega_soft_merge; the
     definition is soft_nms.py's).  soft_method None | "linear" | "gaussian"; vote_scoring "ID" | "AVG".  Inputs, outputs
     and limits as bbox_aug_merge; with soft_method None and vote False the result is bbox_aug_merge's, bit for bit."""
-    _gpu(cboxes, cscores)
-    lib = _lib.load()
     if soft_method not in SOFT_NMS_METHODS:
         raise ValueError("soft_merge: soft_method %r, not None, 'linear' or 'gaussian'" % (soft_method,))
     if vote_scoring not in BBOX_VOTE_SCORING:
@@ -771,14 +696,11 @@ def soft_merge(cboxes, cscores, view_sizes, view_flips, score_thresh, nms_thresh
     if not 0 < float(vote_thresh) <= 1:
         raise ValueError("soft_merge: vote_thresh = %r must be in (0, 1]" % (vote_thresh,))
     F, K, R, NC, (ob, os_, ol, oc), (vw, vh, vf), ws, nb = _merge_setup(
-        "soft_merge", lib.mega_soft_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
-    _tok = _pb("soft_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4)
-    rc = lib.mega_soft_merge(_ptr(cboxes), _ptr(cscores), F, K, R, NC, vw, vh, vf, float(score_thresh),
-                             float(nms_thresh), int(strict_gt), SOFT_NMS_METHODS[soft_method], float(sigma),
-                             1 if vote else 0, float(vote_thresh), BBOX_VOTE_SCORING[vote_scoring], int(max_det),
-                             _ptr(ob), _ptr(os_), _ptr(ol), _ptr(oc), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_soft_merge")
+        "soft_merge", _lib.load().mega_soft_merge_workspace_bytes, cboxes, cscores, view_sizes, view_flips)
+    _call("mega_soft_merge", cboxes, cscores, F, K, R, NC, vw, vh, vf, float(score_thresh), float(nms_thresh),
+          int(strict_gt), SOFT_NMS_METHODS[soft_method], float(sigma), 1 if vote else 0, float(vote_thresh),
+          BBOX_VOTE_SCORING[vote_scoring], int(max_det), ob, os_, ol, oc, ws, nb,
+          prof=("soft_merge", 0.0, (cboxes.numel() + cscores.numel()) * 4))
     return ob, os_, ol, oc
 
 
@@ -790,8 +712,6 @@ def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False
     Only the logits of the keys below Nk are written: the pad columns Nk .. ldp-1 of the rows, and the pad-key slots of the
     last tile, hold whatever the allocator's block held (NaN included).  The attention kernels never let a pad key's logit
     reach the softmax."""
-    _gpu(rois_q, rois_k, wg_t, bg, dim_mat)
-    lib = _lib.load()
     Nq, Nk = rois_q.shape[0], rois_k.shape[0]
     if tiled:        # one problem of the batched launch (the tile-ordered kernel has no other launch form)
         assert not precise, "the tile-ordered position logits are bf16 / f16"
@@ -800,11 +720,8 @@ def position_logits(rois_q, rois_k, wg_t, bg, dim_mat, precise=True, tiled=False
         return position_logits_batched([rois_q], [rois_k], wg_t, bg, dim_mat, precise=False, tiled=tiled)[0]
     ldp = (Nk + 31) // 32 * 32
     out = torch.empty((16, Nq, ldp), dtype=torch.float32, device=rois_q.device)
-    _tok = _pb("pos_logits", 2.0 * Nq * Nk * 1024, 16.0 * Nq * ldp * 4)
-    rc = lib.mega_position_logits(_ptr(rois_q.contiguous()), _ptr(rois_k.contiguous()), _ptr(wg_t), _ptr(bg),
-                                  _ptr(dim_mat), _ptr(out), Nq, Nk, ldp, int(precise), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_position_logits")
+    _call("mega_position_logits", rois_q.contiguous(), rois_k.contiguous(), wg_t, bg, dim_mat, out, Nq, Nk, ldp,
+          int(precise), prof=("pos_logits", 2.0 * Nq * Nk * 1024, 16.0 * Nq * ldp * 4))
     return out
 
 
@@ -828,16 +745,8 @@ def _even_chunks(n, cap):
     return -(-n // launches) if launches else cap
 
 
-class _AttnDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("q", "k", "vt", "pos", "pos_tiled", "resid", "bias_v", "out", "ws")] + \
-               [("ws_bytes", ctypes.c_size_t)] + \
-               [(n, ctypes.c_int) for n in ("ldq", "ldk", "ldv", "ldp", "ldr", "ldo", "Nq", "Nk", "io_f32", "nk1")] + \
-               [("k2", ctypes.c_void_p), ("vt2", ctypes.c_void_p), ("ldv2", ctypes.c_int), ("reserved", ctypes.c_int)]
-
-
-class _PosDesc(ctypes.Structure):
-    _fields_ = [("rois_q", ctypes.c_void_p), ("rois_k", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("Nq", ctypes.c_int), ("Nk", ctypes.c_int)]
+# the descriptor structs of the batched / segmented entry points, as include/mega_hip.h declares them
+_AttnDesc, _PosDesc, _CopySeg = (_lib.STRUCTS[n] for n in ("mega_attn_desc", "mega_pos_desc", "mega_copy_seg"))
 
 
 def position_logits_batched(rois_qs, rois_ks, wg_t, bg, dim_mat, precise=True, tiled=False):
@@ -847,8 +756,7 @@ def position_logits_batched(rois_qs, rois_ks, wg_t, bg, dim_mat, precise=True, t
         return [position_logits(a, b, wg_t, bg, dim_mat, precise=precise, tiled=False) for a, b in zip(rois_qs, rois_ks)]
     tdt = torch.bfloat16 if tiled is True else tiled
     assert tdt in _HALF, "the tile-ordered position logits are bf16 / f16"
-    _gpu(wg_t, bg, dim_mat, *rois_qs, *rois_ks)
-    lib = _lib.load()
+    _gpu(*rois_qs, *rois_ks)      # (they reach the kernel through the descriptors, not through _call)
     outs, keep = [], []
     for a, b in zip(rois_qs, rois_ks):
         a, b = a.contiguous(), b.contiguous()
@@ -862,11 +770,9 @@ def position_logits_batched(rois_qs, rois_ks, wg_t, bg, dim_mat, precise=True, t
             a, b = keep[o + i]
             arr[i].rois_q, arr[i].rois_k, arr[i].out = a.data_ptr(), b.data_ptr(), outs[o + i].data_ptr()
             arr[i].Nq, arr[i].Nk = a.shape[0], b.shape[0]
-        _tok = _pb("pos_logits", sum(2.0 * arr[i].Nq * arr[i].Nk * 1024 for i in range(n)),
-                   sum(outs[o + i].numel() * 2.0 for i in range(n)))
-        rc = lib.mega_position_logits_tiled_batched_dt(ctypes.addressof(arr), n, _ptr(wg_t), _ptr(bg), _ptr(dim_mat), _DT[tdt], _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_position_logits_tiled_batched_dt")
+        _call("mega_position_logits_tiled_batched_dt", ctypes.addressof(arr), n, wg_t, bg, dim_mat, _DT[tdt],
+              prof=("pos_logits", sum(2.0 * arr[i].Nq * arr[i].Nk * 1024 for i in range(n)),
+                    sum(outs[o + i].numel() * 2.0 for i in range(n))))
     return outs
 
 
@@ -875,7 +781,6 @@ def relation_attention_batched(items, groups=16):
     per 20 problems (+ one combine launch).  A problem's bits do not depend on what it is batched with."""
     if not items:
         return []
-    lib = _lib.load()
     dt = items[0]["q"].dtype
     # stream dtype: the residual's (the head's f32 activation stream over bf16 operands), else the operands'
     r0 = items[0].get("resid")
@@ -908,7 +813,7 @@ def relation_attention_batched(items, groups=16):
         assert (pos is None) == (items[0].get("pos") is None) and (pos is None or pos.dtype == items[0]["pos"].dtype)
         outs.append(out_all[o:o + q.shape[0]])
         o += q.shape[0]
-        nb = lib.mega_relation_attention_workspace_bytes(q.shape[0], it["Nk"], groups)
+        nb = _lib.load().mega_relation_attention_workspace_bytes(q.shape[0], it["Nk"], groups)
         wss.append(_ws(nb, q.device) if nb else None)
     per = _even_chunks(len(items), _MAX_BATCHED)
     for o in range(0, len(items), per):
@@ -941,16 +846,9 @@ def relation_attention_batched(items, groups=16):
             fl += 4.0 * Nq * Nk * 64 * groups
             by += (q.numel() + k.numel() + vt.numel()) * q.element_size() + outs[o + i].numel() * outs[o + i].element_size() + \
                 (0 if pos is None else pos.numel() * pos.element_size())
-        _tok = _pb("attention_" + _ATT_NAME.get(dt, "f32"), fl, by)
-        rc = lib.mega_relation_attention_batched(ctypes.addressof(arr), n, groups, 1.0 / math.sqrt(64.0), _DT[dt], _stream())
-        _pe(_tok)
-        _lib.check(rc, "mega_relation_attention_batched")
+        _call("mega_relation_attention_batched", ctypes.addressof(arr), n, groups, 1.0 / math.sqrt(64.0), _DT[dt],
+              prof=("attention_" + _ATT_NAME.get(dt, "f32"), fl, by))
     return outs
-
-
-class _CopySeg(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_stride", ctypes.c_longlong),
-                ("dst_stride", ctypes.c_longlong), ("rows", ctypes.c_int), ("row_bytes", ctypes.c_int)]
 
 
 def copy_blocks(pairs):
@@ -959,7 +857,6 @@ def copy_blocks(pairs):
     pairs = [(d, s_) for d, s_ in pairs if d.numel() > 0]
     if not pairs:
         return
-    lib = _lib.load()
     arr = (_CopySeg * len(pairs))()
     nbytes = 0
     for i, (d, s_) in enumerate(pairs):
@@ -971,10 +868,7 @@ def copy_blocks(pairs):
         arr[i].src_stride, arr[i].dst_stride = s_.stride(0) * es, d.stride(0) * es
         arr[i].rows, arr[i].row_bytes = d.shape[0], d.shape[1] * es
         nbytes += 2 * d.numel() * es
-    _tok = _pb("assemble", 0.0, nbytes)
-    rc = lib.mega_copy_segments(ctypes.addressof(arr), len(pairs), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_copy_segments")
+    _call("mega_copy_segments", ctypes.addressof(arr), len(pairs), prof=("assemble", 0.0, nbytes))
 
 
 def multi_cat(groups):
@@ -1005,7 +899,6 @@ def cat_rows_cast_bf16(pieces, dtype=torch.bfloat16):
     ONE launch that never writes the f32 concatenation: the K / V sources of the relation modules under an f32 activation
     stream."""
     pieces = [p for p in pieces if p.shape[0] > 0]
-    lib = _lib.load()
     K = pieces[0].shape[1]
     assert dtype in _HALF
     out = torch.empty((sum(p.shape[0] for p in pieces), K), dtype=dtype, device=pieces[0].device)
@@ -1020,37 +913,26 @@ def cat_rows_cast_bf16(pieces, dtype=torch.bfloat16):
         arr[i].rows, arr[i].row_bytes = p.shape[0], K * 4
         o += p.shape[0]
         nbytes += p.numel() * 6
-    _tok = _pb("assemble", 0.0, nbytes)
-    rc = lib.mega_copy_cast_segments_dt(ctypes.addressof(arr), len(pieces), _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_copy_cast_segments_dt")
+    _call("mega_copy_cast_segments_dt", ctypes.addressof(arr), len(pieces), _DT[dtype], prof=("assemble", 0.0, nbytes))
     return out
 
 
 def resize_bilinear_u8(frames_u8, out_hw, tables):
     """uint8 [N,Hi,Wi,3] -> [N,Ho,Wo,3], Pillow-exact BILINEAR.  tables = feed.ResizeTables (device coefficient tables)."""
-    _gpu(frames_u8)
-    lib = _lib.load()
     N, Hi, Wi, C = frames_u8.shape
     Ho, Wo = out_hw
     assert C == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     assert tables.in_hw == (Hi, Wi) and tables.out_hw == (Ho, Wo)
     out = torch.empty((N, Ho, Wo, 3), dtype=torch.uint8, device=frames_u8.device)
     tmp = torch.empty((N, Hi, Wo, 3), dtype=torch.uint8, device=frames_u8.device) if (Hi != Ho and Wi != Wo) else None
-    _tok = _pb("resize", 0.0, frames_u8.numel() + out.numel() * 3)
-    rc = lib.mega_resize_bilinear_u8(_ptr(frames_u8), _ptr(out), _ptr(tmp), N, Hi, Wi, Ho, Wo, _ptr(tables.bounds_h),
-                                     _ptr(tables.coef_h), tables.ksize_h, _ptr(tables.bounds_v), _ptr(tables.coef_v),
-                                     tables.ksize_v, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_resize_bilinear_u8")
+    _call("mega_resize_bilinear_u8", frames_u8, out, tmp, N, Hi, Wi, Ho, Wo, tables.bounds_h, tables.coef_h, tables.ksize_h,
+          tables.bounds_v, tables.coef_v, tables.ksize_v, prof=("resize", 0.0, frames_u8.numel() + out.numel() * 3))
     return out
 
 
 def resize_bilinear_u8_flip(frames_u8, out_hw, tables, hflip=True):
     """resize_bilinear_u8 followed by a left-right mirror (PIL resize(BILINEAR).transpose(FLIP_LEFT_RIGHT)), the mirror
     written by the last pass.  tables may be None when out_hw is the input size (the mirror alone)."""
-    _gpu(frames_u8)
-    lib = _lib.load()
     N, Hi, Wi, C = frames_u8.shape
     Ho, Wo = out_hw
     assert C == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
@@ -1059,32 +941,23 @@ def resize_bilinear_u8_flip(frames_u8, out_hw, tables, hflip=True):
     out = torch.empty((N, Ho, Wo, 3), dtype=torch.uint8, device=frames_u8.device)
     tmp = torch.empty((N, Hi, Wo, 3), dtype=torch.uint8, device=frames_u8.device) if (Hi != Ho and Wi != Wo) else None
     t = tables
-    _tok = _pb("resize", 0.0, frames_u8.numel() + out.numel() * 3)
-    rc = lib.mega_resize_bilinear_u8_flip(_ptr(frames_u8), _ptr(out), _ptr(tmp), N, Hi, Wi, Ho, Wo,
-                                          _ptr(t.bounds_h) if t else None, _ptr(t.coef_h) if t else None,
-                                          t.ksize_h if t else 0, _ptr(t.bounds_v) if t else None,
-                                          _ptr(t.coef_v) if t else None, t.ksize_v if t else 0, int(bool(hflip)),
-                                          _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_resize_bilinear_u8_flip")
+    _call("mega_resize_bilinear_u8_flip", frames_u8, out, tmp, N, Hi, Wi, Ho, Wo, t.bounds_h if t else None,
+          t.coef_h if t else None, t.ksize_h if t else 0, t.bounds_v if t else None, t.coef_v if t else None,
+          t.ksize_v if t else 0, int(bool(hflip)),
+          prof=("resize", 0.0, frames_u8.numel() + out.numel() * 3))
     return out
 
 
 def preprocess_frames(frames_u8, mean, to_bgr=True, out=None):
     """uint8 [N,H,W,3] RGB -> f32 [N,3,H,W] (BGR*255 - mean); out: optional contiguous f32 [N,3,H,W] to write into."""
-    _gpu(frames_u8, out)
-    lib = _lib.load()
     N, H, W, C = frames_u8.shape
     assert C == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     if out is None:
         out = torch.empty((N, 3, H, W), dtype=torch.float32, device=frames_u8.device)
     else:
         assert out.shape == (N, 3, H, W) and out.dtype == torch.float32 and out.is_contiguous()
-    _tok = _pb("preprocess", 0.0, frames_u8.numel() * 5)
-    rc = lib.mega_preprocess_frames(_ptr(frames_u8), _ptr(out), N, H, W, float(mean[0]), float(mean[1]),
-                                    float(mean[2]), int(to_bgr), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_preprocess_frames")
+    _call("mega_preprocess_frames", frames_u8, out, N, H, W, float(mean[0]), float(mean[1]), float(mean[2]), int(to_bgr),
+          prof=("preprocess", 0.0, frames_u8.numel() * 5))
     return out
 
 
@@ -1092,14 +965,9 @@ def cast_half(x, dtype):
     """f32 -> bf16 / f16 copy (round to nearest even) of a contiguous tensor; an input of that dtype is returned as it is."""
     if x.dtype == dtype:
         return x
-    _gpu(x)
-    lib = _lib.load()
     assert x.dtype == torch.float32 and x.is_contiguous() and dtype in _HALF
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
-    _tok = _pb("assemble", 0.0, x.numel() * 6.0)
-    rc = lib.mega_cast_f32_to_half(_ptr(x), _ptr(out), x.numel(), _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_cast_f32_to_half")
+    _call("mega_cast_f32_to_half", x, out, x.numel(), _DT[dtype], prof=("assemble", 0.0, x.numel() * 6.0))
     return out
 
 
@@ -1110,15 +978,10 @@ def cast_bf16(x):
 def split_bf16x3(x):
     """f32 [M,K] -> bf16 [M,3K] = [hi | lo | hi] (hi = bf16(x), lo = bf16(x - hi)): A operand of a split-precision bf16
     GEMM against weights packed by split_weight_bf16x3."""
-    _gpu(x)
-    lib = _lib.load()
     M, K = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and K % 8 == 0
     out = torch.empty((M, 3 * K), dtype=torch.bfloat16, device=x.device)
-    _tok = _pb("assemble", 0.0, x.numel() * 10.0)
-    rc = lib.mega_split_f32_to_bf16x3(_ptr(x), _ptr(out), M, K, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_split_f32_to_bf16x3")
+    _call("mega_split_f32_to_bf16x3", x, out, M, K, prof=("assemble", 0.0, x.numel() * 10.0))
     return out
 
 
@@ -1163,15 +1026,10 @@ class Planes(object):
 
 def split_planes(x, dtype=torch.bfloat16):
     """f32 [..., C] (contiguous, C % 8 == 0) -> Planes of `dtype` pairs (one launch)."""
-    _gpu(x)
-    lib = _lib.load()
     C = x.shape[-1]
     assert x.dtype == torch.float32 and x.is_contiguous() and C % 8 == 0 and dtype in _HALF
     out = torch.empty(tuple(x.shape[:-1]) + (2 * C,), dtype=dtype, device=x.device)
-    _tok = _pb("assemble", 0.0, x.numel() * 8.0)
-    rc = lib.mega_split_f32_to_planes_dt(_ptr(x), _ptr(out), x.numel() // C, C, _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_split_f32_to_planes_dt")
+    _call("mega_split_f32_to_planes_dt", x, out, x.numel() // C, C, _DT[dtype], prof=("assemble", 0.0, x.numel() * 8.0))
     return Planes(out, C)
 
 
@@ -1217,8 +1075,6 @@ def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1
     else:
         xt, ldi = x.t, 2 * x.C
     assert xt.dtype == pdt and (residual is None or residual.t.dtype == pdt)
-    _gpu(xt, w, scale, bias, None if residual is None else residual.t)
-    lib = _lib.load()
     N, H, W, C = x.shape
     Cout, R, S, Cw = w.shape
     assert Cw == kmul * C and w.dtype == pdt and w.is_contiguous() and C % 64 == 0 and Cout % 8 == 0
@@ -1243,18 +1099,15 @@ def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1
                          "frame-stage batch (ClipEngine steps_per_batch) or split the call over M")
     K = R * S * Cw
     M = N * Ho * Wo
-    _tok = None
+    prof = None
     if _PROF is not None:
-        _tok = _pb("igemm8_sp_" + operands, 2.0 * M * Cout * K,
-                   xt.numel() * (2.0 if operands != "hi" or xt is x else 1.0) + w.numel() * 2.0 + out.numel() * out.element_size()
-                   + (0 if residual is None else residual.t.numel() * 2.0), detail="%dx%dx%d (%dx%d)" % (M, Cout, K, R, S))
-    nb = lib.mega_conv2d_nhwc_workspace_bytes(M, Cout, K) if mode == 2 and residual is None else 0
+        prof = ("igemm8_sp_" + operands, 2.0 * M * Cout * K,
+                xt.numel() * (2.0 if operands != "hi" or xt is x else 1.0) + w.numel() * 2.0 + out.numel() * out.element_size()
+                + (0 if residual is None else residual.t.numel() * 2.0), "%dx%dx%d (%dx%d)" % (M, Cout, K, R, S))
+    nb = _lib.load().mega_conv2d_nhwc_workspace_bytes(M, Cout, K) if mode == 2 and residual is None else 0
     ws = _ws(nb, x.device) if nb else None
-    rc = lib.mega_conv2d_nhwc_sp_dt(_ptr(xt), ldi, 2 * C if kwrap else 0, _ptr(w), _ptr(scale), _ptr(bias),
-                                    None if residual is None else _ptr(residual.t), 0, _ptr(out), ldo, mode, N, H, W, Cw, Cout,
-                                    R, S, stride, pad, dil, int(relu), _DT[pdt], _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_conv2d_nhwc_sp_dt")
+    _call("mega_conv2d_nhwc_sp_dt", xt, ldi, 2 * C if kwrap else 0, w, scale, bias, None if residual is None else residual.t,
+          0, out, ldo, mode, N, H, W, Cw, Cout, R, S, stride, pad, dil, int(relu), _DT[pdt], ws, nb, prof=prof)
     return Planes(out, Cout) if mode == 1 else out
 
 
@@ -1283,10 +1136,7 @@ def linear_transposed_x3(w, x, ld):
     xs = torch.empty((M8, 3 * K), dtype=torch.bfloat16, device=x.device)
     if M8 > M:
         xs[M:].zero_()
-    lib = _lib.load()
-    _gpu(x)
-    rc = lib.mega_split_f32_to_bf16x3(_ptr(x.contiguous()), _ptr(xs), M, K, _stream())
-    _lib.check(rc, "mega_split_f32_to_bf16x3")
+    _call("mega_split_f32_to_bf16x3", x.contiguous(), xs, M, K)
     out = torch.empty((Nout, ld), dtype=torch.float32, device=x.device)
     if ld > M8:
         out[:, M8:].zero_()
@@ -1311,8 +1161,6 @@ def linear_transposed(w, x, ld, residual=None):
     if isinstance(w, X3Weight):
         assert residual is None
         return linear_transposed_x3(w, x, ld)
-    _gpu(w, x, residual)
-    lib = _lib.load()
     Nout, K = w.shape
     M = x.shape[0]
     assert x.shape[1] == K and ld >= M and w.dtype == x.dtype and w.is_contiguous() and x.is_contiguous()
@@ -1322,29 +1170,22 @@ def linear_transposed(w, x, ld, residual=None):
     out = torch.empty((Nout, ld), dtype=x.dtype, device=x.device)
     if ld > M:
         out[:, M:].zero_()
-    _tok = None
+    prof = None
     if _PROF is not None:
-        _tok = _pb(_igemm_family(lib, Nout, M, K, x.dtype),
-                   2.0 * Nout * M * K, (w.numel() + x.numel() + out.numel()) * x.element_size())
-    rc = lib.mega_conv2d_nhwc(_ptr(w), _ptr(x), None, None, _ptr(residual), _ptr(out), Nout, 1, 1, K, M, 1, 1, 1, 0, 1, 0,
-                              ld, ld, _dt(x), _dt(x), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_conv2d_nhwc(transposed)")
+        prof = (_igemm_family(Nout, M, K, x.dtype), 2.0 * Nout * M * K, (w.numel() + x.numel() + out.numel()) * x.element_size())
+    _call("mega_conv2d_nhwc", w, x, None, None, residual, out, Nout, 1, 1, K, M, 1, 1, 1, 0, 1, 0, ld, ld, _dt(x), _dt(x),
+          prof=prof, what="mega_conv2d_nhwc(transposed)")
     return out
 
 
 def dff_warp_scale(feats, flow, scale):
     """feats NHWC [H,W,C] (key frame), flow [2,H,W] f32, scale [H,W,C] -> warp(feats, flow) * scale  [H,W,C]."""
-    _gpu(feats, flow, scale)
-    lib = _lib.load()
     H, W, C = feats.shape
     assert feats.is_contiguous() and flow.is_contiguous() and scale.is_contiguous()
     assert flow.dtype == torch.float32 and flow.shape == (2, H, W) and scale.shape == feats.shape and scale.dtype == feats.dtype
     out = torch.empty_like(feats)
-    _tok = _pb("dff_warp", 0.0, 6.0 * feats.numel() * feats.element_size())
-    rc = lib.mega_dff_warp_scale(_ptr(feats), _ptr(flow), _ptr(scale), _ptr(out), H, W, C, _dt(feats), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_dff_warp_scale")
+    _call("mega_dff_warp_scale", feats, flow, scale, out, H, W, C, _dt(feats),
+          prof=("dff_warp", 0.0, 6.0 * feats.numel() * feats.element_size()))
     return out
 
 
@@ -1355,8 +1196,6 @@ def fgfa_warp_aggregate(feats, flow, Cf, key, want_weights=False, order=None, fl
     slot like feats ([S,2,H,W]) or, with flow_pos = the key frame's window position, by window position ([T,2,H,W]: exactly
     the window's pairs, in window order).  out: the result tensor to write ([H,W,Cf], contiguous, of feats' dtype).
     A shape the kernel cannot take (see include/mega_hip.h) raises the library's "bad argument" error before any launch."""
-    _gpu(feats, flow, order, out)
-    lib = _lib.load()
     S, H, W, C = feats.shape
     T = S if order is None else order.numel() - 1
     assert feats.is_contiguous() and flow.is_contiguous() and flow.dtype == torch.float32
@@ -1365,41 +1204,31 @@ def fgfa_warp_aggregate(feats, flow, Cf, key, want_weights=False, order=None, fl
         out = torch.empty((H, W, Cf), dtype=feats.dtype, device=feats.device)
     assert tuple(out.shape) == (H, W, Cf) and out.dtype == feats.dtype and out.is_contiguous()
     wts = torch.empty((T, H, W), dtype=torch.float32, device=feats.device) if want_weights else None
-    _tok = _pb("fgfa_warp", 0.0, 4.0 * feats.numel() * feats.element_size())
-    if order is not None:
-        assert order.dtype == torch.int32 and order.is_contiguous()
-        if flow_pos is not None:
-            rc = lib.mega_fgfa_warp_aggregate_ring_pos(_ptr(feats), _ptr(flow), _ptr(out), _ptr(wts), T, H, W, Cf, C - Cf,
-                                                       _ptr(order), int(flow_pos), _dt(feats), _stream())
-            _pe(_tok)
-            _lib.check(rc, "mega_fgfa_warp_aggregate_ring_pos")
-            return (out, wts) if want_weights else out
-        rc = lib.mega_fgfa_warp_aggregate_ring(_ptr(feats), _ptr(flow), _ptr(out), _ptr(wts), T, H, W, Cf, C - Cf,
-                                               _ptr(order), _dt(feats), _stream())
+    prof = ("fgfa_warp", 0.0, 4.0 * feats.numel() * feats.element_size())
+    if order is None:
+        _call("mega_fgfa_warp_aggregate", feats, flow, out, wts, T, H, W, Cf, C - Cf, key, _dt(feats), prof=prof)
+        return (out, wts) if want_weights else out
+    assert order.dtype == torch.int32 and order.is_contiguous()
+    if flow_pos is not None:
+        _call("mega_fgfa_warp_aggregate_ring_pos", feats, flow, out, wts, T, H, W, Cf, C - Cf, order, int(flow_pos), _dt(feats),
+              prof=prof)
     else:
-        rc = lib.mega_fgfa_warp_aggregate(_ptr(feats), _ptr(flow), _ptr(out), _ptr(wts), T, H, W, Cf, C - Cf, key,
-                                          _dt(feats), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_fgfa_warp_aggregate")
+        _call("mega_fgfa_warp_aggregate_ring", feats, flow, out, wts, T, H, W, Cf, C - Cf, order, _dt(feats), prof=prof,
+              what="mega_fgfa_warp_aggregate")
     return (out, wts) if want_weights else out
 
 
 def fgfa_warp_aggregate_group(feats, flow, Cf, orders, key_pos):
     """fgfa_warp_aggregate(..., order=orders[g], flow_pos=key_pos) for the G key frames of a group in ONE launch: feats ring
     [S,H,W,Cf+Ce], flow f32 [G*T,2,H,W] (window order per key frame), orders i32 [G,1+T] -> [G,H,W,Cf]; same bits per key frame."""
-    _gpu(feats, flow, orders)
-    lib = _lib.load()
     S, H, W, C = feats.shape
     G, T1 = orders.shape
     T = T1 - 1
     assert feats.is_contiguous() and flow.is_contiguous() and flow.dtype == torch.float32 and tuple(flow.shape) == (G * T, 2, H, W)
     assert orders.dtype == torch.int32 and orders.is_contiguous()
     out = torch.empty((G, H, W, Cf), dtype=feats.dtype, device=feats.device)
-    _tok = _pb("fgfa_warp", 0.0, 4.0 * G * T * H * W * C * feats.element_size())
-    rc = lib.mega_fgfa_warp_aggregate_ring_pos_batched(_ptr(feats), _ptr(flow), _ptr(out), None, T, H, W, Cf, C - Cf, _ptr(orders),
-                                                       int(key_pos), G, _dt(feats), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_fgfa_warp_aggregate_ring_pos_batched")
+    _call("mega_fgfa_warp_aggregate_ring_pos_batched", feats, flow, out, None, T, H, W, Cf, C - Cf, orders, int(key_pos), G,
+          _dt(feats), prof=("fgfa_warp", 0.0, 4.0 * G * T * H * W * C * feats.element_size()))
     return out
 
 
@@ -1408,8 +1237,6 @@ def fgfa_pair_taps(refs, cur=None, order=None, dtype=torch.bfloat16):
     key frame `cur` [1,3,H,W] (one for all pairs) or [T,3,H,W] (one per pair), or cur=None with `order` (i32 on the device):
     the key frame is refs[order[0]] (the engine's image ring).  -> `dtype` [T, ceil(H/2) + 6, ceil(W/2), 64]:
     out[t, 3 + h, w, s * 8 + c] = avgpool2x2_ceil(cat([cur, refs[t]]))[h, w - 3 + s, c], zeros elsewhere."""
-    _gpu(refs, cur, order)
-    lib = _lib.load()
     T, C, H, W = refs.shape
     assert C == 3 and refs.dtype == torch.float32 and refs.stride(1) == H * W and refs.stride(2) == W and refs.stride(3) == 1
     assert dtype in _HALF and (cur is not None or order is not None)
@@ -1421,22 +1248,17 @@ def fgfa_pair_taps(refs, cur=None, order=None, dtype=torch.bfloat16):
     else:
         assert order.dtype == torch.int32 and order.is_contiguous()
     out = torch.empty((T, (H + 1) // 2 + 6, (W + 1) // 2, 64), dtype=dtype, device=refs.device)
-    _tok = _pb("fgfa_pair_taps", 0.0, refs.numel() * 4.0 + out.numel() * 2.0)
-    rc = lib.mega_fgfa_pair_taps(_ptr(refs), refs.stride(0), _ptr(cur), cs, _ptr(order), _ptr(out), T, H, W, _DT[dtype], _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_fgfa_pair_taps")
+    _call("mega_fgfa_pair_taps", refs, refs.stride(0), cur, cs, order, out, T, H, W, _DT[dtype],
+          prof=("fgfa_pair_taps", 0.0, refs.numel() * 4.0 + out.numel() * 2.0))
     return out
 
 
 def avgpool2x2_ceil(x):
     """nn.AvgPool2d(2, 2, ceil_mode=True) on NHWC."""
-    _gpu(x)
-    lib = _lib.load()
     N, H, W, C = x.shape
     assert x.is_contiguous()
     out = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), dtype=x.dtype, device=x.device)
-    rc = lib.mega_avgpool2x2_ceil_nhwc(_ptr(x), _ptr(out), N, H, W, C, _dt(x), _stream())
-    _lib.check(rc, "mega_avgpool2x2_ceil_nhwc")
+    _call("mega_avgpool2x2_ceil_nhwc", x, out, N, H, W, C, _dt(x))
     return out
 
 
@@ -1446,8 +1268,6 @@ def vid_eval_match(det_box, det_label, det_off, order, ratio, gt_box, gt_label, 
     det_box [N,4] f32, det_label [N] i32, det_off [F+1] i64, order [N] i32, ratio [F,2] f32, gt_box [G,4] f32,
     gt_label [G] i32, gt_motion [G] f64 or None, gt_off [F+1] i64, ranges [R,3] f64 (lo, hi, empty_weight).
     -> match [R,N] u8, pred_ignore [R,N] f64, n_pos [R,C] i32 (all on the device)."""
-    _gpu(det_box, det_label, det_off, order, ratio, gt_box, gt_label, gt_motion, gt_off, ranges)
-    lib = _lib.load()
     N, F, R = det_box.shape[0], det_off.shape[0] - 1, ranges.shape[0]
     for t, dt in ((det_box, torch.float32), (det_label, torch.int32), (det_off, torch.int64), (order, torch.int32),
                   (ratio, torch.float32), (gt_box, torch.float32), (gt_label, torch.int32), (gt_motion, torch.float64),
@@ -1457,32 +1277,22 @@ def vid_eval_match(det_box, det_label, det_off, order, ratio, gt_box, gt_label, 
     match = torch.empty((R, N), dtype=torch.uint8, device=dev)
     pign = torch.empty((R, N), dtype=torch.float64, device=dev)
     n_pos = torch.empty((R, C), dtype=torch.int32, device=dev)
-    _tok = _pb("vid_eval_match")
-    rc = lib.mega_vid_eval_match(_ptr(det_box), _ptr(det_label), _ptr(det_off), _ptr(order), _ptr(ratio), _ptr(gt_box),
-                                 _ptr(gt_label), _ptr(gt_motion), _ptr(gt_off), _ptr(ranges), F, R, int(C), N, int(max_gt),
-                                 _ptr(match), _ptr(pign), _ptr(n_pos), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_vid_eval_match")
+    _call("mega_vid_eval_match", det_box, det_label, det_off, order, ratio, gt_box, gt_label, gt_motion, gt_off, ranges, F,
+          R, int(C), N, int(max_gt), match, pign, n_pos, prof=("vid_eval_match",))
     return match, pign, n_pos
 
 
 def vid_eval_ap(match, pred_ignore, gorder, seg_off, n_pos):
     """vid_eval.py:255-343: per (range, class) precision / recall scans and AP over the classes' detections in global
     order gorder[seg_off[l] : seg_off[l+1]].  -> ap [R,C] f64 on the device (NaN where n_pos == 0)."""
-    _gpu(match, pred_ignore, gorder, seg_off, n_pos)
-    lib = _lib.load()
     R, C = n_pos.shape
     N = match.shape[1]
     assert match.dtype == torch.uint8 and pred_ignore.dtype == torch.float64 and gorder.dtype == torch.int32
     assert seg_off.dtype == torch.int64 and n_pos.dtype == torch.int32 and seg_off.shape[0] == C + 1
     ap = torch.empty((R, C), dtype=torch.float64, device=match.device)
-    nb = lib.mega_vid_eval_workspace_bytes(N, C, R)
+    nb = _lib.load().mega_vid_eval_workspace_bytes(N, C, R)
     ws = _ws(nb, match.device)
-    _tok = _pb("vid_eval_ap")
-    rc = lib.mega_vid_eval_ap(_ptr(match), _ptr(pred_ignore), _ptr(gorder), _ptr(seg_off), _ptr(n_pos), C, R, N, _ptr(ap),
-                              _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_vid_eval_ap")
+    _call("mega_vid_eval_ap", match, pred_ignore, gorder, seg_off, n_pos, C, R, N, ap, ws, nb, prof=("vid_eval_ap",))
     return ap
 
 
@@ -1491,8 +1301,6 @@ def proposal_recall_match(box, off, order, ratio, gt_box, gt_off, limits, max_li
     (include/mega_hip.h mega_proposal_recall_match).  box [N,4] f32, off [F+1] i64, order [N] i32 (each frame's run in
     evaluation order), ratio [F,2] f32, gt_box [G,4] f32, gt_off [F+1] i64, limits [nL] i32 (each <= max_limit <= 1024).
     -> gt_overlap [nL,G] f32, gt_prop [nL,G] i32 (position in the frame's order, -1: unmatched), on the device."""
-    _gpu(box, off, order, ratio, gt_box, gt_off, limits)
-    lib = _lib.load()
     N, F, G, nL = box.shape[0], off.shape[0] - 1, gt_box.shape[0], limits.shape[0]
     for t, dt in ((box, torch.float32), (off, torch.int64), (order, torch.int32), (ratio, torch.float32),
                   (gt_box, torch.float32), (gt_off, torch.int64), (limits, torch.int32)):
@@ -1502,12 +1310,8 @@ def proposal_recall_match(box, off, order, ratio, gt_box, gt_off, limits, max_li
     dev = box.device
     gt_overlap = torch.empty((nL, G), dtype=torch.float32, device=dev)
     gt_prop = torch.empty((nL, G), dtype=torch.int32, device=dev)
-    _tok = _pb("proposal_recall_match")
-    rc = lib.mega_proposal_recall_match(_ptr(box), _ptr(off), _ptr(order), _ptr(ratio), _ptr(gt_box), _ptr(gt_off),
-                                        _ptr(limits), F, nL, N, G, int(max_limit), int(max_gt), _ptr(gt_overlap),
-                                        _ptr(gt_prop), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_proposal_recall_match")
+    _call("mega_proposal_recall_match", box, off, order, ratio, gt_box, gt_off, limits, F, nL, N, G, int(max_limit),
+          int(max_gt), gt_overlap, gt_prop, prof=("proposal_recall_match",))
     return gt_overlap, gt_prop
 
 
@@ -1529,21 +1333,15 @@ def seq_nms(box, score, seg_off, tasks, F, C, link_iou, nms_iou, rescore_max):
     -> keep [N] u8, new_score [N] f32 (valid where keep; the other elements are the wrapper's zeros), stats [T,2] i64
     (iterations, DP frame steps), on the device.  Every box belongs to one task, so every element of keep is written.
     Synchronises the stream (the kernel's status word)."""
-    _gpu(box, score, seg_off, tasks)
-    lib = _lib.load()
     N, T = _check_video_tensors(box, score, seg_off, tasks, F, C)
     dev = box.device
     keep = torch.empty(N, dtype=torch.uint8, device=dev)
     new_score = torch.zeros(N, dtype=torch.float32, device=dev)
     stats = torch.zeros((T, 2), dtype=torch.int64, device=dev)
-    nb = lib.mega_seq_nms_workspace_bytes(N, C * F)
+    nb = _lib.load().mega_seq_nms_workspace_bytes(N, C * F)
     ws = _ws(nb, dev)
-    _tok = _pb("seq_nms")
-    rc = lib.mega_seq_nms(_ptr(box), _ptr(score), _ptr(seg_off), _ptr(tasks), T, int(F), int(C), N, float(link_iou),
-                          float(nms_iou), int(bool(rescore_max)), _ptr(keep), _ptr(new_score), _ptr(stats), _ptr(ws), nb,
-                          _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_seq_nms")
+    _call("mega_seq_nms", box, score, seg_off, tasks, T, int(F), int(C), N, float(link_iou), float(nms_iou),
+          int(bool(rescore_max)), keep, new_score, stats, ws, nb, prof=("seq_nms",))
     return keep, new_score, stats
 
 
@@ -1555,22 +1353,16 @@ def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, m
     open tracks.  -> root [N] i64 (index of the track's first box in this order, -1: no track), and valid at the roots
     cnt [N] i32, sum [N] f64, mx [N] f32, on the device (the kernel writes them at the roots only: the other elements are
     the wrapper's zeros).  Synchronises the stream (the kernel's status word)."""
-    _gpu(box, score, pos, seg_off, tasks)
-    lib = _lib.load()
     N, T = _check_video_tensors(box, score, seg_off, tasks, F, C, pos)
     dev = box.device
     root = torch.full((N,), -1, dtype=torch.int64, device=dev)
     cnt = torch.zeros(N, dtype=torch.int32, device=dev)
     acc = torch.zeros(N, dtype=torch.float64, device=dev)
     mx = torch.zeros(N, dtype=torch.float32, device=dev)
-    nb = lib.mega_link_tracks_workspace_bytes(T, int(max_open))
+    nb = _lib.load().mega_link_tracks_workspace_bytes(T, int(max_open))
     ws = _ws(max(nb, 1), dev)
-    _tok = _pb("link_tracks")
-    rc = lib.mega_link_tracks(_ptr(box), _ptr(score), _ptr(pos), _ptr(seg_off), _ptr(tasks), T, int(F), int(C), N,
-                              float(score_thresh), float(link_iou), int(max_gap), int(max_open), _ptr(root), _ptr(cnt),
-                              _ptr(acc), _ptr(mx), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_link_tracks")
+    _call("mega_link_tracks", box, score, pos, seg_off, tasks, T, int(F), int(C), N, float(score_thresh), float(link_iou),
+          int(max_gap), int(max_open), root, cnt, acc, mx, ws, nb, prof=("link_tracks",))
     return root, cnt, acc, mx
 
 
@@ -1579,16 +1371,11 @@ def tubelet_scores(score, off, use_max=False):
     """A tubelet's score as track_eval.py defines it (include/mega_hip.h mega_tubelet_scores).  score [M] f32: the members
     sorted by tubelet, then frame; off [U+1] i64.  -> [U] f64 on the device: the f64 sum in that order / the count, or the
     largest member with use_max."""
-    _gpu(score, off)
-    lib = _lib.load()
     M, U = score.shape[0], off.shape[0] - 1
     assert score.dtype == torch.float32 and off.dtype == torch.int64 and score.is_contiguous() and off.is_contiguous()
     assert score.shape == (M,) and off.shape == (U + 1,)
     out = torch.zeros(U, dtype=torch.float64, device=score.device)
-    _tok = _pb("tubelet_scores")
-    rc = lib.mega_tubelet_scores(_ptr(score), _ptr(off), U, M, int(bool(use_max)), _ptr(out), _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_tubelet_scores")
+    _call("mega_tubelet_scores", score, off, U, M, int(bool(use_max)), out, prof=("tubelet_scores",))
     return out
 
 
@@ -1602,8 +1389,6 @@ def tubelet_match(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off
     table does not fit LDS.  -> match [R,U] u8 (0 outside the tasks), matched_gt [R,U] i32 (GT slot, -1: none), hits /
     both [n_pairs] i32 (None without want_pairs), on the device; with return_workspace also the workspace's two tables
     [ws_pairs] i32, preset to -1.  Does not synchronise."""
-    _gpu(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off, tasks, offs, tubelet, tub_len, gt_len)
-    lib = _lib.load()
     M, Gb, T, U, J, slots = box.shape[0], gt_box.shape[0], tasks.shape[0], tub_len.shape[0], gt_len.shape[0], tubelet.shape[0]
     for t, dt in ((box, torch.float32), (frame, torch.int32), (rank, torch.int32), (seg_off, torch.int64),
                   (ratio, torch.float32), (gt_box, torch.float32), (gt_track, torch.int32), (gt_seg_off, torch.int64),
@@ -1621,18 +1406,13 @@ def tubelet_match(box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off
     matched_gt = torch.full((R, U), -1, dtype=torch.int32, device=dev)
     hits = torch.zeros(int(n_pairs), dtype=torch.int32, device=dev) if want_pairs else None
     both = torch.zeros(int(n_pairs), dtype=torch.int32, device=dev) if want_pairs else None
-    nb = lib.mega_tubelet_match_workspace_bytes(int(ws_pairs))
+    nb = _lib.load().mega_tubelet_match_workspace_bytes(int(ws_pairs))
     ws = _ws(max(nb, 1), dev)
     if return_workspace:
         ws.fill_(0xFF)
-    _tok = _pb("tubelet_match")
-    rc = lib.mega_tubelet_match(_ptr(box), _ptr(frame), _ptr(rank), _ptr(seg_off), _ptr(ratio), _ptr(gt_box), _ptr(gt_track),
-                                _ptr(gt_seg_off), _ptr(tasks), _ptr(offs), _ptr(tubelet), _ptr(tub_len), _ptr(gt_len),
-                                ctypes.cast(thr_c, ctypes.c_void_p), T, int(F), int(C), R, M, Gb, U, J, slots, int(n_pairs),
-                                int(ws_pairs), _ptr(match), _ptr(matched_gt), _ptr(hits), _ptr(both), _ptr(ws), nb,
-                                _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_tubelet_match")
+    _call("mega_tubelet_match", box, frame, rank, seg_off, ratio, gt_box, gt_track, gt_seg_off, tasks, offs, tubelet,
+          tub_len, gt_len, ctypes.cast(thr_c, ctypes.c_void_p), T, int(F), int(C), R, M, Gb, U, J, slots, int(n_pairs),
+          int(ws_pairs), match, matched_gt, hits, both, ws, nb, prof=("tubelet_match",))
     if return_workspace:
         n, half = int(ws_pairs), nb // 2             # two arrays of n i32, each rounded up to 256 bytes
         tabs = (ws[:4 * n].view(torch.int32), ws[half:half + 4 * n].view(torch.int32))
@@ -1648,8 +1428,6 @@ def motion_iou(gt_box, gt_track, gt_off, video_start, video_end, window, max_gt,
     (counts preset to -1: a frame the kernel skipped keeps it); with return_workspace also the workspace's slots as
     [G, 2W] i32 (the pair IoUs' bits, -1: no neighbour; preset to -1), or None when no frame needs it.  Does not
     synchronise."""
-    _gpu(gt_box, gt_track, gt_off, video_start, video_end)
-    lib = _lib.load()
     G, F, W = gt_box.shape[0], gt_off.shape[0] - 1, int(window)
     for t, dt in ((gt_box, torch.float32), (gt_track, torch.int64), (gt_off, torch.int64), (video_start, torch.int32),
                   (video_end, torch.int32)):
@@ -1659,15 +1437,12 @@ def motion_iou(gt_box, gt_track, gt_off, video_start, video_end, window, max_gt,
     dev = gt_box.device
     values = torch.zeros(G, dtype=torch.float64, device=dev)
     counts = torch.full((G,), -1, dtype=torch.int32, device=dev)
-    nb = lib.mega_motion_iou_workspace_bytes(G, W, int(max_gt))
+    nb = _lib.load().mega_motion_iou_workspace_bytes(G, W, int(max_gt))
     ws = _ws(max(nb, 1), dev)
     if return_workspace:
         ws.fill_(0xFF)
-    _tok = _pb("motion_iou")
-    rc = lib.mega_motion_iou(_ptr(gt_box), _ptr(gt_track), _ptr(gt_off), _ptr(video_start), _ptr(video_end), F, G, W,
-                             int(max_gt), _ptr(values), _ptr(counts), _ptr(ws), nb, _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_motion_iou")
+    _call("mega_motion_iou", gt_box, gt_track, gt_off, video_start, video_end, F, G, W, int(max_gt), values, counts, ws, nb,
+          prof=("motion_iou",))
     if return_workspace:
         return values, counts, (ws[:8 * G * W].view(torch.int32).reshape(G, 2 * W) if nb else None)
     return values, counts
@@ -1681,8 +1456,6 @@ def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, t
     (resized_hw = its (height, width)), scores [F,R] f32, labels [F,R] i64 or i32, counts [F] i32, palette [NC,3] u8,
     atlas: demo.LabelAtlas.to(device) (cells [G,gh,gw] u8, advances [G] i32, class_glyphs [NC,ML] i32, fmt_glyphs [13] i32).
     Returns frames.  No synchronisation; nothing is copied to the host."""
-    _gpu(frames, boxes, scores, labels, counts, palette, atlas.cells, atlas.advances, atlas.class_glyphs, atlas.fmt_glyphs)
-    lib = _lib.load()
     F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
     R = boxes.shape[1]
     assert frames.dtype == torch.uint8 and frames.shape == (F, H, W, 3) and frames.is_contiguous()
@@ -1701,14 +1474,9 @@ def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, t
     rh, rw = int(resized_hw[0]), int(resized_hw[1])
     # BoxList.resize: the ratio is a Python float (f64 division), the multiply an f32 tensor op with the ratio rounded to f32
     sx, sy = float(torch.tensor(W / rw, dtype=torch.float32)), float(torch.tensor(H / rh, dtype=torch.float32))
-    nb = lib.mega_overlay_detections_workspace_bytes(F, R)
+    nb = _lib.load().mega_overlay_detections_workspace_bytes(F, R)
     ws = _ws(max(nb, 1), frames.device)
-    _tok = _pb("overlay")
-    rc = lib.mega_overlay_detections(_ptr(frames), F, H, W, _ptr(boxes), _ptr(scores), _ptr(labels),
-                                     int(labels.dtype == torch.int64), _ptr(counts), R, sx, sy, float(thr), int(thickness),
-                                     _ptr(palette), NC, _ptr(atlas.class_glyphs), ML, _ptr(atlas.fmt_glyphs),
-                                     _ptr(atlas.cells), _ptr(atlas.advances), G, gh, gw, int(bool(select_only)), _ptr(ws), nb,
-                                     _stream())
-    _pe(_tok)
-    _lib.check(rc, "mega_overlay_detections")
+    _call("mega_overlay_detections", frames, F, H, W, boxes, scores, labels, int(labels.dtype == torch.int64), counts, R,
+          sx, sy, float(thr), int(thickness), palette, NC, atlas.class_glyphs, ML, atlas.fmt_glyphs, atlas.cells,
+          atlas.advances, G, gh, gw, int(bool(select_only)), ws, nb, prof=("overlay",))
     return frames

@@ -3,7 +3,8 @@
 
     python tools/kernel_code_diff.py OLD NEW [--units boxes.hip,fgfa.hip] [--jobs 4] [--keep DIR]
 
-OLD / NEW: a csrc directory, a git revision (its mega/pytorch_amd/csrc is extracted), or `worktree`.
+OLD / NEW: a csrc directory (three levels below the include/ it uses), a git revision (its mega/pytorch_amd/csrc and
+include/ are extracted), or `worktree`.
 
 Every unit of build.SOURCES is compiled for the device alone (--cuda-device-only --no-gpu-bundle-output) with exactly
 build.BASE_FLAGS plus the unit's own flags (the probed -mllvm flag included).  Per unit the report names
@@ -39,7 +40,10 @@ def resolve_tree(spec, tmp):
         return os.path.abspath(spec)
     dst = os.path.join(tmp, "rev_" + re.sub(r"\W", "_", spec))
     os.makedirs(dst)
-    tar = subprocess.run(["git", "-C", ROOT, "archive", spec, CSRC_REL], stdout=subprocess.PIPE, check=True).stdout
+    # csrc/common.h includes ../../../include/mega_hip.h: a revision's header travels with its sources
+    paths = [p for p in (CSRC_REL, "include")
+             if subprocess.run(["git", "-C", ROOT, "cat-file", "-e", "%s:%s" % (spec, p)]).returncode == 0]
+    tar = subprocess.run(["git", "-C", ROOT, "archive", spec] + paths, stdout=subprocess.PIPE, check=True).stdout
     subprocess.run(["tar", "-x", "-C", dst], input=tar, check=True)
     return os.path.join(dst, CSRC_REL)
 
