@@ -598,6 +598,29 @@ int mega_link_tracks(const float* box, const float* score, const int* pos, const
                      int T, int F, int C, long long N, float score_thresh, float link_iou, int max_gap, int max_open,
                      long long* root, int* cnt, double* sum, float* mx, void* ws, size_t ws_bytes, void* stream);
 
+/* Refining linked tracks: gap frames filled by interpolation, boxes smoothed along the track
+ * (mega/pytorch_amd/tracks.py defines it; the reference has no counterpart).  One 256-thread workgroup per tile of 256
+ * output slots, plus a halo of r slots on each side held in LDS; one launch, no atomics, no status word.  Inputs:
+ *   m_box [M][4] f32, m_score [M] f32 (>= 0), m_frame [M] i32 (dataset frame): the members (boxes with a track id) sorted
+ *   by (video, track id, frame); m_off [K + 1] i64: track k's members are m_off[k] .. m_off[k + 1] (at least one, frames
+ *   strictly ascending); o_off [K + 1] i64, o_off[0] = 0, o_off[K] = S: track k's output slots, with fill = 1 one per frame
+ *   from its first member's frame to its last member's, with fill = 0 one per member.
+ * A slot that is a member copies it; any other slot f between the members a, b that bracket it gets, per coordinate in
+ * f32 without contraction, a.c + (b.c - a.c) * (f32(f - fa) / f32(fb - fa)) and the score min(a.score, b.score) *
+ * fill_scale.  With r > 0 every slot's box is then the mean of the unsmoothed boxes of its own track's slots within r
+ * frames: f64 sum in ascending frame order starting from the first term, / count, rounded once to f32.
+ * Outputs, per slot: out_box [S][4] f32, out_score [S] f32, out_frame [S] i32, out_track [S] i32 (k), out_src [S] i32 (the
+ * member's index, -1 for a filled slot), out_filled [S] u8 (1 for a filled slot).
+ * Negative sizes, M or S above 2^31 - 1, a NULL pointer with a non-zero size, S > 0 with K = 0 or M = 0, fill outside
+ * 0..1, r outside 0..64, fill_scale outside (0, 1]: MEGA_ERR_ARG; a workspace below
+ * mega_refine_tracks_workspace_bytes(S, r) (0: a tile and its halos live in LDS): MEGA_ERR_WS; both before any launch.
+ * S = 0 launches nothing.  Does not synchronise. */
+size_t mega_refine_tracks_workspace_bytes(long long S, int r);
+int mega_refine_tracks(const float* m_box, const float* m_score, const int* m_frame, const long long* m_off,
+                       const long long* o_off, int K, long long M, long long S, int fill, int r, float fill_scale,
+                       float* out_box, float* out_score, int* out_frame, int* out_track, int* out_src,
+                       unsigned char* out_filled, void* ws, size_t ws_bytes, void* stream);
+
 /* Tubelet AP: matching linked tracks (tubelets) against ground-truth tracks by temporal IoU
  * (mega/pytorch_amd/track_eval.py defines it; the reference has no counterpart).  One workgroup per (video, label) task
  * with P tubelets and G GT tracks (G <= 4096).  Phase 1 counts, per pair, both = frames where both have a box and hits =

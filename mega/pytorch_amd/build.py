@@ -30,6 +30,7 @@ SOURCES = {
     "vid_eval.hip": ["-ffp-contract=off"],    # rescale + IoU must round like the reference's separate f32 torch ops
     "seq_nms.hip": ["-ffp-contract=off"],     # the f32 IoU in the order seq_nms.py defines
     "tracks.hip": ["-ffp-contract=off"],      # the same IoU, as tracks.py defines the linking
+    "track_refine.hip": ["-ffp-contract=off"],      # a + (b - a) * w as the separate f32 ops tracks.py defines for a filled box
     "bbox_aug.hip": ["-ffp-contract=off"],    # flip / resize of the merged boxes round like BoxList's separate f32 ops
     "soft_nms.hip": ["-ffp-contract=off"],    # IoU, view mapping and score decay round as soft_nms.py's separate f32 ops
     "overlay.hip": ["-ffp-contract=off"],     # box rescale is one f32 multiply, the score digits one f64 multiply

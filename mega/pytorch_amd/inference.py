@@ -323,7 +323,11 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     (tracks.format_table), and with rescore and anno_path result_tracks.txt the evaluation of the rescored list;
     predictions.pth, result.txt and the return value do not change.  With "tubelet_ap": True in the dict (and optionally
     "tubelet_score": "mean" | "max") and anno_path, the linked tracks are also scored against the annotations' <trackid>
-    tracks (track_eval.evaluate_tracks): result_tubelets.txt.
+    tracks (track_eval.evaluate_tracks): result_tubelets.txt.  The dict's "fill": bool, "smooth": int and "fill_scale":
+    float are tracks.refine's parameters: with fill true or smooth > 0 the linked (and rescored) list is refined -- gap
+    frames filled, boxes smoothed -- and predictions_tracks.pth (now with the field "filled"), result_tracks.txt (written
+    with anno_path also when only the refinement is on) and the tubelet AP are those of the refined list; tracks.txt stays
+    the linker's table.
     cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
     (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
     Seq-NMS, track linking, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY
@@ -342,6 +346,8 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if tubelet_ap:
             from . import track_eval
             track_eval.check_params(tubelet_score=tubelet_score)
+        fill, smooth, fill_scale = tr.check_refine_params(track_params.pop("fill", False), track_params.pop("smooth", 0),
+                                                          track_params.pop("fill_scale", 1.0))
         tr.check_params(**track_params)                          # (a bad value raises before the run, not after it)
     if isinstance(motion_iou, dict) or motion_iou == "derive":
         from . import motion_iou as mi
@@ -383,9 +389,15 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if output_folder:
             save_predictions(rescored, os.path.join(output_folder, "predictions_seq_nms.pth"))
     tracked = None
+    refined = False
     if tracks is not None and tracks is not False:
         tracked, table = tr.link(predictions if rescored is None else rescored,
                                  [(v["start"], v["seg_len"]) for v in index.videos], device=device, **track_params)
+        if fill or smooth > 0:                                   # after the linking and its rescoring
+            tracked, info = tr.refine(tracked, [(v["start"], v["seg_len"]) for v in index.videos], fill=fill,
+                                      smooth=smooth, fill_scale=fill_scale, device=device)
+            refined = True
+            logger.info("Refined %d tracks: %d boxes filled", info["tracks"], info["filled"])
         if output_folder:
             save_predictions(tracked, os.path.join(output_folder, "predictions_tracks.pth"))
             with open(os.path.join(output_folder, "tracks.txt"), "w") as f:
@@ -405,7 +417,7 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         if rescored is not None:
             vid_eval.evaluate_detections(rescored, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                          logger=logger, result_name="result_seq_nms.txt")
-        if tracked is not None and track_params.get("rescore") is not None:
+        if tracked is not None and (track_params.get("rescore") is not None or refined):
             vid_eval.evaluate_detections(tracked, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                          logger=logger, result_name="result_tracks.txt")
         if tracked is not None and tubelet_ap:

@@ -1366,6 +1366,33 @@ def link_tracks(box, score, pos, seg_off, tasks, F, C, score_thresh, link_iou, m
     return root, cnt, acc, mx
 
 
+# ------------------------------------------------------------------------------------------------ track refinement
+def refine_tracks(m_box, m_score, m_frame, m_off, o_off, slots, fill, smooth, fill_scale):
+    """Fill the gap frames of K tracks and smooth their boxes (include/mega_hip.h mega_refine_tracks;
+    mega/pytorch_amd/tracks.py defines it).  m_box [M,4] f32, m_score [M] f32, m_frame [M] i32: the members sorted by (video,
+    track id, frame); m_off / o_off [K+1] i64: each track's members and output slots; slots: S = o_off[K], which the
+    caller knows on the host.  -> per slot box [S,4] f32, score [S] f32, frame [S] i32, track [S] i32, src [S] i32 (the
+    member's index, -1: filled), filled [S] u8, on the device.  Does not synchronise."""
+    M, K = m_box.shape[0], m_off.shape[0] - 1
+    for t, dt in ((m_box, torch.float32), (m_score, torch.float32), (m_frame, torch.int32), (m_off, torch.int64),
+                  (o_off, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert m_box.shape == (M, 4) and m_score.shape == (M,) and m_frame.shape == (M,) and o_off.shape == (K + 1,)
+    dev = m_box.device
+    S = int(slots)
+    box = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    score = torch.empty(S, dtype=torch.float32, device=dev)
+    frame = torch.empty(S, dtype=torch.int32, device=dev)
+    track = torch.empty(S, dtype=torch.int32, device=dev)
+    src = torch.empty(S, dtype=torch.int32, device=dev)
+    filled = torch.empty(S, dtype=torch.uint8, device=dev)
+    # no workspace: the fused kernel keeps a tile and its halos in LDS (mega_refine_tracks_workspace_bytes is 0 at every
+    # size; a library that wanted one would answer MEGA_ERR_WS here)
+    _call("mega_refine_tracks", m_box, m_score, m_frame, m_off, o_off, K, M, S, int(bool(fill)), int(smooth),
+          float(fill_scale), box, score, frame, track, src, filled, None, 0, prof=("refine_tracks",))
+    return box, score, frame, track, src, filled
+
+
 # ------------------------------------------------------------------------------------------------ tubelet AP
 def tubelet_scores(score, off, use_max=False):
     """A tubelet's score as track_eval.py defines it (include/mega_hip.h mega_tubelet_scores).  score [M] f32: the members

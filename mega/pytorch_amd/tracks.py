@@ -49,6 +49,54 @@ to the video), box count and mean score (f64: the f64 sum / count).
 There is no CPU path: the association runs on a HIP device, one workgroup per (video, class) task (csrc/tracks.hip); the
 ids, the rescoring and the table are a few segment operations on the device over the kernel's per-box root and per-root
 count / sum / max, then one copy back.
+
+
+Refinement (refine): filling a track's gap frames by interpolation and smoothing its boxes along the track.  The reference
+has no counterpart either; this section defines it, and the kernel (csrc/track_refine.hip) and the test twin
+(tests/track_refine_twin.py) implement it.
+
+Input: predictions, a list[BoxList] in dataset order with "scores" (f32, >= 0, not NaN), "labels" (int >= 0) and
+"track_ids" (int64, -1 = in no track) -- what link returns or predictions_tracks.pth holds -- and optionally "filled"
+(uint8), so that refining twice is defined; videos as for link.
+
+Parameters:
+    fill       = True    bool
+    smooth     = 0       int radius r, 0 <= r <= 64 (a bool is not accepted)
+    fill_scale = 1.0     rounded to f32; must lie in (0, 1]
+
+Track: all boxes of one video with the same track id >= 0.  Boxes with id -1 are never touched; where fill is off, neither
+is a box that the smoothing does not reach.
+
+Host checks, each a ValueError with the prefix "tracks:" before any device work: a missing "track_ids" field or an id
+< -1; two boxes of one track in the same frame; a track with more than one label; a non-finite box; a NaN or negative
+score, a negative label (flat.pack's checks); frames of one video with different size or mode; with fill a field other
+than "scores", "labels", "track_ids", "filled" (a filled box has no value for it); an output of more than 2^31 - 1
+boxes; the parameter ranges above.
+
+Filling (fill = True).  For consecutive members a, b of a track at frames fa < fb with fb - fa > 1, every frame f with
+fa < f < fb gets one new box.  Per coordinate, in f32, in this order, with no FMA contraction:
+    w = f32(f - fa) / f32(fb - fa)
+    c = a.c + (b.c - a.c) * w
+Its score is min(a.score, b.score) * fill_scale, one f32 multiply (a -0.0 score counts as +0.0); its label and track id are
+the track's; its "filled" is 1.  A filled box lies in the convex hull of two boxes of the same image size, so no clipping
+is defined.
+
+Smoothing (r > 0) runs after filling and reads only unsmoothed values.  It applies to every box s of a track, filled boxes
+included: take the track's boxes s' with |frame(s') - frame(s)| <= r (the window is cut at the track's first and last
+frame; with fill = False it holds only the boxes that exist); per coordinate, their f32 values are added in f64 in
+ascending frame order, starting from the first of them, the sum is divided by their count in f64 and rounded once to f32.
+Scores, labels and ids do not change.  A track of one box is unchanged, bit for bit.
+
+Output: a new list[BoxList] of the same length, sizes and modes.  In every frame the input boxes come first, in their input
+order, with all fields bit for bit -- only the bbox of smoothed members changes -- then the frame's filled boxes by
+ascending track id.  The field "filled" (uint8) is always present: the input's own value where it carried one, else 0 for
+input boxes.  refine also returns {"tracks": K, "filled": n_new}.  Refining a refined list with smooth = 0 adds nothing and
+changes no bit.  DETECTIONS_PER_IMG is not re-applied.
+
+There is no CPU path here either.  The host checks order the members by (video, track id, frame) and so know every track's
+members m_off[K + 1] and output slots o_off[K + 1] (last - first + 1 frames with fill, the member count without); the
+kernel fills and smooths one tile of 256 slots per workgroup; the results go back to their frames with a few torch
+operations on the device and one copy.
 """
 import numpy as np
 import torch
@@ -186,6 +234,155 @@ def link(predictions, videos, score_thresh=0.05, link_iou=0.5, max_gap=1, min_le
     r = run(predictions, videos, score_thresh, link_iou, max_gap, min_len, rescore, device)
     return _attach(predictions, r["track_ids"], r["scores"] if rescore is not None else None,
                    r["packed"]["counts"]), r["table"]
+
+
+# ------------------------------------------------------------------------------------------------ refinement
+REFINE_FIELDS = ("scores", "labels", "track_ids", "filled")
+MAX_SMOOTH = 64
+
+
+def check_refine_params(fill=True, smooth=0, fill_scale=1.0):
+    """-> (fill, smooth, fill_scale rounded to f32 as a Python float); ValueError for a bad value."""
+    if not isinstance(fill, (bool, np.bool_)):
+        raise ValueError("tracks: fill must be a bool, got %r" % (fill,))
+    if isinstance(smooth, (bool, np.bool_)) or not isinstance(smooth, (int, np.integer)) or not 0 <= smooth <= MAX_SMOOTH:
+        raise ValueError("tracks: smooth must be an int in [0, %d], got %r" % (MAX_SMOOTH, smooth))
+    try:
+        scale = float(np.float32(fill_scale))
+    except (TypeError, ValueError):
+        raise ValueError("tracks: fill_scale must be a number in (0, 1], got %r" % (fill_scale,))
+    if isinstance(fill_scale, (bool, np.bool_)) or not 0.0 < scale <= 1.0:
+        raise ValueError("tracks: fill_scale must lie in (0, 1] (in f32), got %r" % (fill_scale,))
+    return bool(fill), int(smooth), scale
+
+
+def _refine_pack(predictions, videos, fill):
+    """The host checks of refine and what they compute on the way: flat.pack's dict plus "track_ids" [N] i64, "order" [M] i64
+    (the members' flat positions by (video, track id, frame)), "frame" [M] (their frames, in that order), "m_off" / "o_off"
+    [K+1] i64, "track_id" / "track_label" [K] i64, "K", "M", "S" (slots) and "n_new" (S - M)."""
+    for f, p in enumerate(predictions):
+        if not p.has_field("track_ids"):
+            raise ValueError("tracks: refine needs the field \"track_ids\" (tracks.link's output); frame %d has none" % f)
+        extra = sorted(set(p.fields()) - set(REFINE_FIELDS))
+        if fill and extra:
+            raise ValueError("tracks: fill=True cannot give a filled box a value for the field(s) %s (frame %d)"
+                             % (", ".join(extra), f))
+        if p.get_field("track_ids").numel() != len(p):
+            raise ValueError("tracks: frame %d has %d boxes and %d track ids" % (f, len(p), p.get_field("track_ids").numel()))
+    pk = flat.pack(predictions, videos, "tracks")
+    F, N, vs, vl = pk["F"], pk["N"], pk["video_start"], pk["video_len"]
+    for s0, n in zip(vs.tolist(), vl.tolist()):
+        for p in predictions[s0 + 1:s0 + n]:
+            if tuple(p.size) != tuple(predictions[s0].size) or p.mode != predictions[s0].mode:
+                raise ValueError("tracks: the frames of the video at %d differ in size or mode" % s0)
+    ids = np.zeros(0, np.int64)
+    if N:
+        ids = torch.cat([p.get_field("track_ids").reshape(-1).to("cpu", torch.int64) for p in predictions]).numpy()
+        if ids.min() < -1:
+            raise ValueError("tracks: a track id is below -1")
+    fid = np.repeat(np.arange(F, dtype=np.int64), pk["counts"])
+    vid = np.repeat(np.arange(len(vl), dtype=np.int64), vl)[fid]
+    mem = np.nonzero(ids >= 0)[0]
+    # by (video, track id); the flat order is by frame, and the sort is stable: frames ascend within a track
+    order = mem[np.lexsort((ids[mem], vid[mem]))]
+    sv, si, sf, sl = vid[order], ids[order], fid[order], pk["labels"][order]
+    same = (sv[1:] == sv[:-1]) & (si[1:] == si[:-1])
+    if (same & (sf[1:] == sf[:-1])).any():
+        raise ValueError("tracks: two boxes of one track in the same frame")
+    if (same & (sl[1:] != sl[:-1])).any():
+        raise ValueError("tracks: a track with more than one label")
+    M = int(order.shape[0])
+    starts = np.nonzero(np.concatenate([[True], ~same]))[0] if M else np.zeros(0, np.int64)      # each track's first member
+    m_off = np.concatenate([starts, [M]]).astype(np.int64)
+    K = int(starts.shape[0])
+    first, last = sf[m_off[:-1]], sf[m_off[1:] - 1]
+    o_off = np.zeros(K + 1, np.int64)
+    o_off[1:] = np.cumsum(last - first + 1 if fill else np.diff(m_off))
+    S = int(o_off[-1])
+    if N + S - M > 0x7fffffff:
+        raise ValueError("tracks: refine would return %d boxes: too many" % (N + S - M))
+    pk.update(track_ids=ids, order=order, frame=sf, m_off=m_off, o_off=o_off, track_id=si[m_off[:-1]],
+              track_label=sl[m_off[:-1]], K=K, M=M, S=S, n_new=S - M)
+    return pk
+
+
+def refine_run(predictions, videos, fill=True, smooth=0, fill_scale=1.0, device="cuda"):
+    """The refinement as flat host arrays: {"boxes": [N,4] f32, the input boxes in frame-by-frame order (smoothed where
+    they are in a track); "fill_box" [n_new,4] f32, "fill_score" [n_new] f32, "fill_frame", "fill_label", "fill_id" [n_new]
+    i64: the filled boxes by frame, then track id; "tracks": K; "packed": the checked input (_refine_pack)}."""
+    fill, r, scale = check_refine_params(fill, smooth, fill_scale)
+    pk = _refine_pack(predictions, videos, fill)
+    dev = torch.device(device)
+    flat.require_hip(dev, "tracks", device)
+    N, K, M, S, n_new = pk["N"], pk["K"], pk["M"], pk["S"], pk["n_new"]
+    out = {"packed": pk, "tracks": K, "boxes": pk["boxes"].copy(), "fill_box": np.zeros((0, 4), np.float32),
+           "fill_score": np.zeros(0, np.float32), "fill_frame": np.zeros(0, np.int64), "fill_label": np.zeros(0, np.int64),
+           "fill_id": np.zeros(0, np.int64)}
+    if K == 0:
+        return out
+    from . import ops
+    with torch.cuda.device(dev):
+        t = flat.upload([("box", pk["boxes"]), ("score", pk["scores"]), ("order", pk["order"]),
+                         ("frame", pk["frame"].astype(np.int32)), ("m_off", pk["m_off"]), ("o_off", pk["o_off"])], dev)
+        box, score, frame, track, src, _ = ops.refine_tracks(t["box"][t["order"]].contiguous(),
+                                                             t["score"][t["order"]].contiguous(), t["frame"], t["m_off"],
+                                                             t["o_off"], S, fill, r, scale)
+        # members return to their source positions
+        new_box = t["box"].clone()
+        kept = torch.nonzero(src >= 0).reshape(-1)
+        new_box[t["order"][src[kept].to(torch.int64)]] = box[kept]
+        # the filled slots are in (video, track id, frame) order; a stable sort by frame groups them by frame with the
+        # track ids ascending within it (a frame lies in one video)
+        new = torch.nonzero(src < 0).reshape(-1)
+        new = new[torch.sort(frame[new], stable=True).indices]
+        # [boxes f32 [N,4] | fill_box f32 [n_new,4] | fill_score f32 | fill_frame i32 | fill track i32]: one copy back
+        res = torch.cat([x.contiguous().view(torch.uint8).reshape(-1)
+                         for x in (new_box, box[new], score[new], frame[new], track[new])])
+        host = res.cpu().numpy()
+    if host.shape[0] != 16 * N + 28 * n_new:
+        raise RuntimeError("tracks: the refinement kernel filled %d bytes of boxes, expected %d"
+                           % (host.shape[0] - 16 * N, 28 * n_new))
+    o = 16 * N
+    out["boxes"] = host[:o].view(np.float32).reshape(N, 4).copy()
+    out["fill_box"] = host[o:o + 16 * n_new].view(np.float32).reshape(n_new, 4).copy()
+    o += 16 * n_new
+    out["fill_score"] = host[o:o + 4 * n_new].view(np.float32).copy()
+    out["fill_frame"] = host[o + 4 * n_new:o + 8 * n_new].view(np.int32).astype(np.int64)
+    k = host[o + 8 * n_new:].view(np.int32)
+    out["fill_label"], out["fill_id"] = pk["track_label"][k], pk["track_id"][k]
+    return out
+
+
+def refine(predictions, videos, fill=True, smooth=0, fill_scale=1.0, device="cuda"):
+    """Fill the gap frames of the tracks in `predictions` (list[BoxList] with "track_ids") and smooth their boxes ->
+    (a new list[BoxList] with the field "filled", {"tracks": K, "filled": n_new}); see the module docstring."""
+    r = refine_run(predictions, videos, fill, smooth, fill_scale, device)
+    pk = r["packed"]
+    off = pk["off"]
+    foff = np.zeros(pk["F"] + 1, np.int64)
+    foff[1:] = np.cumsum(np.bincount(r["fill_frame"], minlength=pk["F"]))
+    n_new = int(foff[-1])
+    boxes = torch.from_numpy(r["boxes"])
+    added = {"bbox": torch.from_numpy(r["fill_box"]), "scores": torch.from_numpy(r["fill_score"]),
+             "labels": torch.from_numpy(r["fill_label"]), "track_ids": torch.from_numpy(r["fill_id"]),
+             "filled": torch.ones(n_new, dtype=torch.uint8)}
+    out = []
+    for f, p in enumerate(predictions):
+        a, b = int(foff[f]), int(foff[f + 1])
+        d = p.bbox.device
+        bbox = boxes[int(off[f]):int(off[f + 1])]
+        if b > a:
+            bbox = torch.cat([bbox, added["bbox"][a:b]])
+        bl = BoxList(bbox.to(d), p.size, p.mode)
+        for k in p.fields():
+            v = p.get_field(k)
+            if b > a:              # (fill is on: the frame carries none but the four fields a filled box has a value for)
+                v = torch.cat([v.reshape(-1), added[k][a:b].to(device=v.device, dtype=v.dtype)])
+            bl.add_field(k, v)
+        if not p.has_field("filled"):
+            bl.add_field("filled", torch.cat([torch.zeros(len(p), dtype=torch.uint8), added["filled"][a:b]]).to(d))
+        out.append(bl)
+    return out, {"tracks": r["tracks"], "filled": n_new}
 
 
 def format_table(table, classes=None):

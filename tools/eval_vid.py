@@ -20,7 +20,9 @@ that evaluation too.
 --tracks (with --tracks-score-thresh / --tracks-link-iou / --tracks-max-gap / --tracks-min-len / --tracks-rescore) links
 the detections (what Seq-NMS kept, with --seq-nms) into tracks (mega.pytorch_amd.tracks): predictions_tracks.pth with the
 field "track_ids", tracks.txt with one line per track, and with --tracks-rescore avg|max result_tracks.txt, the evaluation
-of the rescored detections.
+of the rescored detections.  --tracks-fill / --tracks-smooth R / --tracks-fill-scale X (only with --tracks) then refine the
+tracks (tracks.refine): gap frames filled by interpolation, boxes averaged over +-R frames; predictions_tracks.pth gets the
+field "filled", and result_tracks.txt and --tubelet-ap judge the refined list.
 
 --tubelet-ap (with --tubelet-score mean|max) scores tracks against the annotations' <trackid> tracks
 (mega.pytorch_amd.track_eval): the tubelet AP at temporal IoU 0.25 / 0.5 / 0.75 -> result_tubelets.txt.  With --tracks it
@@ -68,6 +70,12 @@ def main(argv=None):
     ap.add_argument("--tracks-min-len", type=int, default=1, help="tracks: shorter tracks get no id")
     ap.add_argument("--tracks-rescore", choices=("none", "avg", "max"), default="none",
                     help="tracks: replace a linked box's score by its track's mean / max -> result_tracks.txt")
+    ap.add_argument("--tracks-fill", action="store_true", help="tracks: fill each track's gap frames by interpolation "
+                    "(predictions_tracks.pth gets the field \"filled\"; result_tracks.txt judges the refined list)")
+    ap.add_argument("--tracks-smooth", type=int, default=None, metavar="R", help="tracks: replace every track box by the "
+                    "mean of its track's boxes within R frames (0 .. 64)")
+    ap.add_argument("--tracks-fill-scale", type=float, default=None, metavar="X", help="--tracks-fill: a filled box scores "
+                    "X times the smaller of its two neighbours' scores (0 < X <= 1, default 1)")
     ap.add_argument("--tubelet-ap", action="store_true", help="tubelet AP of the tracks against the GT tracks "
                     "(result_tubelets.txt)")
     ap.add_argument("--tubelet-score", choices=("mean", "max"), default="mean", help="--tubelet-ap: a tubelet's score")
@@ -81,6 +89,15 @@ def main(argv=None):
         ap.error("--box-only evaluates proposals: --tracks applies to detections")
     if a.box_only and a.tubelet_ap:
         ap.error("--box-only evaluates proposals: --tubelet-ap applies to tracks")
+    if not a.tracks and (a.tracks_fill or a.tracks_smooth is not None or a.tracks_fill_scale is not None):
+        ap.error("--tracks-fill / --tracks-smooth / --tracks-fill-scale refine linked tracks: they need --tracks")
+    if a.tracks:
+        from mega.pytorch_amd import tracks
+        try:
+            refine = tracks.check_refine_params(a.tracks_fill, 0 if a.tracks_smooth is None else a.tracks_smooth,
+                                                1.0 if a.tracks_fill_scale is None else a.tracks_fill_scale)
+        except ValueError as e:
+            ap.error(str(e))
     derive = a.motion_iou == "derive"
     if not derive and (a.motion_window is not None or a.save_motion_iou):
         ap.error("--motion-window / --save-motion-iou apply to --motion-iou derive")
@@ -130,15 +147,23 @@ def main(argv=None):
         rescore = None if a.tracks_rescore == "none" else a.tracks_rescore
         tracked, table = tracks.link(preds, videos, score_thresh=a.tracks_score_thresh, link_iou=a.tracks_link_iou,
                                      max_gap=a.tracks_max_gap, min_len=a.tracks_min_len, rescore=rescore, device=a.device)
+        refined = refine[0] or refine[1] > 0
+        if refined:
+            tracked, info = tracks.refine(tracked, videos, fill=refine[0], smooth=refine[1], fill_scale=refine[2],
+                                          device=a.device)
         os.makedirs(out, exist_ok=True)
         inference.save_predictions(tracked, os.path.join(out, "predictions_tracks.pth"))
         with open(os.path.join(out, "tracks.txt"), "w") as f:
             f.write(tracks.format_table(table))
         sys.stdout.write("Tracks: %d\n" % len(table))
-        if rescore is not None:
+        if refined:
+            sys.stdout.write("Filled boxes: %d\n" % info["filled"])
+        if rescore is not None or refined:
             res = vid_eval.evaluate_detections(tracked, gt, motion_iou=motion, output_folder=out, device=a.device,
                                                result_name="result_tracks.txt")
-            sys.stdout.write("Tracks, rescored:\n" + vid_eval.format_result(res))
+            sys.stdout.write("Tracks, %s:\n" % " and ".join(w for w, on in (("rescored", rescore is not None),
+                                                                             ("refined", refined)) if on)
+                             + vid_eval.format_result(res))
         preds = tracked
     if a.tubelet_ap:
         from mega.pytorch_amd import track_eval
