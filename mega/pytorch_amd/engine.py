@@ -170,17 +170,22 @@ class ClipEngine(object):
         self._res5_stream = None
         self.reuse_records = reuse_records
         self.frames_per_launch = steps_per_batch + 2      # reuse_records: fixed frame-stage launch size
-        # experimental, opt-in: steady-state aggregation steps on fixed-address pools, replayed from one hipGraph
-        self._static = StaticAggregation(model, use_graph=graphs) if static_aggregation else None
-        self.use_static = True            # False: step eagerly even when a StaticAggregation exists (instrumented passes)
+        fe = getattr(getattr(getattr(model, "roi_heads", None), "box", None), "feature_extractor", None)
+        # static_aggregation (opt-in, diagnostic): every key frame after the cold start is its own aggregation batch of ONE
+        # step, in steady state on fixed-address state and replayed from one hipGraph per key frame (RDN has no batched
+        # path: per-frame steps)
+        self._static = None
+        if static_aggregation and hasattr(fe, "aggregate_batch"):
+            self._static = StaticBatchAggregation(model, 1, use_graph=graphs, keep_keys=keep_logits)
+        self.use_static = True            # False: aggregate eagerly on the model's deques (instrumented passes)
         # graph_aggregation (round 4, default with graphs + batched aggregation, single process): in steady state -- all
         # pools full, every frame with all its proposals -- the BATCHED aggregation of a step-batch (prepare_batch +
-        # step_batch: ~100 launches, ~6 ms of Python) runs on fixed-address state and is replayed from one hipGraph
+        # step_batch: ~100 launches, ~6 ms of Python) runs on fixed-address state and is replayed from one hipGraph.
+        # Created at the first full step-batch, and only on an engine without _static (see run(): batched and use_static)
         self._sbatch = None
         self.graph_aggregation = bool(graph_aggregation and graphs)
         # batch_aggregation: the aggregation of all key frames of a step-batch runs stage by stage over the whole batch
         # (model.step_batch: projections / stage FCs as one GEMM each); off = one model.step() per key frame
-        fe = getattr(getattr(getattr(model, "roi_heads", None), "box", None), "feature_extractor", None)
         self.batch_aggregation = batch_aggregation and hasattr(fe, "aggregate_batch")      # (RDN: per-frame steps)
         # multi-GPU wire format: with the batched aggregation a key frame is aggregated by ONE rank, the one
         # that ran its frame stage, and only the base_num rows every window reads travel (shard_plan / records_async)
@@ -226,7 +231,7 @@ class ClipEngine(object):
         m = self.model
         fe = m.roi_heads.box.feature_extractor
         if self._static is not None and self._static.active:
-            full = True                   # StaticAggregation.ready() only admits full pools
+            full = True                   # StaticBatchAggregation.ready() only admits full pools
         else:
             full = hasattr(m, "records") and len(m.records) == m.all_frame_interval
             if full and getattr(m, "global_enable", False):
@@ -728,8 +733,11 @@ class ClipEngine(object):
                     raise RuntimeError("ClipEngine: frames were dealt owner-aligned but the batched aggregation is off "
                                        "(cache_memory_kv / batch_aggregation changed after construction); build the engine "
                                        "after setting them")
-                if batched and self._static is not None:
-                    self._static.leave()          # the pools go back into the model's deques
+                fe = m.roi_heads.box.feature_extractor
+                # static mode: a key frame is its own batch of one step (whole records on every rank: never a shard)
+                single = not batched and self._static is not None and fe.cache_memory_kv
+                if not single and self._static is not None:
+                    self._static.leave()          # the state goes back into the model's deques
                 if not batched and self._sbatch is not None:
                     self._sbatch.leave()
                 prepared = []                     # (key frame index, (new local record, new global records)) of
@@ -739,35 +747,40 @@ class ClipEngine(object):
                     if not prepared:
                         return
                     shard = None
-                    if (self.world > 1 or self.force_sharded) and pp.candidates:
+                    sharded = batched and (self.world > 1 or self.force_sharded)
+                    if sharded and pp.candidates:
                         raise RuntimeError("ClipEngine: sharded key frames (KeyFrameShard) do not carry the candidates of "
                                            "TEST.BBOX_AUG / TEST.SOFT_NMS / TEST.BBOX_VOTE; run these with one rank per "
                                            "video (inference())")
-                    if self.world > 1 or self.force_sharded:
+                    if sharded:
                         # (legacy dealing: batch position t -> rank t mod world, whole records are everywhere)
                         shard = KeyFrameShard(self.dist, self.group_agg, self.rank, self.world,
                                               base=prepared[0][0] if self.owner_aligned else 0, wire=self.wire,
                                               order=self.wire_order)
                         self.wire_order.append("aggregate")
                     steps = [st for _, st in prepared]
-                    sb = self._sbatch
-                    if (self.graph_aggregation and self.use_static and shard is None and clip.is_cuda and prepared[0][0] > 0
-                            and len(steps) == self.steps_per_batch):
-                        if sb is None:
-                            sb = self._sbatch = StaticBatchAggregation(m, len(steps))
-                        if sb.ready(steps):
-                            c0 = sb.captures
-                            outs, frames = sb.step(steps, (W, H))
+                    # the owner of the fixed-address state this batch may run on: _static (a batch of one) or _sbatch
+                    sb = None
+                    if self.use_static and shard is None and prepared[0][0] > 0:
+                        if single:
+                            sb = self._static
+                        elif self.graph_aggregation and clip.is_cuda and len(steps) == self.steps_per_batch:
+                            if self._sbatch is None:
+                                assert self._static is None
+                                self._sbatch = StaticBatchAggregation(m, len(steps), keep_keys=self.keep_logits)
+                            sb = self._sbatch
+                    if sb is not None and sb.ready(steps):
+                        c0 = sb.captures
+                        outs, frames = sb.step(steps, (W, H))
+                        if single:
+                            self.static_steps += 1
+                        else:
                             self.graph_stats["agg_captured"] = self.graph_stats.get("agg_captured", 0) + sb.captures - c0
                             self.graph_stats["agg_replayed"] = sb.replays
-                        else:
-                            sb.leave()
-                            sb = None
                     else:
-                        if sb is not None:
-                            sb.leave()
-                        sb = None
-                    if sb is None:
+                        for owner in (self._static, self._sbatch):
+                            if owner is not None:
+                                owner.leave()
                         frames = m.prepare_batch(steps)
                         outs = m.step_batch(frames, (W, H), shard)
                     for (i2, _), pd in zip(prepared, outs):
@@ -790,6 +803,7 @@ class ClipEngine(object):
                         o += len(js)
                     loc = [x for x, j in zip(r, js) if j[2] == "l"]
                     glob = [x for x, j in zip(r, js) if j[2] == "g"]
+                    new_local = loc[0]
                     if i == 0:
                         if self._static is not None:
                             self._static.reset()
@@ -800,28 +814,19 @@ class ClipEngine(object):
                             m.records.append(loc[0])
                         for x in loc[1:]:
                             m.records.append(x)
-                        if batched:
-                            prepared.append((i, (None, glob)))
-                            continue
-                        pending.append((i, m.step(None, glob, (W, H), defer=True)))
+                        new_local = None
+                    if batched:
+                        prepared.append((i, (new_local, glob)))
+                    elif single and i > 0:
+                        prepared.append((i, (new_local, glob)))
+                        flush()
+                    else:                     # the cold start of the per-frame lanes; no batched path (RDN, cache_memory_kv off)
+                        pending.append((i, m.step(new_local, glob, (W, H), defer=True)))
                         if self.keep_logits:
+                            key = m.records[m.key_frame_location]
                             self.logits_log.append(m.last_logits.float().clone())
-                            self.key_boxes_log.append(m.records[m.key_frame_location]["boxes"].clone())
-                    elif batched:
-                        prepared.append((i, (loc[0], glob)))
-                    elif self._static is not None and self.use_static and self._static.ready(loc[0], glob):
-                        pending.append((i, self._static.step(loc[0], glob, (W, H))))
-                        self.static_steps += 1
-                        if self.keep_logits:
-                            self.logits_log.append(self._static.last_logits.float().clone())
-                            self.key_boxes_log.append(self._static.hist_boxes[m.key_frame_location].clone())
-                    else:
-                        if self._static is not None:
-                            self._static.leave()
-                        pending.append((i, m.step(loc[0], glob, (W, H), defer=True)))
-                        if self.keep_logits:
-                            self.logits_log.append(m.last_logits.float().clone())
-                            self.key_boxes_log.append(m.records[m.key_frame_location]["boxes"].clone())
+                            self.key_boxes_log.append(key["boxes"].clone())
+                            self.key_index_log.append(key["index"].clone() if "index" in key else None)
                 flush()
                 if use_streams:   # detection counts of the whole batch -> pinned host memory, async + event
                     dc = torch.cat([pd[3] for _, pd in pending])
@@ -884,166 +889,6 @@ class ClipEngine(object):
         return out
 
 
-class StaticAggregation(object):
-    """The per-key-frame aggregation step on FIXED-ADDRESS state, so that in steady state the whole step
-    (window / pool updates, 7 relation-attention calls, stage FCs, predictor, post-processing: ~80 launches) can be
-    captured once as a hipGraph and replayed with one host call per key frame.
-
-    Steady state = every record in the 25-frame window has all its proposals (key_num rows), the memory pools hold
-    25 entries per stage and the global pool is full: then every tensor of the step has a fixed shape.  The pools live
-    in tensors that are updated by SHIFT-APPEND (`pool = cat(pool[n:], new)` copied back in place), which keeps the
-    reference's oldest-first key order -- the attention sums run in exactly the order of the eager path, so the
-    results are bit-identical to it (tests/test_host_logic.py::test_static_aggregation_equals_eager on the CPU twins).
-
-    Opt-in (ClipEngine(static_aggregation=True)); the eager path remains the default.  Leaving steady state (a frame
-    with fewer proposals) writes the pools back into the model's deques and continues eagerly.
-    """
-
-    def __init__(self, model, use_graph=True):
-        self.m = model
-        self.fe = model.roi_heads.box.feature_extractor
-        self.use_graph = use_graph
-        self.active = False
-        self.graph = None
-        self.replays = 0
-
-    # ---- conditions
-    def ready(self, new_local, new_globals):
-        m, fe = self.m, self.fe
-        if not (m.memory_enable and m.global_enable and fe.cache_memory_kv and len(new_globals) == 1):
-            return False
-        if new_local is None or new_local["boxes"].shape[0] != m.key_num or new_globals[0]["boxes"].shape[0] < m.base_num:
-            return False
-        if self.active:
-            return True
-        if len(m.records) != m.all_frame_interval or any(r["boxes"].shape[0] != m.key_num for r in m.records):
-            return False
-        if len(fe.global_queue_list[0]["feats"]) != fe.global_size:
-            return False
-        if any(g.shape[0] != m.base_num for g in fe.global_queue_list[0]["feats"]):
-            return False
-        for i in range(fe.stage):
-            q = fe.mem_queue_list[i]
-            n = m.base_num if i == 0 else m.advanced_num
-            if len(q["k"]) != fe.all_frame_interval or len(q["rois"]) != fe.all_frame_interval:
-                return False
-            if any(t.shape[0] != n for t in q["rois"]):
-                return False
-        return True
-
-    # ---- eager state -> static tensors
-    def enter(self):
-        m, fe = self.m, self.fe
-        recs = list(m.records)
-        self.hist_boxes = torch.stack([r["boxes"] for r in recs]).contiguous()        # [25,300,4] oldest first
-        self.hist_scores = torch.stack([r["scores"] for r in recs]).contiguous()
-        self.hist_feats = torch.stack([r["feats"] for r in recs]).contiguous()
-        self.glob = torch.cat(list(fe.global_queue_list[0]["feats"]), dim=0).contiguous()
-        self.mem_rois = [torch.cat(list(fe.mem_queue_list[i]["rois"]), 0).contiguous() for i in range(fe.stage)]
-        self.mem_k = [torch.cat(list(fe.mem_queue_list[i]["k"]), 0).contiguous() for i in range(fe.stage)]
-        self.mem_vt = [torch.cat(list(fe.mem_queue_list[i]["vt"]), 1).contiguous() for i in range(fe.stage)]
-        dev = self.hist_feats.device
-        self.in_boxes = torch.zeros_like(self.hist_boxes[0])
-        self.in_scores = torch.zeros_like(self.hist_scores[0])
-        self.in_feats = torch.zeros_like(self.hist_feats[0])
-        self.in_glob = torch.zeros((m.base_num, self.glob.shape[1]), dtype=self.glob.dtype, device=dev)
-        n25, bn, an = m.all_frame_interval, m.base_num, m.advanced_num
-        self.dis_index = torch.cat([torch.arange(f * bn, f * bn + an) for f in range(n25)]).to(dev)
-        fe.static_pools = self
-        fe.global_cache[-1]["feats"] = self.glob
-        self.active = True
-        self.graph = None
-
-    # ---- static tensors -> eager state (leaving steady state / end of video)
-    def leave(self):
-        if not self.active:
-            return
-        m, fe = self.m, self.fe
-        n25 = m.all_frame_interval
-        m.records = deque(({"boxes": self.hist_boxes[f].clone(), "scores": self.hist_scores[f].clone(),
-                            "feats": self.hist_feats[f].clone()} for f in range(n25)), maxlen=n25)
-        gq = fe.global_queue_list[0]["feats"]
-        gq.clear()
-        for g in torch.split(self.glob.clone(), m.base_num, dim=0):
-            gq.append(g)
-        fe.global_cache[0]["feats"] = torch.cat(list(gq), dim=0)
-        for i in range(fe.stage):
-            n = m.base_num if i == 0 else m.advanced_num
-            q = fe.mem_queue_list[i]
-            for key in ("rois", "k", "vt"):
-                q[key].clear()
-            for f in range(fe.all_frame_interval):
-                q["rois"].append(self.mem_rois[i][f * n:(f + 1) * n].clone())
-                q["k"].append(self.mem_k[i][f * n:(f + 1) * n].clone())
-                q["vt"].append(self.mem_vt[i][:, f * n:(f + 1) * n].clone())
-            fe.mem[i] = {"rois": self.mem_rois[i].clone(), "k": self.mem_k[i].clone(), "vt": self.mem_vt[i].clone()}
-        fe.static_pools = None
-        self.active = False
-        self.graph = None
-
-    # ---- pool access used by MEGAFeatureExtractor.aggregate
-    def read_memory(self, i):
-        return {"rois": self.mem_rois[i], "k": self.mem_k[i], "vt": self.mem_vt[i]}
-
-    @staticmethod
-    def _shift_append(pool, new, dim=0):
-        n = new.shape[dim]
-        pool.copy_(torch.cat([pool.narrow(dim, n, pool.shape[dim] - n), new], dim=dim))
-
-    def push_memory(self, i, rois, k, vt):
-        self._shift_append(self.mem_rois[i], rois)
-        self._shift_append(self.mem_k[i], k)
-        self._shift_append(self.mem_vt[i], vt, dim=1)
-
-    # ---- one key frame on the static state (this body is what the graph captures)
-    def _body(self, im_size):
-        m, fe = self.m, self.fe
-        bn, an = m.base_num, m.advanced_num
-        self._shift_append(self.hist_boxes, self.in_boxes[None])
-        self._shift_append(self.hist_scores, self.in_scores[None])
-        self._shift_append(self.hist_feats, self.in_feats[None])
-        self._shift_append(self.glob, self.in_glob)
-        rois = self.hist_boxes[:, :bn].reshape(-1, 4)
-        x_ref = self.hist_feats[:, :bn].reshape(-1, self.hist_feats.shape[2])
-        rois_dis = self.hist_boxes[:, :an].reshape(-1, 4)
-        kl = m.key_frame_location
-        x = fe.aggregate(self.hist_feats[kl], self.hist_boxes[kl], rois, rois_dis, x_ref, self.dis_index)
-        logits, deltas = m.roi_heads.box.predictor(x)
-        self.last_logits = logits         # (a graph output buffer once captured: read it right after the replay)
-        kb = BoxListLike(self.hist_boxes[kl], im_size)
-        return m.roi_heads.box.post_processor.run((logits, deltas), kb)
-
-    @torch.no_grad()
-    def step(self, new_local, new_globals, im_size):
-        """new_local: record with key_num rows; new_globals: [record].  Returns padded outputs (fresh tensors)."""
-        if not self.active:
-            self.enter()
-        self.in_boxes.copy_(new_local["boxes"])
-        self.in_scores.copy_(new_local["scores"])
-        self.in_feats.copy_(new_local["feats"])
-        self.in_glob.copy_(new_globals[0]["feats"][:self.m.base_num])
-        if not (self.use_graph and self.in_feats.is_cuda):
-            return self._body(im_size)
-        if self.graph is None:                      # first steady-state step: eager on the static state (warm-up)
-            self.graph = "armed"
-            return self._body(im_size)
-        if self.graph == "armed":                   # second: capture (records the launches, executes nothing) ...
-            torch.cuda.current_stream().synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):     # (see ClipEngine._frame_stage)
-                self._out = self._body(im_size)
-            self.graph = g
-        self.graph.replay()                         # ... and every step from then on is one replay
-        self.replays += 1
-        return tuple(t.clone() for t in self._out)
-
-    def reset(self):
-        """New video: the model re-creates its deques; drop the static state without writing it back."""
-        self.fe.static_pools = None
-        self.active = False
-        self.graph = None
-
-
 class StaticBatchAggregation(object):
     """The BATCHED aggregation of a step-batch (GeneralizedRCNNMEGA.prepare_batch + step_batch: tapes, 7 batched attention
     stages, stage FCs, predictor, post-processing of S key frames; ~100 launches and ~6 ms of Python per 20 key frames) on
@@ -1061,13 +906,20 @@ class StaticBatchAggregation(object):
     kernels and their operand values are those of the eager path: identical bits (tests/test_e2e_gpu.py::
     test_graph_aggregation_is_bit_identical; the host logic on the CPU twins in tests/test_host_logic.py).
     Anything else (a ragged record, a short last batch, a new video, sharding) leaves: the state goes back into the
-    model's own deques and the eager path continues."""
+    model's own deques and the eager path continues.
 
-    def __init__(self, model, S, use_graph=True):
+    S = 1 is the per-key-frame lane (ClipEngine(static_aggregation=True), bench.py --aggregation static): one replay per
+    key frame.  While active, an instance owns the model's per-video state, so a model has at most one active instance:
+    ClipEngine holds either _static (S = 1) or _sbatch (S = steps_per_batch), never both.
+    keep_keys: the key frames' boxes / anchor indices in the returned frames are copies (an engine that logs them), not
+    views of state that the write-back has already shifted."""
+
+    def __init__(self, model, S, use_graph=True, keep_keys=False):
         self.m = model
         self.fe = model.roi_heads.box.feature_extractor
         self.S = S
         self.use_graph = use_graph
+        self.keep_keys = keep_keys
         self.active = False
         self.graph = None
         self.replays = 0
@@ -1076,7 +928,7 @@ class StaticBatchAggregation(object):
     # ---- conditions
     def ready(self, steps):
         m, fe = self.m, self.fe
-        if not (m.memory_enable and m.global_enable and fe.cache_memory_kv and fe.static_pools is None):
+        if not (m.memory_enable and m.global_enable and fe.cache_memory_kv):
             return False
         if len(steps) != self.S:
             return False
@@ -1177,6 +1029,10 @@ class StaticBatchAggregation(object):
         steps = [({k: self.inp[k][t] for k in self.keys}, [{"feats": self.in_glob[t]}]) for t in range(S)]
         frames = m.prepare_batch(steps)
         outs = m.step_batch(frames, im_size)
+        if self.keep_keys:
+            for f in frames:
+                f["rois_key"] = f["rois_key"].clone()
+                f["index_key"] = None if f["index_key"] is None else f["index_key"].clone()
         # the state the batch leaves behind -> the state tensors, through temporaries (sources may be views of the state)
         groups = [([r[k].reshape(r[k].shape[0], -1) for r in m.records], 0) for k in self.keys]
         tmp = ops.multi_cat(groups)
@@ -1229,9 +1085,3 @@ class StaticBatchAggregation(object):
         packed, frames = self._out
         return self._unpack(packed, True), frames
 
-
-class BoxListLike(object):
-    """(bbox, size) pair for PostProcessor.run, which reads nothing else."""
-
-    def __init__(self, bbox, size):
-        self.bbox, self.size = bbox, size

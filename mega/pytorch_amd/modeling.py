@@ -699,7 +699,6 @@ class MEGAFeatureExtractor(_Packed):
         self.mem = None
         self.global_cache = None
         self.cache_memory_kv = True      # keep the Wk / Wv projections of memory rows (False: re-project every step)
-        self.static_pools = None         # set by engine.StaticAggregation while it owns the pools
 
     # ---- kernel operands
     def _pack(self, dtype, device):
@@ -859,14 +858,10 @@ class MEGAFeatureExtractor(_Packed):
         for _ in range(self.stage - 2):
             cache.append({"rois_cur": rois_cur01, "rois_ref": rois_dis})
         cache.append({"rois_cur": rois_key, "rois_ref": rois_dis})
-        sp = self.static_pools       # engine.StaticAggregation: pools as fixed-address tensors (hipGraph-able step)
         for i in range(self.stage):
-            if sp is not None:
-                memory = sp.read_memory(i)
-            else:
-                memory = self.mem[i] if self.mem[i] else None             # read BEFORE the push (:914-917)
-                if self.memory_enable:
-                    self.update_memory(i, cache[i])
+            memory = self.mem[i] if self.mem[i] else None             # read BEFORE the push (:914-917)
+            if self.memory_enable:
+                self.update_memory(i, cache[i])
             rois_cur, rois_ref = cache[i]["rois_cur"], cache[i]["rois_ref"]
             feats_cur, feats_ref = cache[i]["feats_cur"], cache[i]["feats_ref"]
             mem_kv = None
@@ -879,10 +874,7 @@ class MEGAFeatureExtractor(_Packed):
             feats_cur, k_loc, vt_loc = relation_attention_forward(
                 pk["local"][i], feats_cur.contiguous(), feats_ref.contiguous(), rois_cur.contiguous(),
                 rois_ref.contiguous(), residual=True, mem_kv=mem_kv, return_kv=True)
-            if sp is not None:          # the push comes after the read and after every use of the old rows
-                n = self.base_num if i == 0 else self.advanced_num
-                sp.push_memory(i, cache[i]["rois_ref"][:n], k_loc[:n], vt_loc[:, :n])
-            elif self.memory_enable and self.cache_memory_kv:
+            if self.memory_enable and self.cache_memory_kv:
                 self._remember_kv(i, k_loc, vt_loc)
             if i != self.stage - 1:
                 feats_cur = self._stage_fc(pk, i + 1, feats_cur)
@@ -947,7 +939,7 @@ class MEGAFeatureExtractor(_Packed):
         projections recomputed by every rank (one tiny GEMM pair per stage), and every rank replays all pushes in
         frame order, so the memory pools stay replicated.  No key frame is aggregated twice: the step no longer has a
         serial (replicated) part."""
-        assert self.cache_memory_kv and self.static_pools is None
+        assert self.cache_memory_kv
         pk = self._packed(self.dtype, frames[0]["x"].device)
         S = len(frames)
         own = [t for t in range(S) if shard is None or shard.owner(t) == shard.rank]

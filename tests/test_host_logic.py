@@ -496,9 +496,12 @@ def test_engine_takes_uint8_clips_and_defers_preprocessing(monkeypatch):
 
 
 def test_static_aggregation_equals_eager(monkeypatch):
-    """ClipEngine(static_aggregation=True): once the window, memory and global pools are full, the aggregation step
-    runs on fixed-address shift-append pools (the hipGraph-able form) -- same detections as the deque-based eager
-    path, including leaving and re-entering steady state and a second video."""
+    """ClipEngine(static_aggregation=True): every key frame after the cold start is an aggregation batch of ONE step;
+    once the window, memory and global pools are full it runs on fixed-address state (engine.StaticBatchAggregation(model,
+    1), the hipGraph-able form) -- the same detections, bit for bit, as the same batch of one on the model's deques
+    (use_static = False), including leaving and re-entering steady state and a second video; and the detections of one
+    model.step() per key frame (CPU twins: MKL's GEMMs are not batch-invariant -> 1e-3 px / 1e-5, as
+    test_batched_aggregation_equals_per_frame_steps; the HIP kernels are: tests/test_e2e_gpu.py asserts bit equality)."""
     from mega.pytorch_amd import engine
     cpu_ops.install(monkeypatch)
     torch.set_num_threads(8)
@@ -510,31 +513,45 @@ def test_static_aggregation_equals_eager(monkeypatch):
     T, nkey = 26, 20
     frames = synth.preprocess_cpu(synth.make_clip(T, 96, 128, seed=2))
     outs, engines = [], []
-    for static in (False, True):
+    for mode in ("per_frame", "eager", "static"):
         model = modeling.build_detection_model(cfg)
         model.load_state_dict(sd)
-        eng = engine.ClipEngine(model, steps_per_batch=3, overlap=False, graphs=False, static_aggregation=static,
-                                batch_aggregation=False)
+        eng = engine.ClipEngine(model, steps_per_batch=3, overlap=False, graphs=False, static_aggregation=mode != "per_frame",
+                                batch_aggregation=False, keep_logits=True)
+        static = mode == "static"
+        eng.use_static = static
+        assert (eng._static is None) == (mode == "per_frame")
         a = eng.run(frames, T, last=12)
         if static:                       # force a round trip static -> eager -> static in the middle of the video
             assert eng._static.active
             eng._static.leave()
         a += eng.run(frames, T, first=12, last=15)
         if static:                       # ... and a stretch of plain eager steps on the written-back deques
-            eng._static.leave()
-            keep, eng._static = eng._static, None
+            assert eng._static.active
+            eng.use_static = False
             a += eng.run(frames, T, first=15, last=17)
-            eng._static = keep
+            assert not eng._static.active
+            eng.use_static = True
         else:
             a += eng.run(frames, T, first=15, last=17)
         a += eng.run(frames, T, first=17, last=nkey)
         a += eng.run(frames[:12], 12, last=4)          # a second video re-initialises everything
         outs.append(a)
         engines.append(eng)
-    assert engines[1].static_steps >= 8, engines[1].static_steps
-    for a, b in zip(*outs):
+    assert engines[2].static_steps >= 8, engines[2].static_steps
+    assert engines[0].static_steps == 0 and engines[1].static_steps == 0
+    assert len(outs[0]) == len(outs[1]) == len(outs[2]) == nkey + 4
+    for a, b in zip(outs[1], outs[2]):
         assert len(a) == len(b) and torch.equal(a.get_field("labels"), b.get_field("labels"))
         assert torch.equal(a.bbox, b.bbox) and torch.equal(a.get_field("scores"), b.get_field("scores"))
+    for e in engines:                    # one log entry per key frame, whichever way it was stepped
+        assert len(e.logits_log) == len(e.key_boxes_log) == len(e.key_index_log) == nkey + 4
+    for i in range(nkey + 4):
+        assert torch.equal(engines[1].logits_log[i], engines[2].logits_log[i]), i
+        assert torch.equal(engines[0].key_boxes_log[i], engines[2].key_boxes_log[i]), i
+    for a, b in zip(outs[0], outs[2]):
+        assert len(a) == len(b) and torch.equal(a.get_field("labels"), b.get_field("labels"))
+        assert (a.bbox - b.bbox).abs().max() < 1e-3 and (a.get_field("scores") - b.get_field("scores")).abs().max() < 1e-5
 
 
 def test_batched_aggregation_equals_per_frame_steps(monkeypatch):
@@ -766,10 +783,12 @@ def test_fgfa_window_override_matches_oracle(monkeypatch):
         assert (det.bbox - wb).abs().max() < 5e-3 and (det.get_field("scores") - ws).abs().max() < 1e-5
 
 
-def test_static_batch_aggregation_equals_eager(monkeypatch):
+@pytest.mark.parametrize("S", [1, 3])
+def test_static_batch_aggregation_equals_eager(monkeypatch, S):
     """engine.StaticBatchAggregation (the batched aggregation on fixed-address state -- what the hipGraph captures) on the
     CPU twins, without a graph: same padded outputs as the eager prepare_batch + step_batch for every key frame over
-    several steady step-batches, the same model state afterwards, and a clean hand-back (leave) to the eager path."""
+    several steady step-batches, the same model state afterwards, and a clean hand-back (leave) to the eager path.
+    S = 3: a step-batch (the default lane); S = 1: the per-key-frame lane of ClipEngine(static_aggregation=True)."""
     from mega.pytorch_amd import engine
     cpu_ops.install(monkeypatch)
     torch.set_num_threads(8)
@@ -800,9 +819,8 @@ def test_static_batch_aggregation_equals_eager(monkeypatch):
         for r in recs[:7]:
             m.records.append(r)
     pos = 7
-    S = 3
     with torch.no_grad():
-        for _ in range(4):                    # eager on both until every pool is full (memory: 7 entries, global: 3)
+        for _ in range(12 // S):              # eager on both until every pool is full (memory: 7 entries, global: 3)
             steps = [(recs[pos + j], globs[pos + j]) for j in range(S)]
             pos += S
             for m in models:
@@ -826,7 +844,7 @@ def test_static_batch_aggregation_equals_eager(monkeypatch):
                 for k in ("rois", "k", "vt"):
                     assert torch.equal(fa.mem[i][k], fb.mem[i][k]), (it, i, k)
         # a ragged record ends the steady state: hand back, continue eagerly, still equal
-        steps = [(record(kn - 5), globs[pos]), (recs[pos + 1], globs[pos + 1]), (recs[pos + 2], globs[pos + 2])]
+        steps = [(record(kn - 5), globs[pos])] + [(recs[pos + j], globs[pos + j]) for j in range(1, S)]
         assert not sb.ready(steps)
         sb.leave()
         want = a.step_batch(a.prepare_batch(steps), (128, 96))
