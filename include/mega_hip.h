@@ -39,6 +39,7 @@ extern "C" {
 #define MEGA_F32 0
 #define MEGA_BF16 1
 #define MEGA_F16 2
+#define MEGA_F8 3     /* OCP e4m3fn codes, one byte each: mega_conv2d_nhwc_f8 only */
 
 #define MEGA_OK 0
 #define MEGA_ERR_ARG 1
@@ -698,6 +699,26 @@ int mega_overlay_detections(unsigned char* frames, int F, int H, int W, const fl
                             int thickness, const unsigned char* palette, int NC, const int* class_glyphs, int ML,
                             const int* fmt_glyphs, const unsigned char* cov, const int* adv, int G, int gh, int gw,
                             int select_only, void* ws, size_t ws_bytes, void* stream);
+
+/* Conv2d + FrozenBatchNorm2d scale / bias + ReLU on FP8 operands (OCP e4m3fn: bias 7, largest finite value 448, no infinities;
+ * not MI300's fnuz), f32 accumulation on the block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, unit block scales): the
+ * opt-in FP8 path of layer3's conv1 / conv2 (cfg FP8_CONV; backbone/resnet.py:324-344).  mega/pytorch_amd/f8.py defines the
+ * quantisation  quantize(v, inv) = e4m3(clamp(f32(v) * inv, -448, 448)), round to nearest even.
+ *   in    [N][H][W][Cin]: in_dtype MEGA_F8 (the producer's codes; in_inv_scale is not read) or MEGA_BF16 (quantised on the load
+ *         path with in_inv_scale = 1 / s_in: no fp8 copy of the tensor is ever written)
+ *   w_f8  [Cout][R][S][Cin] codes (OHWI), one scale sw[c] per output channel
+ *   out   [N*H*W][Cout]: out_dtype MEGA_BF16, y rounded once, or MEGA_F8, quantize(y, out_inv_scale)
+ *   y = act(acc * scale[c] + bias[c]), acc = the f32 sum of code products; the caller folds s_in * sw[c] * bn_scale[c] into
+ *   scale.  scale / bias: f32 [Cout] or NULL (1 / 0).  relu 0 / 1.  No residual operand, no workspace, no synchronisation.
+ * Admitted: 1x1 / stride 1 / pad 0 and 3x3 / stride 1 / pad 1 / dil 1, Cin % 128 == 0, Cout % 64 == 0, N H W < 2^30; anything
+ * else returns MEGA_ERR_ARG before any launch, the output untouched.  A padding tap contributes +0. */
+int mega_conv2d_nhwc_f8(const void* in, int in_dtype, float in_inv_scale, const void* w_f8, const float* scale,
+                        const float* bias, void* out, int out_dtype, float out_inv_scale, int N, int H, int W, int Cin,
+                        int Cout, int R, int S, int stride, int pad, int dil, int relu, void* stream);
+/* < 0: mega_conv2d_nhwc_f8 does not admit the layer; else its tile class, the columns of the 128-row block tile (256 when
+ * Cout % 256 == 0, else 64).  Computed by the function the launch itself uses; launches nothing. */
+int mega_conv2d_nhwc_f8_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int in_dtype,
+                             int out_dtype);
 
 #ifdef __cplusplus
 }

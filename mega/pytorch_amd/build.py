@@ -17,6 +17,7 @@ STAMP = os.path.join(HERE, "csrc", ".build_stamp")
 SOURCES = {
     "igemm.hip": [],
     "igemm8.hip": [],
+    "igemm_f8.hip": [],
     "spatial.hip": [],
     "boxes.hip": ["-ffp-contract=off"],
     # MFMA results in VGPRs: the attention loop otherwise keeps its O accumulators in AGPRs and moves them to VGPRs and

@@ -137,6 +137,10 @@ def _mega_cfg(r50):
         # bfloat16 mode only: "bfloat16" = the residual trunk is a bf16 tensor (rounded at each of the 36 `out += identity`,
         # resnet.py:324-344); "planes" = the trunk is carried as [hi | lo] planes and added in f32 (modeling.conv_mode "wide")
         "RESIDUAL_STREAM": "bfloat16",
+        # bfloat16 mode with RESIDUAL_STREAM "bfloat16" only: "off", or "layer3" = conv1 / conv2 of layer3's identity blocks run
+        # on FP8 (e4m3) operands with calibrated per-tensor scales (f8.py; twice the bf16 MFMA rate); any other combination
+        # raises at model construction
+        "FP8_CONV": "off",
         # test-time box augmentation (defaults.py:511-526; bbox_aug.py): views = identity, its flip if H_FLIP, then every
         # SCALES entry at MAX_SIZE and its flip if SCALE_H_FLIP
         "TEST": {"BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False},

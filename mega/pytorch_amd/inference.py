@@ -306,7 +306,7 @@ def load_predictions(path):
 
 
 def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, anno_path=None,
-              motion_iou=None, seq_nms=None, tracks=None, **kw):
+              motion_iou=None, seq_nms=None, tracks=None, f8_scales=None, **kw):
     """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
     evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
     result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
@@ -331,8 +331,13 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     cfg.MODEL.RPN_ONLY (tools/test_net.py's box_only, inference.py:127): predictions.pth holds the proposal BoxLists
     (field "objectness") and the evaluation is vid_eval.evaluate_proposals: "Recall: x" in proposal_result.txt.
     Seq-NMS, track linking, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY
-    they are a ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is."""
+    they are a ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is.
+    f8_scales (--f8-scales FILE): the calibrated scales of a model built with cfg.FP8_CONV "layer3" -- the JSON file
+    tools/calibrate_f8.py writes, or its dict -- set on the model's FP8 blocks before the run (f8.load_scales)."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
+    if f8_scales is not None:
+        from . import f8
+        f8.load_scales(model, f8_scales)
     box_only = _rpn_only(cfg)
     if box_only and seq_nms is not None and seq_nms is not False:
         raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")

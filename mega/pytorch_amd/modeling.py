@@ -21,6 +21,7 @@ from collections import OrderedDict, deque, namedtuple
 import torch
 from torch import nn
 
+from . import f8
 from . import ops
 from .relation import (RelationWeights, cat_rows, cat_rows_many, relation_attend_batched, relation_attention_forward,
                        relation_project_batched, op_dtype, project_v)
@@ -124,6 +125,22 @@ def conv_mode_of(cfg):
     return CONV_MODES[conv_mode(cfg)]      # the cfg's ConvMode
 
 
+def fp8_conv(cfg):
+    """cfg.FP8_CONV: "off" or "layer3" (f8.py).  "layer3" is honoured only by the plain bf16 mode (DTYPE bfloat16, RESIDUAL_STREAM
+    bfloat16); with any other mode it raises.  The conv mode of an FP8 model is still "bf16"."""
+    v = str(getattr(cfg, "FP8_CONV", "off"))
+    if v not in ("off", "layer3"):
+        raise ValueError("FP8_CONV = %r: 'off' or 'layer3'" % (v,))
+    if v != "off" and conv_mode(cfg) != "bf16":
+        raise ValueError("FP8_CONV %r needs DTYPE bfloat16 with RESIDUAL_STREAM bfloat16 (conv mode 'bf16'), not conv mode %r"
+                         % (v, conv_mode(cfg)))
+    return v
+
+
+# f8.calibrate's pass: while set, FP8 blocks run their bf16 launches and report (block, input, conv1 output) to it
+_F8_RECORDER = None
+
+
 def _nhwc(x):
     """logical NCHW / channels-last memory -> contiguous NHWC view (no copy when the contract holds)."""
     if isinstance(x, ops.Planes):
@@ -212,9 +229,17 @@ class Bottleneck(_Packed):
     """backbone/resnet.py:239-344 with FrozenBN, stride_in_1x1=True: three fused conv+BN(+ReLU) launches,
     the residual add + final ReLU live in conv3's epilogue."""
 
-    def __init__(self, in_channels, bottleneck_channels, out_channels, stride, dilation=1, mode=CONV_MODES["f32"]):
+    def __init__(self, in_channels, bottleneck_channels, out_channels, stride, dilation=1, mode=CONV_MODES["f32"], f8=False):
         super().__init__()
         self.mode = mode
+        # f8 (cfg.FP8_CONV, set here and never from outside afterwards): conv1 / conv2 on FP8 operands (f8.py) with the two
+        # calibrated scales below -- plain floats, not parameters or buffers: the state_dict keys stay the reference's
+        self.f8 = bool(f8)
+        self.f8_in_scale = self.f8_mid_scale = None
+        if self.f8 and (in_channels != out_channels or stride != 1 or dilation != 1 or mode.name != "bf16"
+                        or in_channels % 128 != 0 or bottleneck_channels % 128 != 0):
+            raise ValueError("an FP8 bottleneck is an identity block (stride 1, no dilation) of the plain bf16 mode with "
+                             "channel counts that are multiples of 128")
         self.downsample = None
         if in_channels != out_channels:
             self.down_stride = stride if dilation == 1 else 1
@@ -241,7 +266,38 @@ class Bottleneck(_Packed):
             s, b = self.downsample[1].folded()
             pk["wd"] = pack(self.downsample[0]).to(device)
             pk["sd"], pk["bd"] = s.to(device), b.to(device)
+        if self.f8:      # the FP8 codes of conv1 / conv2 beside the bf16 operands (conv3 still needs its own)
+            for i in (1, 2):
+                codes, sw = ops.pack_conv_weight_f8(getattr(self, "conv%d" % i).weight.detach().float().permute(0, 2, 3, 1))
+                pk["q%d" % i], pk["sw%d" % i] = codes.to(device), sw.to(device)
+            pk["fold"] = None      # ((f8_in_scale, f8_mid_scale), conv1's scale vector, conv2's): see _f8_fold
         return pk
+
+    def set_f8_scales(self, in_scale, mid_scale):
+        """the calibrated scales of an FP8 block (f8.calibrate / f8.load_scales)"""
+        if not self.f8:
+            raise ValueError("not an FP8 block")
+        self.f8_in_scale, self.f8_mid_scale = float(in_scale), float(mid_scale)
+
+    def _f8_fold(self, pk):
+        """the epilogue scale vectors s_act * sw * bn_scale of conv1 / conv2, folded once per pair of scales"""
+        key = (self.f8_in_scale, self.f8_mid_scale)
+        if pk["fold"] is None or pk["fold"][0] != key:
+            with torch.no_grad():
+                pk["fold"] = (key, f8.fold_scale(key[0], pk["sw1"], pk["s1"]), f8.fold_scale(key[1], pk["sw2"], pk["s2"]))
+        return pk["fold"][1], pk["fold"][2]
+
+    def run_f8(self, x, out=None):
+        """conv1 bf16 trunk -> fp8, conv2 fp8 -> bf16 (both ops.conv2d_nhwc_f8), conv3 + residual as the bf16 block's"""
+        if self.f8_in_scale is None or self.f8_mid_scale is None:
+            raise RuntimeError("an FP8 bottleneck has no scales: run f8.calibrate(model, frames) or f8.load_scales(model, file)")
+        if x.dtype != torch.bfloat16:
+            raise ValueError("an FP8 bottleneck reads a bfloat16 trunk, not %s" % x.dtype)
+        pk = self._packed(x.dtype, x.device)
+        sc1, sc2 = self._f8_fold(pk)
+        t = ops.conv2d_nhwc_f8(x, pk["q1"], sc1, pk["b1"], in_scale=self.f8_in_scale, out_scale=self.f8_mid_scale, relu=True)
+        t = ops.conv2d_nhwc_f8(t, pk["q2"], sc2, pk["b2"], pad=1, relu=True)
+        return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=x, relu=True, out=out)
 
     def run_sp(self, x, out_mode="planes"):
         """The block of a planes mode (self.mode.planes).  x: ops.Planes, or -- "trunk", the stem's output -- a plain
@@ -297,6 +353,9 @@ class Bottleneck(_Packed):
         if self.mode.planes:
             assert out is None and not subsample and not compact_in
             return self.run_sp(x)
+        if self.f8 and _F8_RECORDER is None:
+            assert not subsample and not compact_in
+            return self.run_f8(x, out=out)
         pk = self._packed(x.dtype, x.device)
         assert not subsample or self.can_subsample(x)
         assert not compact_in or self.reads_even_pixels_only()
@@ -315,14 +374,18 @@ class Bottleneck(_Packed):
         if subsample:
             t = ops.conv2d_nhwc(t, pk["w2"], pk["s2"], pk["b2"], stride=2, pad=1, relu=True)
             return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out=out, residual_stride=2)
+        if self.f8:      # (f8.calibrate's pass)
+            _F8_RECORDER(self, x, t)
         t = ops.conv2d_nhwc(t, pk["w2"], pk["s2"], pk["b2"], pad=self.dilation, dil=self.dilation, relu=True)
         return ops.conv2d_nhwc(t, pk["w3"], pk["s3"], pk["b3"], residual=identity, relu=True, out=out)
 
 
-def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride, dilation=1, mode=CONV_MODES["f32"]):
+def _make_stage(in_channels, bottleneck_channels, out_channels, block_count, first_stride, dilation=1, mode=CONV_MODES["f32"],
+                f8=False):
+    """f8: the stage's identity blocks (every block but the first) are FP8 blocks"""
     blocks, stride = [], first_stride
-    for _ in range(block_count):
-        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride, dilation, mode))
+    for bi in range(block_count):
+        blocks.append(Bottleneck(in_channels, bottleneck_channels, out_channels, stride, dilation, mode, f8=f8 and bi > 0))
         stride, in_channels = 1, out_channels
     return nn.Sequential(*blocks)
 
@@ -376,6 +439,7 @@ class ResNet(nn.Module):
         super().__init__()
         self.dtype = compute_dtype(cfg)
         self.mode = conv_mode_of(cfg)
+        self.fp8 = fp8_conv(cfg)
         blocks = _STAGE_BLOCKS[cfg.MODEL.BACKBONE.CONV_BODY]
         self.stem = BaseStem(cfg.MODEL.RESNETS.STEM_OUT_CHANNELS)
         in_ch = cfg.MODEL.RESNETS.STEM_OUT_CHANNELS
@@ -383,7 +447,8 @@ class ResNet(nn.Module):
         for i, n in enumerate(blocks):
             mid, out = 64 * 2 ** i, cfg.MODEL.RESNETS.RES2_OUT_CHANNELS * 2 ** i
             name = "layer%d" % (i + 1)
-            self.add_module(name, _make_stage(in_ch, mid, out, n, first_stride=int(i > 0) + 1, mode=self.mode))
+            self.add_module(name, _make_stage(in_ch, mid, out, n, first_stride=int(i > 0) + 1, mode=self.mode,
+                                              f8=self.fp8 == "layer3" and name == "layer3"))
             self.stages.append(name)
             in_ch = out
 

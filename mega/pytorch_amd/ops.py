@@ -12,6 +12,7 @@ import math
 import torch
 
 from . import _lib
+from . import f8
 
 F32, BF16, F16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -1109,6 +1110,67 @@ def conv2d_sp(x, w, scale=None, bias=None, residual=None, stride=1, pad=0, dil=1
     _call("mega_conv2d_nhwc_sp_dt", xt, ldi, 2 * C if kwrap else 0, w, scale, bias, None if residual is None else residual.t,
           0, out, ldo, mode, N, H, W, Cw, Cout, R, S, stride, pad, dil, int(relu), _DT[pdt], ws, nb, prof=prof)
     return Planes(out, Cout) if mode == 1 else out
+
+
+# ------------------------------------------------------------------------------------------------ FP8 conv (f8.py)
+F8 = 3      # MEGA_F8: OCP e4m3fn codes
+
+
+def pack_conv_weight_f8(w_ohwi_f32):
+    """f32 conv weight [Cout,R,S,Cin] (OHWI) -> (codes float8_e4m3fn [Cout,R,S,Cin], sw f32 [Cout]): one scale per output
+    channel, sw[o] = absmax(w[o]) / 448 (1 for an all-zero channel), codes = f8.quantize(w[o], 1 / sw[o])."""
+    w = w_ohwi_f32.float().contiguous()
+    sw = f8.weight_scales(w)
+    return f8.quantize(w, (1.0 / sw).view(-1, 1, 1, 1)).contiguous(), sw.contiguous()
+
+
+def f8_conv_admitted(N, H, W, Cin, Cout, R, S, stride, pad, dil):
+    """the shapes mega_conv2d_nhwc_f8 admits (the library's own rule, mega_conv2d_nhwc_f8_plan, says the same)"""
+    geo = (R, S, pad) in ((1, 1, 0), (3, 3, 1)) and stride == 1 and dil == 1
+    return bool(geo and min(N, H, W) >= 1 and Cin >= 128 and Cin % 128 == 0 and Cout >= 64 and Cout % 64 == 0
+                and max(H, W) <= 1 << 20 and N * H * W <= 0x3FFFFFFF)
+
+
+def conv2d_nhwc_f8(x, w_codes, scale, bias, in_scale=None, out_scale=None, pad=0, relu=False, stride=1, dil=1, out=None):
+    """conv + scale / bias (+ ReLU) on FP8 operands (mega_conv2d_nhwc_f8; f8.py defines the quantisation).
+    x [N,H,W,Cin]: float8_e4m3fn codes, or bfloat16 with in_scale = the tensor's scale s (quantised with 1 / s on the kernel's
+    load path); w_codes [Cout,R,S,Cin] float8_e4m3fn; scale / bias f32 [Cout] (the caller folds s_in * sw * bn_scale into
+    scale: f8.fold_scale).  out_scale None: bf16 output; a scale s: float8_e4m3fn output quantize(y, 1 / s).
+    An unknown dtype or a shape the kernel does not admit raises ValueError before any device or library check."""
+    if x.dtype not in (torch.bfloat16, f8.FP8):
+        raise ValueError("conv2d_nhwc_f8: input dtype %s (bfloat16 or float8_e4m3fn)" % x.dtype)
+    if w_codes.dtype != f8.FP8:
+        raise ValueError("conv2d_nhwc_f8: weight dtype %s (float8_e4m3fn codes: pack_conv_weight_f8)" % w_codes.dtype)
+    if x.dim() != 4 or w_codes.dim() != 4 or x.shape[3] != w_codes.shape[3]:
+        raise ValueError("conv2d_nhwc_f8: x %s against w %s" % (tuple(x.shape), tuple(w_codes.shape)))
+    N, H, W, Cin = x.shape
+    Cout, R, S, _ = w_codes.shape
+    if not f8_conv_admitted(N, H, W, Cin, Cout, R, S, stride, pad, dil):
+        raise ValueError("conv2d_nhwc_f8 does not admit x %s, w %s, stride %d, pad %d, dil %d: 1x1 / pad 0 or 3x3 / pad 1, "
+                         "stride 1, dil 1, Cin %% 128 == 0, Cout %% 64 == 0" % (tuple(x.shape), tuple(w_codes.shape), stride, pad, dil))
+    if x.dtype == torch.bfloat16 and in_scale is None:
+        raise ValueError("conv2d_nhwc_f8: a bfloat16 input needs in_scale")
+    for s in (in_scale, out_scale):
+        if s is not None and not (float(s) > 0.0 and float(s) < float("inf")):
+            raise ValueError("conv2d_nhwc_f8: scale %r is not a positive finite number" % (s,))
+    assert x.is_contiguous() and w_codes.is_contiguous()
+    for v in (scale, bias):
+        assert v is None or (v.dtype == torch.float32 and v.numel() == Cout and v.is_contiguous())
+    odt = torch.bfloat16 if out_scale is None else f8.FP8
+    if out is None:
+        out = torch.empty((N, H, W, Cout), dtype=odt, device=x.device)
+    else:
+        assert out.dtype == odt and out.shape == (N, H, W, Cout) and out.is_contiguous()
+    prof = None
+    if _PROF is not None:
+        prof = ("igemm_f8_%s_%s" % ("bf16in" if x.dtype == torch.bfloat16 else "f8in", "f8out" if out_scale is not None else "bf16out"),
+                2.0 * N * H * W * Cout * R * S * Cin,
+                x.numel() * x.element_size() + w_codes.numel() + out.numel() * out.element_size(),
+                "%dx%dx%d (%dx%d)" % (N * H * W, Cout, R * S * Cin, R, S))
+    _call("mega_conv2d_nhwc_f8", x, BF16 if x.dtype == torch.bfloat16 else F8, 1.0 if in_scale is None else f8.inv_scale(in_scale),
+          w_codes, scale, bias, out, BF16 if out_scale is None else F8, 1.0 if out_scale is None else f8.inv_scale(out_scale),
+          N, H, W, Cin, Cout, R, S, stride, pad, dil, int(bool(relu)), prof=prof)
+    return out
 
 
 class X3Weight(object):

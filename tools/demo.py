@@ -3,6 +3,8 @@ demo/demo.py).
 
   python tools/demo.py mega --arch R-101 --weights MEGA_R_101.pth --image-folder <frames> --output-folder <out>
       the sorted "*<suffix>" files of the folder as one video -> <out>/000000.jpg ...; one JSON line with the timings.
+  python tools/demo.py mega --dtype bfloat16 --f8-scales scales.json ...
+      the same with layer3's identity blocks in FP8 (cfg.FP8_CONV), the scales from tools/calibrate_f8.py.
   python tools/demo.py mega --dry-run
       parses the arguments and prints the resolved settings as one JSON line; no device code is imported.
 Video files (the reference's --video / --output-video) are out of scope: no codec library is a dependency.
@@ -27,6 +29,8 @@ def parse(argv=None):
     ap.add_argument("--threshold", type=float, default=0.7, help="draw detections with score > threshold")
     ap.add_argument("--thickness", type=int, default=1, help="outline thickness in pixels (odd)")
     ap.add_argument("--dtype", choices=["float32", "bfloat16", "float16"], default="float32")
+    ap.add_argument("--f8-scales", default=None, metavar="FILE", help="run layer3's identity blocks in FP8 (cfg.FP8_CONV "
+                    "'layer3'; --dtype bfloat16) with the calibrated scales of this JSON file (tools/calibrate_f8.py)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--dry-run", action="store_true", help="print the resolved settings as one JSON line and stop")
     a = ap.parse_args(argv)
@@ -41,19 +45,24 @@ def main(argv=None):
     a = parse(argv)
     settings = {"method": a.method, "arch": a.arch, "weights": a.weights, "flownet_weights": a.flownet_weights,
                 "image_folder": a.image_folder, "suffix": a.suffix, "output_folder": a.output_folder,
-                "threshold": a.threshold, "thickness": a.thickness, "dtype": a.dtype, "device": a.device}
+                "threshold": a.threshold, "thickness": a.thickness, "dtype": a.dtype, "device": a.device,
+                "f8_scales": a.f8_scales}
     if a.dry_run:
         print(json.dumps(dict(settings, dry_run=True)))
         return 0
     sys.path.insert(0, ROOT)
     import torch
-    from mega.pytorch_amd import checkpoint, config, demo, modeling
+    from mega.pytorch_amd import checkpoint, config, demo, f8, modeling
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a HIP device (the detector has no CPU fallback)")
     cfg = config.get_cfg(a.arch, a.method)
     cfg.DTYPE = a.dtype
     cfg.MODEL.DEVICE = a.device
+    if a.f8_scales:
+        cfg.FP8_CONV = "layer3"
     model = modeling.build_detection_model(cfg)
+    if a.f8_scales:
+        f8.load_scales(model, a.f8_scales)
     if a.weights:
         checkpoint.load_checkpoint(cfg, model, a.weights)
     if a.flownet_weights:
