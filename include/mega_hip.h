@@ -678,6 +678,30 @@ int mega_motion_iou(const float* gt_box, const long long* gt_track, const long l
                     const int* video_end, int F, long long G, int W, int max_gt, double* values, int* counts, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* Detection error diagnosis (mega/pytorch_amd/diagnose.py defines it; the reference has no counterpart): the kind of every
+ * detection and the detections that found or nearly found every GT box, for F frames and labels 0 .. C-1.  One wave per
+ * frame.  The IoU is mega_vid_eval_match's throughout (prediction rescaled by ratio in f32, +1 on x2 / y2, boxlist_iou, no
+ * contraction); a NaN IoU satisfies no comparison; tf = 0.5f and tb = bg_thresh are compared in f32 with >=.
+ *   Matching: mega_vid_eval_match's for one range and no motion list -- per frame, in the frame's run of `order` (label,
+ *   then score descending, then position descending), each detection takes the not yet taken GT box of its label with the
+ *   largest IoU >= tf, the lowest GT index among equals: a TP.
+ *   Every other detection, with a / ga = the largest IoU with a GT box of its label and that box (lowest index on a tie),
+ *   b / gb the same over the boxes of other labels ("none" meets no threshold), by the first rule that holds:
+ *   DUPE a >= tf (ga), LOC tb <= a < tf (ga), CLS b >= tf (gb), BOTH tb <= b < tf (gb), else BKG (no box).
+ * Inputs, flat over frames: det_box [N][4] f32, det_label [N] i32, det_score [N] f32 (no NaN), det_off [F+1] i64, order [N]
+ * i32 and ratio [F][2] f32 as for mega_vid_eval_match; gt_box [G][4] f32, gt_label [G] i32, gt_off [F+1] i64; max_gt = the
+ * largest GT count of a frame (<= 4096).
+ * Outputs, every element written: det_kind [N] u8 (0 TP, 1 DUPE, 2 LOC, 3 CLS, 4 BOTH, 5 BKG), det_gt [N] i32 (the matched
+ * or attributed box's index in gt_box, -1 for BKG), det_iou [N] f32 (the IoU with that box, 0 for BKG); gt_det [3][G] i32,
+ * per GT box the index of the TP that took it, of the best LOC and of the best CLS detection attributed to it (-1: none;
+ * best = the highest score, on equal scores the higher position in its frame).
+ * No workspace, no atomics.  A NULL pointer with a non-zero size, negative sizes, C <= 0, max_gt > 4096, N > 2^31 - 1,
+ * bg_thresh outside (0, 0.5): MEGA_ERR_ARG before any launch.  F = 0 launches nothing.  Does not synchronise. */
+int mega_diagnose_match(const float* det_box, const int* det_label, const float* det_score, const long long* det_off,
+                        const int* order, const float* ratio, const float* gt_box, const int* gt_label,
+                        const long long* gt_off, int F, int C, long long N, long long G, int max_gt, float bg_thresh,
+                        unsigned char* det_kind, int* det_gt, float* det_iou, int* gt_det, void* stream);
+
 /* Detection overlay of the demo (mega/pytorch_amd/demo.py defines it), in place on F original-size frames, no host round
  * trip.  Per frame: rows i < counts[f] with score > thr (strict), drawn in descending score order (equal scores: ascending
  * row); box -> original frame by ONE f32 multiply per coordinate (x * sx, y * sy; sx = f32(W / resized width) computed by

@@ -306,7 +306,7 @@ def load_predictions(path):
 
 
 def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, group=None, anno_path=None,
-              motion_iou=None, seq_nms=None, tracks=None, f8_scales=None, **kw):
+              motion_iou=None, seq_nms=None, tracks=None, f8_scales=None, diagnose=None, **kw):
     """inference.py:72-134: predictions.pth, and with anno_path (the directory of the frames' XML annotations) the VID
     evaluation of inference.py:129-132 on the main process: vid_eval.evaluate_detections logs the AP50 text and writes
     result.txt next to predictions.pth.  motion_iou: None, the path of vid_groundtruth_motion_iou.mat or its
@@ -333,7 +333,11 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     Seq-NMS, track linking, TEST.BBOX_AUG, TEST.SOFT_NMS and TEST.BBOX_VOTE work on detections: combined with RPN_ONLY
     they are a ValueError.  TEST.SOFT_NMS / TEST.BBOX_VOTE are read from cfg, as TEST.BBOX_AUG is.
     f8_scales (--f8-scales FILE): the calibrated scales of a model built with cfg.FP8_CONV "layer3" -- the JSON file
-    tools/calibrate_f8.py writes, or its dict -- set on the model's FP8 blocks before the run (f8.load_scales)."""
+    tools/calibrate_f8.py writes, or its dict -- set on the model's FP8 blocks before the run (f8.load_scales).
+    diagnose: None (off), True or a dict of diagnose.evaluate_errors' score_thresh / bg_thresh: with anno_path, after the
+    AP the raw detections' error diagnosis (error kinds, GT states and the mAP each error type costs) goes to the log and
+    to result_diagnosis.txt, with the motion cross-tabulation when motion_iou is given; result.txt and the return value
+    do not change.  It works on detections: combined with RPN_ONLY it is a ValueError."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     if f8_scales is not None:
         from . import f8
@@ -343,6 +347,12 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
         raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")
     if box_only and tracks is not None and tracks is not False:
         raise ValueError("MODEL.RPN_ONLY returns proposals: track linking (tracks=...) needs detections")
+    if box_only and diagnose is not None and diagnose is not False:
+        raise ValueError("MODEL.RPN_ONLY returns proposals: the error diagnosis (diagnose=...) needs detections")
+    if diagnose is not None and diagnose is not False:
+        from . import diagnose as dg
+        diagnose_params = {} if diagnose is True else dict(diagnose)
+        dg.check_params(**diagnose_params)                       # (a bad value raises before the run, not after it)
     if tracks is not None and tracks is not False:
         from . import tracks as tr
         track_params = {} if tracks is True else dict(tracks)
@@ -419,6 +429,9 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
             return predictions
         vid_eval.evaluate_detections(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                      logger=logger)
+        if diagnose is not None and diagnose is not False:
+            dg.evaluate_errors(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
+                               logger=logger, **diagnose_params)
         if rescored is not None:
             vid_eval.evaluate_detections(rescored, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
                                          logger=logger, result_name="result_seq_nms.txt")

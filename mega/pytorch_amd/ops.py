@@ -1537,6 +1537,35 @@ def motion_iou(gt_box, gt_track, gt_off, video_start, video_end, window, max_gt,
     return values, counts
 
 
+# ------------------------------------------------------------------------------------------------ error diagnosis
+def diagnose_match(det_box, det_label, det_score, det_off, order, ratio, gt_box, gt_label, gt_off, C, max_gt, bg_thresh,
+                   out=None):
+    """The kind of every detection and the detections of every GT box (include/mega_hip.h mega_diagnose_match;
+    mega/pytorch_amd/diagnose.py defines it).  det_box [N,4] f32, det_label [N] i32, det_score [N] f32, det_off [F+1] i64,
+    order [N] i32 and ratio [F,2] f32 as for vid_eval_match, gt_box [G,4] f32, gt_label [G] i32, gt_off [F+1] i64.
+    -> det_kind [N] u8, det_gt [N] i32, det_iou [N] f32, gt_det [3,G] i32 on the device, every element written by the
+    kernel (out: such a tuple to write into instead of fresh tensors).  The kernel takes no workspace.  Does not
+    synchronise."""
+    N, F, G = det_box.shape[0], det_off.shape[0] - 1, gt_box.shape[0]
+    for t, dt in ((det_box, torch.float32), (det_label, torch.int32), (det_score, torch.float32), (det_off, torch.int64),
+                  (order, torch.int32), (ratio, torch.float32), (gt_box, torch.float32), (gt_label, torch.int32),
+                  (gt_off, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous()
+    assert det_box.shape == (N, 4) and det_label.shape == (N,) and det_score.shape == (N,) and order.shape == (N,)
+    assert ratio.shape == (F, 2) and gt_box.shape == (G, 4) and gt_label.shape == (G,) and gt_off.shape == (F + 1,)
+    dev = det_box.device
+    if out is None:
+        out = (torch.empty(N, dtype=torch.uint8, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+               torch.empty(N, dtype=torch.float32, device=dev), torch.empty((3, G), dtype=torch.int32, device=dev))
+    det_kind, det_gt, det_iou, gt_det = out
+    for t, dt, shape in ((det_kind, torch.uint8, (N,)), (det_gt, torch.int32, (N,)), (det_iou, torch.float32, (N,)),
+                         (gt_det, torch.int32, (3, G))):
+        assert t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+    _call("mega_diagnose_match", det_box, det_label, det_score, det_off, order, ratio, gt_box, gt_label, gt_off, F, int(C),
+          N, G, int(max_gt), float(bg_thresh), det_kind, det_gt, det_iou, gt_det, prof=("diagnose_match",))
+    return det_kind, det_gt, det_iou, gt_det
+
+
 # ------------------------------------------------------------------------------------------------ demo overlay
 def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, thickness, palette, atlas,
                        select_only=False):

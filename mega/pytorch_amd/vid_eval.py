@@ -314,6 +314,27 @@ def _pack(predictions, groundtruth, motion_iou, motion_ranges):
     return parts, {"F": F, "N": N, "C": C, "max_gt": max_gt, "counts": counts}
 
 
+def class_orders(scores, labels, counts, C, dev):
+    """The two orders of the evaluation, on the device: scores [N] f32 and labels [N] i32 (flat, frame by frame), counts [F]
+    (host) -> order [N] i32 (each frame's run by label, score descending, position descending: what the matching walks),
+    gorder [N] i32 (each class's run over the dataset: score descending, then descending position in the frame-by-frame
+    concatenation of the frames' ordered detections) and seg_off [C+1] i64 (class l's run of gorder)."""
+    N = scores.shape[0]
+    if N:
+        # within-frame order: frame, label, score descending, position descending
+        key = flat.frame_ids(counts, dev) * C + labels.long()
+        order = flat.segment_order(scores, key, start=torch.arange(N - 1, -1, -1, device=dev))
+        # per class over the dataset: score descending, then descending position in that frame-by-frame concatenation
+        gorder = flat.segment_order(scores, labels, start=order.flip(0))
+        order, gorder = order.int(), gorder.int()
+        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+        seg_off[1:] = torch.cumsum(torch.bincount(labels.long(), minlength=C), 0)
+    else:
+        order = gorder = torch.zeros(0, dtype=torch.int32, device=dev)
+        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+    return order, gorder, seg_off
+
+
 def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_only=False):
     """The kernels' outputs (numpy): match [R,N] u8 and pred_ignore [R,N] f64 per detection (flat, frame by frame, in
     each BoxList's order), n_pos [R,C] i32, ap [R,C] f64, with R = 4 motion ranges (1 without motion IoUs).
@@ -326,19 +347,7 @@ def match_and_ap(predictions, groundtruth, motion_iou=None, device="cuda", ap_on
     F, N, C = meta["F"], meta["N"], meta["C"]
     t = flat.upload(parts, dev)
     labels = t["det_label"]
-    scores = t["score"]
-    if N:
-        # within-frame order: frame, label, score descending, position descending
-        key = flat.frame_ids(meta["counts"], dev) * C + labels.long()
-        order = flat.segment_order(scores, key, start=torch.arange(N - 1, -1, -1, device=dev))
-        # per class over the dataset: score descending, then descending position in that frame-by-frame concatenation
-        gorder = flat.segment_order(scores, labels, start=order.flip(0))
-        order, gorder = order.int(), gorder.int()
-        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
-        seg_off[1:] = torch.cumsum(torch.bincount(labels.long(), minlength=C), 0)
-    else:
-        order = gorder = torch.zeros(0, dtype=torch.int32, device=dev)
-        seg_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+    order, gorder, seg_off = class_orders(t["score"], labels, meta["counts"], C, dev)
     with torch.cuda.device(dev):
         match, pign, n_pos = ops.vid_eval_match(t["det_box"], labels, t["det_off"], order, t["ratio"], t["gt_box"],
                                                 t["gt_label"], t.get("gt_motion"), t["gt_off"], t["ranges"], C,

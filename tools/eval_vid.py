@@ -29,6 +29,10 @@ field "filled", and result_tracks.txt and --tubelet-ap judge the refined list.
 judges the tracks just linked; without, --predictions must already carry the field "track_ids" (a
 predictions_tracks.pth).
 
+--diagnose (with --diagnose-score-thresh X / --diagnose-bg-thresh X) adds the error diagnosis of the raw detections
+(mega.pytorch_amd.diagnose): every detection's kind (TP / DUPE / LOC / CLS / BOTH / BKG), every GT box's state and the mAP
+each error type costs -> result_diagnosis.txt, with the per-motion-range rows when --motion-iou is given.
+
 --box-only evaluates proposals instead (predictions made with MODEL.RPN_ONLY True, field "objectness"): the recall of the
 GT boxes at IoU 0.5 by each frame's first --limit proposals -> proposal_result.txt ("Recall: x", the reference's
 do_vid_evaluation(box_only=True)); --recall-table adds the recall at limits 10 / 50 / 100 / 300 and IoU 0.50 .. 0.95 with
@@ -79,6 +83,12 @@ def main(argv=None):
     ap.add_argument("--tubelet-ap", action="store_true", help="tubelet AP of the tracks against the GT tracks "
                     "(result_tubelets.txt)")
     ap.add_argument("--tubelet-score", choices=("mean", "max"), default="mean", help="--tubelet-ap: a tubelet's score")
+    ap.add_argument("--diagnose", action="store_true", help="error diagnosis of the detections: error kinds, GT states and "
+                    "the mAP each error type costs (result_diagnosis.txt)")
+    ap.add_argument("--diagnose-score-thresh", type=float, default=None, metavar="X", help="--diagnose: the count tables "
+                    "also cover the detections scoring at least X (default 0.5)")
+    ap.add_argument("--diagnose-bg-thresh", type=float, default=None, metavar="X", help="--diagnose: a detection below "
+                    "this IoU with every GT box is background (0 < X < 0.5, default 0.1)")
     ap.add_argument("--box-only", action="store_true", help="proposal recall of RPN-only predictions (proposal_result.txt)")
     ap.add_argument("--limit", type=int, default=300, help="--box-only: proposals used per frame (at most 1024)")
     ap.add_argument("--recall-table", action="store_true", help="--box-only: also the recall per limit and IoU threshold")
@@ -89,6 +99,17 @@ def main(argv=None):
         ap.error("--box-only evaluates proposals: --tracks applies to detections")
     if a.box_only and a.tubelet_ap:
         ap.error("--box-only evaluates proposals: --tubelet-ap applies to tracks")
+    if a.box_only and a.diagnose:
+        ap.error("--box-only evaluates proposals: --diagnose applies to detections")
+    if not a.diagnose and (a.diagnose_score_thresh is not None or a.diagnose_bg_thresh is not None):
+        ap.error("--diagnose-score-thresh / --diagnose-bg-thresh apply to --diagnose")
+    if a.diagnose:
+        from mega.pytorch_amd import diagnose
+        try:
+            diag = diagnose.check_params(diagnose.SCORE_THRESH if a.diagnose_score_thresh is None else a.diagnose_score_thresh,
+                                         diagnose.BG_THRESH if a.diagnose_bg_thresh is None else a.diagnose_bg_thresh)
+        except ValueError as e:
+            ap.error(str(e))
     if not a.tracks and (a.tracks_fill or a.tracks_smooth is not None or a.tracks_fill_scale is not None):
         ap.error("--tracks-fill / --tracks-smooth / --tracks-fill-scale refine linked tracks: they need --tracks")
     if a.tracks:
@@ -130,6 +151,10 @@ def main(argv=None):
         return 0
     res = vid_eval.evaluate_detections(preds, gt, motion_iou=motion, output_folder=out, device=a.device)
     sys.stdout.write(vid_eval.format_result(res))
+    if a.diagnose:
+        res = diagnose.evaluate_errors(preds, gt, motion_iou=motion, score_thresh=diag[0], bg_thresh=diag[1],
+                                       output_folder=out, device=a.device)
+        sys.stdout.write("Diagnosis:\n" + res["text"])
     if a.seq_nms:
         from mega.pytorch_amd import seq_nms
         videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
