@@ -9,6 +9,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All work is
  *     enqueued on that stream; no call synchronises the device or copies to the host, except mega_seq_nms and
  *     mega_link_tracks, which read their status word back.
+ *   - mega_jpeg_probe and mega_jpeg_entropy_decode are the exception to both rules above: they take HOST pointers and no
+ *     stream, run entirely on the calling thread and touch no device (lengths are long long, everything else a pointer).
  *   - dtype codes: MEGA_F32 = 0 (exact-f32 MFMA path, parity mode), MEGA_BF16 = 1, MEGA_F16 = 2 (IEEE half: the same
  *     kernels instantiated for _Float16 operands -- the bf16 MFMA rate and bytes with 11 significant bits instead of 8,
  *     values bounded by 65 504; accumulation is f32 in every mode).  Wherever an entry point takes a dtype code, MEGA_F16
@@ -743,6 +745,32 @@ int mega_conv2d_nhwc_f8(const void* in, int in_dtype, float in_inv_scale, const 
  * Cout % 256 == 0, else 64).  Computed by the function the launch itself uses; launches nothing. */
 int mega_conv2d_nhwc_f8_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int in_dtype,
                              int out_dtype);
+
+/* JPEG decode, host entropy stage + device pixel stages (mega/pytorch_amd/jpeg.py defines the accepted streams, the layout and
+ * the arithmetic; replaces the PIL.Image.open(...).convert("RGB") of the reference's loader, mega_core/data/datasets/vid.py
+ * __getitem__ / vid_mega.py:95-142, bit for bit).
+ * mega_jpeg_probe: parse the markers of the JPEG at data[0, nbytes) (host memory) and fill info[MEGA_JPEG_INFO_INTS]:
+ *   0 width, 1 height, 2 components, 3 sampling code (0 gray, 1 4:4:4, 2 4:2:2, 3 4:2:0), 4 + 2c / 5 + 2c blocks per row /
+ *   column of component c over the MCU-padded grid, 10 restart interval, 11 int16 elements mega_jpeg_entropy_decode writes.
+ *   MEGA_ERR_ARG for anything outside the accepted set (or not a JPEG); info is then untouched.
+ * mega_jpeg_entropy_decode: Huffman-decode the same bytes into out (host memory, out_elems >= info[11] int16 elements):
+ *   qt[3][64], the quantisation table of each component in natural order, then the coefficient planes of Y, Cb, Cr,
+ *   [block row][block col][64] in natural order, not dequantised.  info: a probe's result the stream must agree with in entries
+ *   0 to 3.  Every element of out[0, info[11]) is written.  MEGA_ERR_ARG for a refused, mismatching, truncated or corrupt
+ *   stream; never reads outside data or writes outside out. */
+#define MEGA_JPEG_INFO_INTS 12
+int mega_jpeg_probe(const unsigned char* data, long long nbytes, int* info);
+int mega_jpeg_entropy_decode(const unsigned char* data, long long nbytes, const int* info, short* out, long long out_elems);
+/* mega_jpeg_reconstruct: N frames of one size and sampling code, frame n's coefficients (the layout above) at coef + n * stride
+ * (device, int16 elements; stride % 8 == 0 and coef 16-byte aligned) -> rgb [N][H][W][3] uint8.  Two launches: dequantise +
+ * integer IDCT + clamp into component planes in ws, then chroma upsampling + YCbCr -> RGB.  MEGA_ERR_ARG before any launch
+ * for N outside [1, 65535], H or W outside [1, 65535], an unknown sampling code, a stride below the frame's element count or
+ * not a multiple of 8, a NULL pointer, ws off an 8-byte boundary, rgb off a 4-byte boundary when W % 4 == 0 (other widths are
+ * stored byte by byte, so a slice of a batch of odd-sized frames is accepted); MEGA_ERR_WS for a workspace below
+ * mega_jpeg_reconstruct_workspace_bytes(N, H, W, sampling) (0 for arguments the launch would refuse). */
+size_t mega_jpeg_reconstruct_workspace_bytes(int N, int H, int W, int sampling);
+int mega_jpeg_reconstruct(const short* coef, long long stride, int N, int H, int W, int sampling, unsigned char* rgb, void* ws,
+                          size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ SOURCES = {
     "track_eval.hip": ["-ffp-contract=off"],  # the detection AP's rescale + IoU (box_math.h's vid_iou), bit for bit
     "motion_iou.hip": ["-ffp-contract=off"],  # the same vid_iou between the boxes of one GT track, bit for bit
     "diagnose.hip": ["-ffp-contract=off"],    # the same vid_iou between a detection and every GT box of its frame
+    "jpeg.hip": [],                           # integer arithmetic only: nothing to contract
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -129,7 +129,7 @@ class VIDDemo(object):
 
     def __init__(self, cfg, model=None, confidence_threshold=0.7, thickness=1, output_folder=None, steps_per_batch=10,
                  engine_kwargs=None, source_kwargs=None, seed=0, render_chunk=16, glyph_height=16, runner=None,
-                 overlay=None):
+                 overlay=None, decode="host"):
         if int(thickness) < 1 or int(thickness) % 2 == 0:
             raise ValueError("thickness must be odd, got %r" % (thickness,))
         self.cfg = cfg
@@ -140,6 +140,9 @@ class VIDDemo(object):
         self.output_folder = output_folder
         self.render_chunk = int(render_chunk)
         self.source_kwargs = dict(source_kwargs or {})
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device", got %r' % (decode,))
+        self.decode = decode      # "device": the frames' JPEG pixel stages run in HIP (feed.FrameSource, jpeg.py)
         from .soft_nms import enabled_filter
         self.final = enabled_filter(cfg)        # (ValueError for a bad value, before any device work)
         if self.final is not None and model is None and runner is not None:
@@ -179,10 +182,16 @@ class VIDDemo(object):
 
         def opener(i):
             return np.asarray(Image.open(files[i]).convert("RGB"))
+
+        def reader(i):
+            with open(files[i], "rb") as f:
+                return f.read()
+        how = dict(decode="device", reader=reader) if self.decode == "device" else dict(opener=opener)
+        how.update(self.source_kwargs)
         return feed.FrameSource(os.path.join(os.path.dirname(files[0]), "%s"), "%s", len(files), self.device,
                                 min_size=self.cfg.INPUT.MIN_SIZE_TEST if min_size is None else min_size,
                                 max_size=self.cfg.INPUT.MAX_SIZE_TEST if max_size is None else max_size,
-                                hflip=hflip, opener=opener, **self.source_kwargs)
+                                hflip=hflip, **how)
 
     def _detect(self, src, files):
         v = {"start": 0, "pattern": "%s", "seg_len": len(files)}

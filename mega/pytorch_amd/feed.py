@@ -12,15 +12,23 @@ mega_preprocess_frames).  The in-forward `PIL.Image.open` of the reference's col
 (generalized_rcnn_mega.py:185-191) disappears: every frame goes through the same source.
 
 `FrameSource` is the object ClipEngine.run() accepts in place of a resident clip tensor.
+
+decode="device" (opt-in; jpeg.py defines it) moves the per-pixel half of the JPEG decode to the device as well: the worker
+threads only read the file and entropy-decode it (C++, csrc/jpeg_entropy.h) into int16 DCT coefficients, the pinned staging
+buffers hold coefficients instead of pixels (3 bytes per pixel for 4:2:0, as before), and two HIP launches per batch --
+dequantise + IDCT, then chroma upsampling + YCbCr -> RGB -- produce the same [n,H,W,3] uint8 tensor, bit for bit.
 """
+import io
 import math
 import os
+import threading
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from . import jpeg
 from . import ops
 
 PRECISION_BITS = 32 - 8 - 2
@@ -108,17 +116,44 @@ class FrameSource(object):
 
     img_dir / pattern follow the reference's conventions (`img_dir % (pattern % frame_id)`,
     vid_mega.py:108-109, vid.py `_img_dir`/`pattern`).  fetch(ids) returns the RESIZED uint8 frames [n,H,W,3] on
-    the device, fetch_original(ids) the decoded frames before the resize; prefetch(ids) starts the host decodes early."""
+    the device, fetch_original(ids) the decoded frames before the resize; prefetch(ids) starts the host decodes early.
+
+    decode: "host" (default) decodes every frame with Pillow on the worker threads.  "device" (a HIP device, no `opener`):
+    frame 0 is probed instead of decoded; if it is a JPEG the device decoder accepts (jpeg.py), the workers entropy-decode
+    and the pixels are made on the device -- `decode_mode` is then "device" -- else the source silently becomes a host
+    source (`decode_mode` "host": a folder of PNGs, say).  A later frame that the decoder refuses, or whose sampling differs
+    from frame 0's, is decoded by Pillow and copied into its slot after the kernels; `host_fallbacks` counts such frames.
+    reader: frame id -> the file's bytes, in place of img_dir / pattern (a caller that holds a list of files)."""
 
     def __init__(self, img_dir, pattern, seg_len, device, min_size=600, max_size=1000, workers=8, cache_frames=64,
-                 opener=None, hflip=False):
+                 opener=None, hflip=False, decode="host", reader=None):
         # hflip: every fetched frame is mirrored left-right after the resize (a TEST.BBOX_AUG flip view, bbox_aug.py)
         self.hflip = bool(hflip)
         self.img_dir, self.pattern, self.seg_len = img_dir, pattern, int(seg_len)
         self.device = torch.device(device)
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device", got %r' % (decode,))
+        if decode == "device" and opener is not None:
+            raise ValueError('decode="device" reads the files itself: it cannot be combined with an opener')
+        if decode == "device" and self.device.type != "cuda":
+            raise ValueError('decode="device" needs a HIP device, got %s' % self.device)
+        self.reader = reader
         self.opener = opener or self._open
-        first = self.opener(0)
-        self.in_hw = (first.shape[0], first.shape[1])
+        self.decode_mode = "host"
+        self.jpeg_info = None
+        self._fallback_ids = set()
+        self._lock = threading.Lock()
+        if decode == "device":
+            try:
+                self.jpeg_info = jpeg.probe(self._read(0))
+                self.decode_mode = "device"
+            except jpeg.Unsupported:
+                pass
+        if self.decode_mode == "device":
+            self.in_hw = self.jpeg_info.hw
+        else:
+            first = self.opener(0)
+            self.in_hw = (first.shape[0], first.shape[1])
         self.out_hw = get_size((self.in_hw[1], self.in_hw[0]), min_size, max_size)
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.cache = OrderedDict()
@@ -135,19 +170,54 @@ class FrameSource(object):
         self._copy_stream = None
         self.ahead_hits = 0
 
+    @property
+    def host_fallbacks(self):
+        """frames of a decode="device" source that Pillow had to decode"""
+        return len(self._fallback_ids)
+
+    def _read(self, frame_id):
+        """the bytes of frame `frame_id`'s file"""
+        if self.reader is not None:
+            return self.reader(frame_id)
+        path = self.img_dir % (self.pattern % frame_id)
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        with open(path, "rb") as f:
+            return f.read()
+
     def _open(self, frame_id):
         from PIL import Image
+        if self.reader is not None:
+            return np.asarray(Image.open(io.BytesIO(self.reader(frame_id))).convert("RGB"))
         path = self.img_dir % (self.pattern % frame_id)
         if not os.path.exists(path):
             raise FileNotFoundError(path)
         return np.asarray(Image.open(path).convert("RGB"))
 
     def _decode(self, frame_id):
+        if self.decode_mode == "device":
+            return self._entropy_decode(frame_id)
         a = self.opener(frame_id)
         if a.shape[:2] != self.in_hw:
             raise ValueError("frame %d is %s, the video started as %s" % (frame_id, a.shape[:2], self.in_hw))
         self.decoded += 1
         return a
+
+    def _entropy_decode(self, frame_id):
+        """decode="device", on a worker thread: the frame's int16 coefficient slot [stride] (ctypes releases the GIL around
+        the C++ decoder) -- or, for a frame the decoder refuses, its uint8 RGB [Hi,Wi,3] from Pillow"""
+        data = self._read(frame_id)
+        try:
+            out = ops.jpeg_entropy_decode(data, self.jpeg_info, np.empty(self.jpeg_info.stride, dtype=np.int16))
+        except (jpeg.Unsupported, jpeg.Corrupt):
+            from PIL import Image
+            out = np.array(Image.open(io.BytesIO(data)).convert("RGB"))      # (a corrupt file raises here, as on the host path)
+            if out.shape[:2] != self.in_hw:
+                raise ValueError("frame %d is %s, the video started as %s" % (frame_id, out.shape[:2], self.in_hw))
+            with self._lock:
+                self._fallback_ids.add(frame_id)
+        self.decoded += 1
+        return out
 
     def prefetch(self, ids):
         for f in ids:
@@ -229,6 +299,8 @@ class FrameSource(object):
         """the decoded frames `ids` as ONE uint8 device tensor [n,Hi,Wi,3] (host copies + H2D on the CURRENT stream)"""
         self.prefetch(ids)
         n = len(ids)
+        if self.decode_mode == "device":
+            return self._to_device_coefficients(ids)
         # pinned staging buffers are a small ring per batch size, re-used once the H2D copy that read them has completed
         # (an event per buffer): page-locking a fresh 72 MB buffer per 40-frame batch costs more than the copy it feeds
         ev = None
@@ -269,6 +341,46 @@ class FrameSource(object):
             dev = stage.to(self.device, non_blocking=True)
         if ev is not None:
             ev.record()
+        return dev
+
+    def _to_device_coefficients(self, ids):
+        """_to_device of a decode="device" source: the pinned ring holds int16 coefficient slots [n,stride]; each chunk is
+        copied and then reconstructed (mega_jpeg_reconstruct: two launches) on the CURRENT stream, behind its copy"""
+        n, info = len(ids), self.jpeg_info
+        ring = self._stage.setdefault(n, [])
+        slot = next((x for x in ring if x[1].query()), None)
+        if slot is None and len(ring) >= 3:
+            slot = ring[0]
+            slot[1].synchronize()
+        if slot is None:
+            slot = [torch.empty((n, info.stride), dtype=torch.int16).pin_memory(), torch.cuda.Event()]
+            ring.append(slot)
+        else:
+            ring.remove(slot)
+            ring.append(slot)
+        stage, ev = slot
+        view = stage.numpy()
+        futs = [self.cache.get(int(f)) or self.pool.submit(self._decode, int(f)) for f in ids]
+        late = {}      # position in the batch -> the RGB of a frame Pillow decoded
+
+        def put(i):      # (on the workers, after the decodes: see _to_device)
+            r = futs[i].result()
+            if r.dtype == np.int16:
+                np.copyto(view[i], r)
+            else:
+                view[i].fill(0)      # its slot still goes through the kernels: defined coefficients, a gray frame
+                late[i] = r
+        coef = torch.empty(stage.shape, dtype=torch.int16, device=self.device)
+        dev = torch.empty((n, self.in_hw[0], self.in_hw[1], 3), dtype=torch.uint8, device=self.device)
+        nch = 4 if n >= 8 else 1
+        for c in range(nch):
+            lo, hi = c * n // nch, (c + 1) * n // nch
+            list(self.pool.map(put, range(lo, hi)))
+            coef[lo:hi].copy_(stage[lo:hi], non_blocking=True)
+            ops.jpeg_reconstruct(coef[lo:hi], info, out=dev[lo:hi])
+        ev.record()
+        for i, rgb in sorted(late.items()):
+            dev[i].copy_(torch.from_numpy(rgb))      # (pageable memory: the copy returns when it is done)
         return dev
 
     def close(self):

@@ -181,7 +181,8 @@ def _video_runner(model, steps_per_batch, seed, engine_kwargs):
 
 
 def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_batch=10, seed=0, timer=None,
-                       source_kwargs=None, engine_kwargs=None, bbox_aug_cfg=None, final_filter=None, runner=None):
+                       source_kwargs=None, engine_kwargs=None, bbox_aug_cfg=None, final_filter=None, runner=None,
+                       decode="host"):
     """inference.py:17-47: -> {dataset index: BoxList on the host}, for every MODEL.VID.METHOD of the reference:
       mega / rdn   ClipEngine on the video's FrameSource (RDN is the MEGA detector without memory / global pools: rdn.py).  The
                    engine runs with reuse_records=True unless engine_kwargs says otherwise: every frame of a video goes
@@ -198,9 +199,14 @@ def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_bat
     final_filter: a config.FinalFilter (default: the model's own TEST.SOFT_NMS / TEST.BBOX_VOTE).  When one of its options
     is on, the detections come from soft_nms.py's filter: the views of TEST.BBOX_AUG feed it, and without box augmentation
     the video runs as the identity view alone (candidate mode, one pass).  With both off nothing changes.
-    runner: replaces the engine, run(src, v) -> the video's per-frame outputs (tests without a device)."""
+    runner: replaces the engine, run(src, v) -> the video's per-frame outputs (tests without a device).
+    decode: "host" or "device" -- feed.FrameSource's decode mode of every video (jpeg.py: entropy decoding on the host
+    threads, the pixel stages in HIP; the frames, and so the detections, are the same bit for bit)."""
     model.eval()
     results = {}
+    source_kwargs = dict(source_kwargs or {})
+    if decode != "host":
+        source_kwargs["decode"] = decode
     videos = index.videos if videos is None else videos
     aug_cfg = bbox_aug_cfg if bbox_aug_cfg is not None else _bbox_aug_cfg(model.cfg)
     final = final_filter if final_filter is not None else _final_filter(model.cfg)
@@ -211,7 +217,7 @@ def compute_on_dataset(model, index, img_dir, device, videos=None, steps_per_bat
     for v in videos:
         def source(min_size, max_size, hflip=False):
             return feed.FrameSource(pattern, v["pattern"], v["seg_len"], device, min_size=min_size, max_size=max_size,
-                                    hflip=hflip, **(source_kwargs or {}))
+                                    hflip=hflip, **source_kwargs)
         if aug_cfg is None and final is None:
             src = source(model.cfg.INPUT.MIN_SIZE_TEST, model.cfg.INPUT.MAX_SIZE_TEST)
             t0 = time.perf_counter()
@@ -337,7 +343,8 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     diagnose: None (off), True or a dict of diagnose.evaluate_errors' score_thresh / bg_thresh: with anno_path, after the
     AP the raw detections' error diagnosis (error kinds, GT states and the mAP each error type costs) goes to the log and
     to result_diagnosis.txt, with the motion cross-tabulation when motion_iou is given; result.txt and the return value
-    do not change.  It works on detections: combined with RPN_ONLY it is a ValueError."""
+    do not change.  It works on detections: combined with RPN_ONLY it is a ValueError.
+    decode="device" (through **kw to compute_on_dataset): the frames' JPEG pixel stages run on the device (jpeg.py)."""
     logger = logging.getLogger("mega.pytorch_amd.inference")
     if f8_scales is not None:
         from . import f8

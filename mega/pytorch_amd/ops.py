@@ -1598,3 +1598,66 @@ def overlay_detections(frames, boxes, scores, labels, counts, resized_hw, thr, t
           sx, sy, float(thr), int(thickness), palette, NC, atlas.class_glyphs, ML, atlas.fmt_glyphs, atlas.cells,
           atlas.advances, G, gh, gw, int(bool(select_only)), ws, nb, prof=("overlay",))
     return frames
+
+
+# ------------------------------------------------------------------------------------------------ JPEG decode
+def _host_u8(data):
+    """a bytes-like object in host memory as a uint8 numpy view (no copy): its .ctypes.data is what the C ABI reads"""
+    import numpy as np
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    assert a.dtype == np.uint8 and a.ndim == 1 and a.flags.c_contiguous
+    return a
+
+
+def jpeg_probe(data):
+    """include/mega_hip.h mega_jpeg_probe on the JPEG bytes `data` (host): the int32 info array [12] (jpeg.Info reads it).
+    Raises jpeg.Unsupported for a stream outside the accepted set.  Host only: no device, no stream."""
+    import numpy as np
+    from . import jpeg
+    a = _host_u8(data)
+    info = np.zeros(jpeg.INFO_INTS, dtype=np.int32)
+    if _lib.load().mega_jpeg_probe(a.ctypes.data, a.size, info.ctypes.data) != 0:
+        raise jpeg.Unsupported("not a JPEG this decoder accepts (mega/pytorch_amd/jpeg.py lists the accepted streams)")
+    return info
+
+
+def jpeg_entropy_decode(data, info, out=None):
+    """include/mega_hip.h mega_jpeg_entropy_decode: the quantisation tables and raw int16 DCT coefficients of the JPEG bytes
+    `data` into `out` (a writable, contiguous int16 numpy array of at least info.coef_elems elements -- a slot of a pinned
+    staging buffer, say) or a new array.  info: the jpeg.Info the stream must agree with in size, components and sampling.
+    ctypes releases the GIL around the call.  Raises jpeg.Unsupported (refused, or other frames than info's) or jpeg.Corrupt."""
+    import numpy as np
+    from . import jpeg
+    a = _host_u8(data)
+    if out is None:
+        out = np.empty(info.coef_elems, dtype=np.int16)
+    assert out.dtype == np.int16 and out.ndim == 1 and out.flags.c_contiguous and out.flags.writeable
+    assert out.size >= info.coef_elems
+    lib = _lib.load()
+    if lib.mega_jpeg_entropy_decode(a.ctypes.data, a.size, info.array.ctypes.data, out.ctypes.data, out.size) != 0:
+        got = np.zeros(jpeg.INFO_INTS, dtype=np.int32)
+        if lib.mega_jpeg_probe(a.ctypes.data, a.size, got.ctypes.data) != 0:
+            raise jpeg.Unsupported("not a JPEG this decoder accepts")
+        if not jpeg.Info(got).same_frames(info):
+            raise jpeg.Unsupported("the stream is %s, expected %s" % (tuple(got[:4]), tuple(info.array[:4])))
+        raise jpeg.Corrupt("truncated or corrupt entropy-coded data")
+    return out
+
+
+def jpeg_reconstruct(coef, info, out=None):
+    """include/mega_hip.h mega_jpeg_reconstruct: coef int16 [N, stride] on the device, every row one frame in the layout of
+    jpeg_entropy_decode (stride % 8 == 0, >= info.coef_elems) -> uint8 RGB [N, H, W, 3].  out: optional contiguous tensor of
+    that shape to write into."""
+    assert coef.dtype == torch.int16 and coef.dim() == 2 and coef.is_contiguous()
+    N, stride = coef.shape
+    H, W = info.hw
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=coef.device)
+    else:
+        assert out.shape == (N, H, W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+    nb = _lib.load().mega_jpeg_reconstruct_workspace_bytes(N, H, W, info.sampling)
+    # the component planes: taken like the output, with torch.empty (tests/test_jpeg_gpu.py poisons both through its proxy)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=coef.device)
+    _call("mega_jpeg_reconstruct", coef, stride, N, H, W, info.sampling, out, ws, nb,
+          prof=("jpeg", 0.0, coef.numel() * 2.0 + out.numel() + 2.0 * nb))
+    return out

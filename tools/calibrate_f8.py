@@ -28,6 +28,7 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=8, help="frames per backbone pass")
     ap.add_argument("--out", default="scales.json")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--decode", choices=["host", "device"], default="host", help="device: the JPEG pixel stages run in HIP")
     ap.add_argument("--dry-run", action="store_true")
     a = ap.parse_args(argv)
     if a.max_frames < 1 or a.batch < 1:
@@ -38,7 +39,8 @@ def parse(argv=None):
 def main(argv=None):
     a = parse(argv)
     settings = {"method": a.method, "arch": a.arch, "weights": a.weights, "image_folder": a.image_folder, "suffix": a.suffix,
-                "max_frames": a.max_frames, "batch": a.batch, "out": a.out, "device": a.device}
+                "max_frames": a.max_frames, "batch": a.batch, "out": a.out, "device": a.device,
+                "decode": a.decode}
     if a.dry_run:
         print(json.dumps(dict(settings, dry_run=True)))
         return 0
@@ -60,9 +62,13 @@ def main(argv=None):
     files = demo.VIDDemo.list_frames(a.image_folder, a.suffix)
     n = min(a.max_frames, len(files))
     ids = sorted({int(round(i * (len(files) - 1) / max(n - 1, 1))) for i in range(n)})
+    def reader(i):
+        with open(files[i], "rb") as f:
+            return f.read()
+    how = (dict(decode="device", reader=reader) if a.decode == "device"
+           else dict(opener=lambda i: np.asarray(Image.open(files[i]).convert("RGB"))))
     src = feed.FrameSource(os.path.join(a.image_folder, "%s"), "%s", len(files), dev, min_size=cfg.INPUT.MIN_SIZE_TEST,
-                           max_size=cfg.INPUT.MAX_SIZE_TEST,
-                           opener=lambda i: np.asarray(Image.open(files[i]).convert("RGB")))
+                           max_size=cfg.INPUT.MAX_SIZE_TEST, **how)
     try:
         batches = [src.fetch(ids[o:o + a.batch]).clone() for o in range(0, len(ids), a.batch)]
     finally:

@@ -32,6 +32,8 @@ def parse(argv=None):
     ap.add_argument("--f8-scales", default=None, metavar="FILE", help="run layer3's identity blocks in FP8 (cfg.FP8_CONV "
                     "'layer3'; --dtype bfloat16) with the calibrated scales of this JSON file (tools/calibrate_f8.py)")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--decode", choices=["host", "device"], default="host", help="device: entropy-decode the JPEGs on the "
+                    "host threads and run the pixel stages (IDCT, upsampling, colour) in HIP; same frames bit for bit")
     ap.add_argument("--dry-run", action="store_true", help="print the resolved settings as one JSON line and stop")
     a = ap.parse_args(argv)
     if a.thickness < 1 or a.thickness % 2 == 0:
@@ -46,7 +48,7 @@ def main(argv=None):
     settings = {"method": a.method, "arch": a.arch, "weights": a.weights, "flownet_weights": a.flownet_weights,
                 "image_folder": a.image_folder, "suffix": a.suffix, "output_folder": a.output_folder,
                 "threshold": a.threshold, "thickness": a.thickness, "dtype": a.dtype, "device": a.device,
-                "f8_scales": a.f8_scales}
+                "f8_scales": a.f8_scales, "decode": a.decode}
     if a.dry_run:
         print(json.dumps(dict(settings, dry_run=True)))
         return 0
@@ -68,7 +70,8 @@ def main(argv=None):
     if a.flownet_weights:
         checkpoint.load_checkpoint(cfg, model, a.flownet_weights, flownet=True)
     model.to(torch.device(a.device))
-    d = demo.VIDDemo(cfg, model, confidence_threshold=a.threshold, thickness=a.thickness, output_folder=a.output_folder)
+    d = demo.VIDDemo(cfg, model, confidence_threshold=a.threshold, thickness=a.thickness, output_folder=a.output_folder,
+                      decode=a.decode)
     frames = d.run_on_image_folder(a.image_folder, suffix=a.suffix)
     print(json.dumps(dict(settings, frames=len(frames), detections=sum(len(p) for p in d.predictions),
                           detect_s=round(d.timer["detect_s"], 3), total_s=round(d.timer["total_s"], 3))))
