@@ -67,8 +67,6 @@ the GT-state row and, with motion_iou, two rows per motion range.
 There is no CPU path: one wave per frame classifies (csrc/diagnose.hip), the rows are segment operations on the device,
 the AP is vid_eval's kernel.  A frame holds at most vid_eval.MAX_GT_PER_FRAME GT boxes.
 """
-import logging
-import os
 import warnings
 
 import numpy as np
@@ -261,9 +259,5 @@ def evaluate_errors(predictions, groundtruth, motion_iou=None, score_thresh=SCOR
     res["map"], res["dap"], res["dap_by_class"] = summarize(ap6, ap_cls)
     res["score_thresh"], res["bg_thresh"] = score_thresh, bg_thresh
     res["text"] = format_result(res)
-    (logger or logging.getLogger("mega.pytorch_amd.diagnose")).info("\n" + res["text"])
-    if output_folder:
-        os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, RESULT_NAME), "w") as f:
-            f.write(res["text"])
+    vid_eval.write_result(res["text"], logger, "diagnose", output_folder, RESULT_NAME)
     return res

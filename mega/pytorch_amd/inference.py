@@ -349,31 +349,10 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     if f8_scales is not None:
         from . import f8
         f8.load_scales(model, f8_scales)
+    from . import postrun                                        # (it imports this module)
     box_only = _rpn_only(cfg)
-    if box_only and seq_nms is not None and seq_nms is not False:
-        raise ValueError("MODEL.RPN_ONLY returns proposals: Seq-NMS rescoring (seq_nms=...) needs detections")
-    if box_only and tracks is not None and tracks is not False:
-        raise ValueError("MODEL.RPN_ONLY returns proposals: track linking (tracks=...) needs detections")
-    if box_only and diagnose is not None and diagnose is not False:
-        raise ValueError("MODEL.RPN_ONLY returns proposals: the error diagnosis (diagnose=...) needs detections")
-    if diagnose is not None and diagnose is not False:
-        from . import diagnose as dg
-        diagnose_params = {} if diagnose is True else dict(diagnose)
-        dg.check_params(**diagnose_params)                       # (a bad value raises before the run, not after it)
-    if tracks is not None and tracks is not False:
-        from . import tracks as tr
-        track_params = {} if tracks is True else dict(tracks)
-        tubelet_ap = bool(track_params.pop("tubelet_ap", False))
-        tubelet_score = track_params.pop("tubelet_score", "mean")
-        if tubelet_ap:
-            from . import track_eval
-            track_eval.check_params(tubelet_score=tubelet_score)
-        fill, smooth, fill_scale = tr.check_refine_params(track_params.pop("fill", False), track_params.pop("smooth", 0),
-                                                          track_params.pop("fill_scale", 1.0))
-        tr.check_params(**track_params)                          # (a bad value raises before the run, not after it)
-    if isinstance(motion_iou, dict) or motion_iou == "derive":
-        from . import motion_iou as mi
-        mi.check_request(motion_iou, anno_path)                  # (a bad window raises before the run, not after it)
+    chain = postrun.plan(seq_nms=seq_nms, tracks=tracks, diagnose=diagnose, motion_iou=motion_iou, box_only=box_only,
+                         anno_path=anno_path)                    # (a bad value raises before the run, not after it)
     if box_only and (_bbox_aug_cfg(cfg) is not None or _bbox_aug_cfg(model.cfg) is not None):
         raise ValueError("MODEL.RPN_ONLY returns proposals: TEST.BBOX_AUG merges detections (disable one of the two)")
     final = _final_filter(cfg) or _final_filter(model.cfg)      # (raises ValueError for a bad value, before any device work)
@@ -403,50 +382,5 @@ def inference(cfg, model, img_dir, img_index, output_folder=None, device=None, g
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
         save_predictions(predictions, os.path.join(output_folder, "predictions.pth"))
-    rescored = None
-    if seq_nms is not None and seq_nms is not False:
-        from . import seq_nms as sn
-        params = {} if seq_nms is True else dict(seq_nms)
-        rescored = sn.seq_nms(predictions, [(v["start"], v["seg_len"]) for v in index.videos], device=device, **params)
-        if output_folder:
-            save_predictions(rescored, os.path.join(output_folder, "predictions_seq_nms.pth"))
-    tracked = None
-    refined = False
-    if tracks is not None and tracks is not False:
-        tracked, table = tr.link(predictions if rescored is None else rescored,
-                                 [(v["start"], v["seg_len"]) for v in index.videos], device=device, **track_params)
-        if fill or smooth > 0:                                   # after the linking and its rescoring
-            tracked, info = tr.refine(tracked, [(v["start"], v["seg_len"]) for v in index.videos], fill=fill,
-                                      smooth=smooth, fill_scale=fill_scale, device=device)
-            refined = True
-            logger.info("Refined %d tracks: %d boxes filled", info["tracks"], info["filled"])
-        if output_folder:
-            save_predictions(tracked, os.path.join(output_folder, "predictions_tracks.pth"))
-            with open(os.path.join(output_folder, "tracks.txt"), "w") as f:
-                f.write(tr.format_table(table))
-        logger.info("Linked %d tracks", len(table))
-    if anno_path is not None:
-        from . import vid_eval
-        from . import motion_iou as mi
-        motion_iou, gt = mi.resolve(motion_iou, img_index, anno_path, device=device)     # (a path, lists: as ever)
-        if gt is None:
-            gt = vid_eval.VIDGroundTruth(img_index, anno_path)
-        if box_only:
-            vid_eval.evaluate_proposals(predictions, gt, output_folder=output_folder, device=device, logger=logger)
-            return predictions
-        vid_eval.evaluate_detections(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
-                                     logger=logger)
-        if diagnose is not None and diagnose is not False:
-            dg.evaluate_errors(predictions, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
-                               logger=logger, **diagnose_params)
-        if rescored is not None:
-            vid_eval.evaluate_detections(rescored, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
-                                         logger=logger, result_name="result_seq_nms.txt")
-        if tracked is not None and (track_params.get("rescore") is not None or refined):
-            vid_eval.evaluate_detections(tracked, gt, motion_iou=motion_iou, output_folder=output_folder, device=device,
-                                         logger=logger, result_name="result_tracks.txt")
-        if tracked is not None and tubelet_ap:
-            track_eval.evaluate_tracks(tracked, vid_eval.VIDTrackGroundTruth(img_index, anno_path),
-                                       [(v["start"], v["seg_len"]) for v in index.videos], tubelet_score=tubelet_score,
-                                       output_folder=output_folder, device=device, logger=logger)
+    rescored = postrun.run(chain, predictions, img_index, anno_path, output_folder, device, logger=logger)["rescored"]
     return predictions if rescored is None else rescored

@@ -42,7 +42,7 @@ from .structures import BoxList
 RESCORE_MODES = ("avg", "max")
 
 
-def check_params(link_iou, nms_iou, rescore):
+def check_params(link_iou=0.5, nms_iou=0.3, rescore="avg"):
     if rescore not in RESCORE_MODES:
         raise ValueError("seq_nms: rescore must be one of %s, got %r" % (RESCORE_MODES, rescore))
     for name, v in (("link_iou", link_iou), ("nms_iou", nms_iou)):

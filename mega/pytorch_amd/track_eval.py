@@ -56,8 +56,6 @@ There is no CPU path: one workgroup per (video, label) task that has a tubelet a
 hits and matches (csrc/track_eval.hip); tubelet scores, ranks and the per-label order are segment operations on the
 device; the AP is vid_eval's kernel.  A (video, label) holds at most 4096 GT tracks.
 """
-import logging
-import os
 import warnings
 
 import numpy as np
@@ -370,10 +368,6 @@ def evaluate_tracks(predictions, groundtruth, videos, thresholds=THRESHOLDS, tub
     r = run(predictions, groundtruth, videos, thresholds, tubelet_score, device, pairs=False)
     maps, mean = summarize(r["ap"])
     text = format_result(r["thresholds"], r["ap"])
-    (logger or logging.getLogger("mega.pytorch_amd.track_eval")).info("\n" + text)
-    if output_folder:
-        os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "result_tubelets.txt"), "w") as f:
-            f.write(text)
+    vid_eval.write_result(text, logger, "track_eval", output_folder, "result_tubelets.txt")
     return {"thresholds": r["thresholds"], "ap": r["ap"], "map": maps, "mean": mean, "gt_table": r["gt_table"],
             "tubelets": r["tubelets"], "text": text}

@@ -256,6 +256,16 @@ def format_result(result, classes=CLASSES, motion_names=None):
     return s
 
 
+def write_result(text, logger, module, output_folder, file_name, lead="\n"):
+    """How every evaluation of the package ends: `text` goes to the log (`logger`, or the logger of the package's `module`)
+    behind `lead`, and to <output_folder>/<file_name> when a folder is given."""
+    (logger or logging.getLogger("mega.pytorch_amd." + module)).info(lead + text)
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+        with open(os.path.join(output_folder, file_name), "w") as f:
+            f.write(text)
+
+
 def _resize_ratios(predictions, groundtruth):
     """[F,2] f32 (width, height): BoxList.resize (bounding_box.py:95) to the annotation's frame size -- ratios as Python
     floats, applied in f32."""
@@ -381,12 +391,7 @@ def evaluate_detections(predictions, groundtruth, motion_iou=None, output_folder
         warnings.simplefilter("ignore", RuntimeWarning)     # nanmean of an all-NaN row is NaN, as in the reference
         for ri in range(len(motion_ranges)):
             result[ri] = {"ap": ap[ri].copy(), "map": np.nanmean(ap[ri])}
-    text = format_result(result)
-    (logger or logging.getLogger("mega.pytorch_amd.vid_eval")).info("\n" + text)
-    if output_folder:
-        os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, result_name), "w") as fid_:
-            fid_.write(text)
+    write_result(format_result(result), logger, "vid_eval", output_folder, result_name)
     return result
 
 
@@ -490,20 +495,11 @@ def evaluate_proposals(predictions, groundtruth, iou_thresh=0.5, limit=300, limi
         return np.float32(n) / np.float32(num_pos) if num_pos else np.float32(np.nan)
     out = {"recall": rec(hits[0, 0]), "num_pos": num_pos, "gt_overlaps": ov[0].cpu().numpy(),
            "gt_prop": prop[0].cpu().numpy()}
-    text = "Recall: {:.4f}".format(out["recall"])
-    log = logger or logging.getLogger("mega.pytorch_amd.vid_eval")
-    log.info(text)
-    if output_folder:
-        os.makedirs(output_folder, exist_ok=True)
-        with open(os.path.join(output_folder, "proposal_result.txt"), "w") as fid_:
-            fid_.write(text)
+    write_result("Recall: {:.4f}".format(out["recall"]), logger, "vid_eval", output_folder, "proposal_result.txt", lead="")
     if want_table:
         table = np.asarray([[rec(hits[launch.index(l), 1 + ti]) for ti in range(len(tt))] for l in tl], np.float32)
         ar = table.mean(axis=1, dtype=np.float32)
         out.update({"limits": tl, "iou_thresholds": tt, "table": table, "ar": ar})
-        ttext = format_recall_table(tl, tt, table, ar, num_pos)
-        log.info("\n" + ttext)
-        if output_folder:
-            with open(os.path.join(output_folder, "proposal_recall_table.txt"), "w") as fid_:
-                fid_.write(ttext)
+        write_result(format_recall_table(tl, tt, table, ar, num_pos), logger, "vid_eval", output_folder,
+                     "proposal_recall_table.txt")
     return out

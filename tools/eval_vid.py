@@ -48,7 +48,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--predictions", required=True, help="predictions.pth (list[BoxList])")
     ap.add_argument("--img-index", required=True, help="the 4-column VID index file the predictions were made on")
@@ -92,110 +92,75 @@ def main(argv=None):
     ap.add_argument("--box-only", action="store_true", help="proposal recall of RPN-only predictions (proposal_result.txt)")
     ap.add_argument("--limit", type=int, default=300, help="--box-only: proposals used per frame (at most 1024)")
     ap.add_argument("--recall-table", action="store_true", help="--box-only: also the recall per limit and IoU threshold")
+    return ap
+
+
+# how this tool words postrun.ProposalOnly, by the option it names
+APPLIES = {"seq_nms": "--seq-nms / --motion-iou apply to detections", "tracks": "--tracks applies to detections",
+           "tubelet_ap": "--tubelet-ap applies to tracks", "diagnose": "--diagnose applies to detections"}
+
+
+def build_plan(argv=None):
+    """The command line -> (the parsed arguments, their postrun.Plan); an argument error exits with status 2."""
+    ap = _parser()
     a = ap.parse_args(argv)
-    if a.box_only and (a.seq_nms or a.motion_iou):
-        ap.error("--box-only evaluates proposals: --seq-nms / --motion-iou apply to detections")
-    if a.box_only and a.tracks:
-        ap.error("--box-only evaluates proposals: --tracks applies to detections")
-    if a.box_only and a.tubelet_ap:
-        ap.error("--box-only evaluates proposals: --tubelet-ap applies to tracks")
-    if a.box_only and a.diagnose:
-        ap.error("--box-only evaluates proposals: --diagnose applies to detections")
+    derive = a.motion_iou == "derive"
+    if a.box_only and a.motion_iou:
+        ap.error("--box-only evaluates proposals: " + APPLIES["seq_nms"])
     if not a.diagnose and (a.diagnose_score_thresh is not None or a.diagnose_bg_thresh is not None):
         ap.error("--diagnose-score-thresh / --diagnose-bg-thresh apply to --diagnose")
-    if a.diagnose:
-        from mega.pytorch_amd import diagnose
-        try:
-            diag = diagnose.check_params(diagnose.SCORE_THRESH if a.diagnose_score_thresh is None else a.diagnose_score_thresh,
-                                         diagnose.BG_THRESH if a.diagnose_bg_thresh is None else a.diagnose_bg_thresh)
-        except ValueError as e:
-            ap.error(str(e))
     if not a.tracks and (a.tracks_fill or a.tracks_smooth is not None or a.tracks_fill_scale is not None):
         ap.error("--tracks-fill / --tracks-smooth / --tracks-fill-scale refine linked tracks: they need --tracks")
-    if a.tracks:
-        from mega.pytorch_amd import tracks
-        try:
-            refine = tracks.check_refine_params(a.tracks_fill, 0 if a.tracks_smooth is None else a.tracks_smooth,
-                                                1.0 if a.tracks_fill_scale is None else a.tracks_fill_scale)
-        except ValueError as e:
-            ap.error(str(e))
-    derive = a.motion_iou == "derive"
     if not derive and (a.motion_window is not None or a.save_motion_iou):
         ap.error("--motion-window / --save-motion-iou apply to --motion-iou derive")
     if derive and a.motion_window is not None and not 1 <= a.motion_window <= 64:
         ap.error("--motion-window must be in 1 .. 64, got %d" % a.motion_window)
-    from mega.pytorch_amd import inference, vid_eval
+
+    def given(**kw):
+        return {k: v for k, v in kw.items() if v is not None}
+    options = {
+        "seq_nms": a.seq_nms and {"link_iou": a.seq_nms_link_iou, "nms_iou": a.seq_nms_iou, "rescore": a.seq_nms_rescore},
+        "tracks": a.tracks and given(score_thresh=a.tracks_score_thresh, link_iou=a.tracks_link_iou,
+                                     max_gap=a.tracks_max_gap, min_len=a.tracks_min_len, fill=a.tracks_fill,
+                                     rescore=None if a.tracks_rescore == "none" else a.tracks_rescore,
+                                     smooth=a.tracks_smooth, fill_scale=a.tracks_fill_scale),
+        "tubelet_score": a.tubelet_score if a.tubelet_ap else None,
+        "diagnose": a.diagnose and given(score_thresh=a.diagnose_score_thresh, bg_thresh=a.diagnose_bg_thresh),
+        "motion_iou": given(derive=True, window=a.motion_window) if derive else a.motion_iou}
+    from mega.pytorch_amd import postrun
+    try:
+        plan = postrun.plan(box_only=a.box_only, limit=a.limit, recall_table=a.recall_table, cache=a.cache,
+                            save_motion_iou=a.save_motion_iou, anno_path=a.anno_path, **options)
+    except postrun.ProposalOnly as e:
+        ap.error("--box-only evaluates proposals: " + APPLIES[e.option])
+    except ValueError as e:
+        ap.error(str(e))
+    return a, plan
+
+
+def main(argv=None):
+    a, plan = build_plan(argv)
+    from mega.pytorch_amd import inference, postrun, vid_eval
     preds = inference.load_predictions(a.predictions)
-    if a.tubelet_ap and not a.tracks and not all(p.has_field("track_ids") for p in preds):
-        ap.error("--tubelet-ap without --tracks needs predictions with the field \"track_ids\" (predictions_tracks.pth)")
-    if a.tubelet_ap or derive:      # (the same boxes and labels, plus each object's <trackid>; its cache holds the ids too)
-        gt = vid_eval.VIDTrackGroundTruth(a.img_index, a.anno_path, cache=a.cache)
-    else:
-        gt = vid_eval.VIDGroundTruth(a.img_index, a.anno_path, cache=a.cache)
-    if derive:
-        from mega.pytorch_amd import motion_iou
-        motion = motion_iou.derive(gt, inference.VIDTestIndex(a.img_index).videos,
-                                   motion_iou.WINDOW if a.motion_window is None else a.motion_window, device=a.device)
-        if a.save_motion_iou:
-            motion_iou.save_mat(a.save_motion_iou, motion, off=gt.off)
-    else:
-        motion = vid_eval.load_motion_iou(a.motion_iou) if a.motion_iou else None
+    if plan.tubelet_score is not None and plan.tracks is None and not all(p.has_field("track_ids") for p in preds):
+        _parser().error("--tubelet-ap without --tracks needs predictions with the field \"track_ids\" "
+                        "(predictions_tracks.pth)")
+
+    def report(title, res):
+        if title == "Recall":
+            sys.stdout.write("Recall: {:.4f}\n".format(res["recall"]))
+            if plan.recall_table:
+                sys.stdout.write(vid_eval.format_recall_table(res["limits"], res["iou_thresholds"], res["table"], res["ar"],
+                                                              res["num_pos"]))
+        elif title == "Tracks":
+            sys.stdout.write("Tracks: %d\n" % len(res["table"]))
+            if res["refine_info"] is not None:
+                sys.stdout.write("Filled boxes: %d\n" % res["refine_info"]["filled"])
+        else:
+            text = res["text"] if "text" in res else vid_eval.format_result(res)
+            sys.stdout.write((title + ":\n" if title else "") + text)
     out = a.output_folder or os.path.dirname(os.path.abspath(a.predictions))
-    if a.box_only:
-        res = vid_eval.evaluate_proposals(preds, gt, limit=a.limit, output_folder=out, device=a.device,
-                                          limits=vid_eval.PROPOSAL_LIMITS if a.recall_table else None)
-        sys.stdout.write("Recall: {:.4f}\n".format(res["recall"]))
-        if a.recall_table:
-            sys.stdout.write(vid_eval.format_recall_table(res["limits"], res["iou_thresholds"], res["table"], res["ar"],
-                                                          res["num_pos"]))
-        return 0
-    res = vid_eval.evaluate_detections(preds, gt, motion_iou=motion, output_folder=out, device=a.device)
-    sys.stdout.write(vid_eval.format_result(res))
-    if a.diagnose:
-        res = diagnose.evaluate_errors(preds, gt, motion_iou=motion, score_thresh=diag[0], bg_thresh=diag[1],
-                                       output_folder=out, device=a.device)
-        sys.stdout.write("Diagnosis:\n" + res["text"])
-    if a.seq_nms:
-        from mega.pytorch_amd import seq_nms
-        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
-        rescored = seq_nms.seq_nms(preds, videos, link_iou=a.seq_nms_link_iou, nms_iou=a.seq_nms_iou,
-                                   rescore=a.seq_nms_rescore, device=a.device)
-        os.makedirs(out, exist_ok=True)
-        inference.save_predictions(rescored, os.path.join(out, "predictions_seq_nms.pth"))
-        res = vid_eval.evaluate_detections(rescored, gt, motion_iou=motion, output_folder=out, device=a.device,
-                                           result_name="result_seq_nms.txt")
-        sys.stdout.write("Seq-NMS:\n" + vid_eval.format_result(res))
-        preds = rescored
-    if a.tracks:
-        from mega.pytorch_amd import tracks
-        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
-        rescore = None if a.tracks_rescore == "none" else a.tracks_rescore
-        tracked, table = tracks.link(preds, videos, score_thresh=a.tracks_score_thresh, link_iou=a.tracks_link_iou,
-                                     max_gap=a.tracks_max_gap, min_len=a.tracks_min_len, rescore=rescore, device=a.device)
-        refined = refine[0] or refine[1] > 0
-        if refined:
-            tracked, info = tracks.refine(tracked, videos, fill=refine[0], smooth=refine[1], fill_scale=refine[2],
-                                          device=a.device)
-        os.makedirs(out, exist_ok=True)
-        inference.save_predictions(tracked, os.path.join(out, "predictions_tracks.pth"))
-        with open(os.path.join(out, "tracks.txt"), "w") as f:
-            f.write(tracks.format_table(table))
-        sys.stdout.write("Tracks: %d\n" % len(table))
-        if refined:
-            sys.stdout.write("Filled boxes: %d\n" % info["filled"])
-        if rescore is not None or refined:
-            res = vid_eval.evaluate_detections(tracked, gt, motion_iou=motion, output_folder=out, device=a.device,
-                                               result_name="result_tracks.txt")
-            sys.stdout.write("Tracks, %s:\n" % " and ".join(w for w, on in (("rescored", rescore is not None),
-                                                                             ("refined", refined)) if on)
-                             + vid_eval.format_result(res))
-        preds = tracked
-    if a.tubelet_ap:
-        from mega.pytorch_amd import track_eval
-        videos = [(v["start"], v["seg_len"]) for v in inference.VIDTestIndex(a.img_index).videos]
-        res = track_eval.evaluate_tracks(preds, gt, videos, tubelet_score=a.tubelet_score, output_folder=out,
-                                         device=a.device)
-        sys.stdout.write("Tubelets:\n" + res["text"])
+    postrun.run(plan, preds, a.img_index, a.anno_path, out, a.device, report=report)
     return 0
 
 
